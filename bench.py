@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: trajectory-steps/s of the MPPI iteration (BASELINE.json `metric`).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4|c5] [--no-cpu-baseline] [--no-batched] [--no-graph-timing]
+    python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4|c5] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-batched] [--no-graph-timing]]
 
 A "step" is one closed-loop MPPI iteration (sample -> rollout -> cost -> softmin weight -> reduce ->
 filter -> shift, then the driver's plant advances the state).  Default workload `c2` = BASELINE config 2:
@@ -25,12 +26,19 @@ obstacles, K = 65536 samples x T = 75 in TOTAL, K/N per GPU (strong scaling), sa
 tanh], Linear 512-3; train/train_diff_mlp.py:13-36) on the matrix cores, K = 32768 samples x T = 50 in TOTAL, K/N per GPU
 (strong scaling), frozen waypoint index; its `roofline` is the MFMA one.
 
-The default line also carries `batched_agents`: 32 independent config-2 problems in ONE handle (agents as a grid
-dimension) -- the launch size at which the chip, not the launch, is the limit.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps iterations and prints the headline
+figure (`value`, `ms_per_step`); nothing else runs on the GPU or the host.  `--full` adds the figures that take runs of
+their own: `phase_latency_us`, `host_in_loop_latency_us`, `roofline` (measured live with HIP events on the launch
+stream, over whole episodes of fixed length whatever --steps is, see `kernel_duration`), config 4's
+`strong_scaling_bound`, and at config 2 `batched_agents` (32 independent config-2 problems in ONE handle, agents as a
+grid dimension, SURVEY.md section 8 f1 -- the launch size at which the chip, not the launch, is the limit) and
+`cpu_baseline` (the plain-C oracle, test infrastructure, oracle/mppi_oracle.c, timed on the host, rank 0 at N=1 only --
+the only place this file touches `oracle/`).
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on the launch stream, over whole episodes
-of fixed length whatever --steps is (see `kernel_duration`); `cpu_baseline` is the plain-C oracle (test
-infrastructure, oracle/mppi_oracle.c) timed on the host, rank 0 at N=1 only -- the only place this file touches `oracle/`.
+`--dump-outputs DIR` writes, after the timed steps, what the timed path left its caller after its last iteration
+(rank 0's handle): DIR/state.npy, u_prev.npy (the nominal control sequence), costs.npy (S of every sample),
+waypoint_idx.npy and softmin.npy ({rho, eta, ess}), all float64.  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -282,6 +290,19 @@ def stamped_profile(name, build_id):
     return d, f"profiles/{PROFILE_ROUND}_{name}.json (build {build_id})"
 
 
+def timed_outputs(eng):
+    """What the timed path left its caller after its last iteration (read back once the timing has ended)."""
+    st = eng.stats
+    return {"state": eng.get_state(), "u_prev": eng.get_u_prev(), "costs": eng.costs(),
+            "waypoint_idx": np.array([st.idx_after], dtype=np.float64), "softmin": np.array([st.rho, st.eta, st.ess])}
+
+
+def write_outputs(out_dir, outputs):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def eps_hbm_line(args):
     """`--eps hbm`: the form of the analytic path north_star calls memory-bound -- the noise tensor of `_calc_epsilon`
     (mppi_differential_drive.py:273-283) MATERIALISED in HBM and read by the rollout as coalesced [K, T, 2] rows, instead of
@@ -349,6 +370,8 @@ def eps_hbm_line(args):
         run(8)
         run(max(1, warm))
         dt = timed(steps)
+        if mode == "hbm" and args.dump_outputs:  # (the timed path of the line: the noise read from HBM)
+            write_outputs(args.dump_outputs, timed_outputs(eng))
         eng.enable_timing(True)
         run(min(steps, 400))
         kms = eng.last_kernel_ms()
@@ -463,11 +486,16 @@ def main():
     ap.add_argument("--eps", choices=["philox", "hbm"], default="philox",
                     help="hbm: the noise tensor materialised in HBM and read by the rollout (one GPU, --workload c2 = 32 batched "
                          "config-2 agents, or c4); see eps_hbm_line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-batched", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last iteration as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: phase and host-in-the-loop latencies, "
+                         "roofline, strong-scaling bound, batched agents, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-batched", action="store_true", help="with --full: skip the batched agents")
     ap.add_argument("--no-graph-timing", action="store_true",
-                    help="skip the graph-replay measurement of the rollout launch (the profiler passes: counter collection "
-                         "and graph replays do not go together)")
+                    help="with --full: skip the graph-replay measurement of the rollout launch (the profiler passes: counter "
+                         "collection and graph replays do not go together)")
     args = ap.parse_args()
     c5 = args.workload == "c5"
     c3 = args.workload == "c3"
@@ -601,6 +629,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         idx_timed = int(eng.stats.idx_after)
+        outputs = timed_outputs(eng) if (args.dump_outputs and rank == 0) else None
+        if not args.full:
+            return ctrl, eng, dt, idx_timed, outputs, None, None, None, None, None
 
         def phase(n_skip, n, reps=1):  # wall time per iteration of iterations [n_skip, n_skip + n) of an episode
             ts = []                      # (one call of n iterations, its fixed cost included; median of `reps` episodes)
@@ -664,10 +695,10 @@ def main():
             except pkg.MppiError:
                 graph = None
         kms = dict(kms, graph=graph, ran=eng.rollout_kernel())
-        return ctrl, eng, dt, idx_timed, k1, k2, n_kernel_iters, kms, phases
+        return ctrl, eng, dt, idx_timed, outputs, k1, k2, n_kernel_iters, kms, phases
 
     try:
-        ctrl, eng, dt, idx_timed, k1, k2, n_kernel_iters, kms, phases = measure()
+        ctrl, eng, dt, idx_timed, outputs, k1, k2, n_kernel_iters, kms, phases = measure()
     except pkg.MppiError as ex:
         # the peer-to-peer exchange lost a rank (every rank then fails within its timeout): measure again with the
         # one collective per iteration instead
@@ -675,11 +706,11 @@ def main():
             raise
         os.environ["MPPI_EXCHANGE"] = "rccl"  # (falls through to the torch.distributed collective if RCCL cannot be set up)
         barrier()
-        ctrl, eng, dt, idx_timed, k1, k2, n_kernel_iters, kms, phases = measure()
+        ctrl, eng, dt, idx_timed, outputs, k1, k2, n_kernel_iters, kms, phases = measure()
 
     # host-in-the-loop latency: x0 from the host, u0 back to the host every iteration
     lat = None
-    if not sharded and not c3 and not c4 and not c5:
+    if args.full and not sharded and not c3 and not c4 and not c5:
         import contextlib
         import io
         state = eng.get_state()
@@ -693,8 +724,8 @@ def main():
                 state = state + 0.1 * np.array([u0[0] * np.cos(state[2]), u0[0] * np.sin(state[2]), u0[1]])
         lat = float(np.median(ts))
 
-    if rank == 0:
-        units = K_global * T
+    def roofline(build_id):
+        """`roofline` of the --full line: the rollout launch's live duration (measure()) against the roof that binds it."""
         # ALGORITHMIC HBM bytes (SURVEY.md section 8d): 16 B per trajectory-step (two passes over the f32
         # noise: rollout, weighted reduce) + 8 B per trajectory (S out, S in).  The fused rollout kernel does BOTH
         # passes in one launch (the noise stays in registers), so one launch owns the whole figure.
@@ -725,7 +756,6 @@ def main():
             method = ("per-launch event pairs minus the empty-pair calibration (excludes dispatch) -- fallback: the "
                       "marginal measurement was not usable here (launch counts %d/%d, regions %.3f/%.3f ms)"
                       % (l1, l2, 1e3 * t1x, 1e3 * t2x))
-        build_id = pkg.source_id()
         frac = alg_bytes / t_roll / 1e9 / HBM_PEAK_GBS if t_roll > 0 else None
         if frac is not None and not (0.0 < frac <= 1.0):  # never report more than the roof: say what was seen instead
             method += "; REJECTED (implied %.3g of the HBM peak)" % frac
@@ -820,6 +850,11 @@ def main():
                 roof["valu_issue_frac"] = min(1.0, issue_us / (1e6 * t_roll))
                 roof["valu_issue"] = {"valu_instructions_per_wave": per_wave, "waves_per_simd": wps, "issue_us": issue_us,
                                       "shader_clock_GHz": SHADER_GHZ, "source": pk_why, "vgprs": pk.get("vgprs")}
+        return roof
+
+    if rank == 0:
+        units = K_global * T
+        build_id = pkg.source_id()
         out = {"metric": "trajectory-steps/sec (KxT/iter_time), " + ("diff-drive + learned MLP dynamics K=32768 T=50" if c5 else
                                                                      "diff-drive + 8 circular obstacles K=16384 T=50" if c3 else
                                                                      "race-car K=65536 T=75" if c4 else "diff-drive K=4096 T=50"),
@@ -854,17 +889,20 @@ def main():
                           "exchange": {"none": "none (one GPU)", "p2p": "peer-to-peer stores + flags inside k_finalize",
                                        "rccl": "one ncclAllGather per iteration enqueued by the library (mppi_comm_init)",
                                        "collective": "one all-gather per iteration (torch.distributed, RCCL)"}[ctrl.exchange]},
-               "iter_latency_us": 1e6 * dt / args.steps,
-               "phase_latency_us": None if phases is None else
-                                   {"traverse (first %d iterations of an episode, one call, median of 9 episodes)" % traverse: 1e6 * phases["traverse"],
-                                    "hold (second half of an episode)": 1e6 * phases["hold"]},
-               "host_in_loop_latency_us": None if lat is None else 1e6 * lat,
-               "roofline": roof}
-        if world == 1 and c4:
+               "iter_latency_us": 1e6 * dt / args.steps}
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
+        if args.full:
+            out["phase_latency_us"] = None if phases is None else {
+                "traverse (first %d iterations of an episode, one call, median of 9 episodes)" % traverse: 1e6 * phases["traverse"],
+                "hold (second half of an episode)": 1e6 * phases["hold"]}
+            out["host_in_loop_latency_us"] = None if lat is None else 1e6 * lat
+            out["roofline"] = roofline(build_id)
+        if args.full and world == 1 and c4:
             out["strong_scaling_bound"] = strong_scaling_bound_c4(1e-3 * out["ms_per_step"])
-        if world == 1 and not c3 and not c4 and not c5 and not args.no_batched:
+        if args.full and world == 1 and not c3 and not c4 and not c5 and not args.no_batched:
             out["batched_agents"] = batched_agents()
-        if world == 1 and not c3 and not c4 and not c5 and not args.no_cpu_baseline:  # (the C restatement timed is config 2's)
+        if args.full and world == 1 and not c3 and not c4 and not c5 and not args.no_cpu_baseline:  # (the C restatement timed is config 2's)
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     if sharded:

@@ -1,19 +1,14 @@
 """CPU: the residual-MLP restatement (config 5's oracle)."""
-import os
-
 import numpy as np
-import pytest
 
 from oracle import mppi_oracle as mo
 
-CKPT = "/root/reference/saved_models/mlp_diff_300x100_3l.pth"
 
-
-@pytest.mark.skipif(not os.path.exists(CKPT), reason="reference checkpoint only exists in the build container")
 def test_mlp_forward_matches_torch_on_the_reference_checkpoint():
+    """The checkpoint mlp_diff_300x100_3l, stored bit for bit as arrays in tests/golden (oracle/gen_golden.py)."""
     import torch
-    sd = torch.load(CKPT, map_location="cpu", weights_only=True)  # loader that executes nothing from the file
-    w = {k: v.numpy() for k, v in sd.items()}
+    import golden_util as gu
+    w = gu.mlp_weights()
     assert w["input_layer.weight"].shape == (512, 5) and w["out_layer.weight"].shape == (3, 512)
     z = np.random.default_rng(0).normal(size=(33, 5))
     x = torch.tensor(z)

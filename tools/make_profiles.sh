@@ -13,7 +13,7 @@ OUT="gpurun_out/prof_${R}"
 mkdir -p "$OUT"
 find "$OUT" -mindepth 1 -delete
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-Q="--no-cpu-baseline --no-batched --no-graph-timing"
+Q="--full --no-cpu-baseline --no-batched --no-graph-timing"
 declare -A CMD
 CMD[c2]="bench.py --steps 2000 --warmup 200 $Q"
 CMD[c3]="bench.py --workload c3 --steps 600 --warmup 60 $Q"
@@ -56,17 +56,17 @@ reduce pmc_mfma2_c5
 echo "== counter summaries -> profiles/${R}_pmc.json (on the box: the bench lines below quote them)"; date
 python3 tools/collect_profiles.py "$R" --on-box || echo "collect failed"
 echo "== bench lines"; date
-timeout -k 10 300 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || echo "bench failed"
-timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_steps20.json" 2>> "$OUT/bench.err" || echo "bench20 failed"
-timeout -k 10 300 python3 bench.py --workload c3 --steps 1000 --warmup 100 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" || echo "bench c3 failed"
-timeout -k 10 300 python3 bench.py --workload c4 --steps 300 --warmup 30 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err" || echo "bench c4 failed"
-timeout -k 10 300 python3 bench.py --workload c5 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" || echo "bench c5 failed"
-MPPI_MLP_TERMS=2 timeout -k 10 300 python3 bench.py --workload c5 --no-cpu-baseline > "$OUT/bench_c5_two_terms.json" 2> "$OUT/bench_c5_two_terms.err" || echo "bench c5 (two terms) failed"
+timeout -k 10 300 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || echo "bench failed"
+timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_steps20.json" 2>> "$OUT/bench.err" || echo "bench20 failed"
+timeout -k 10 300 python3 bench.py --full --workload c3 --steps 1000 --warmup 100 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" || echo "bench c3 failed"
+timeout -k 10 300 python3 bench.py --full --workload c4 --steps 300 --warmup 30 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err" || echo "bench c4 failed"
+timeout -k 10 300 python3 bench.py --full --workload c5 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" || echo "bench c5 failed"
+MPPI_MLP_TERMS=2 timeout -k 10 300 python3 bench.py --full --workload c5 --no-cpu-baseline > "$OUT/bench_c5_two_terms.json" 2> "$OUT/bench_c5_two_terms.err" || echo "bench c5 (two terms) failed"
 timeout -k 10 300 python3 bench.py --eps hbm --workload c2 > "$OUT/bench_eps_c2.json" 2> "$OUT/bench_eps_c2.err" || echo "bench eps c2 failed"
 timeout -k 10 300 python3 bench.py --eps hbm --workload c4 > "$OUT/bench_eps_c4.json" 2> "$OUT/bench_eps_c4.err" || echo "bench eps c4 failed"
 echo "== self-launched 2-rank rehearsals (one GPU, gloo host side)"; date
 for W in c2 c4; do
-  MPPI_BENCH_DEVICE=0 MPPI_BENCH_BACKEND=gloo timeout -k 10 300 python3 bench.py --gpus 2 --workload $W --steps 200 --warmup 20 > "$OUT/bench_2rank_$W.json" 2> "$OUT/bench_2rank_$W.err" || echo "2-rank $W failed"
+  MPPI_BENCH_DEVICE=0 MPPI_BENCH_BACKEND=gloo timeout -k 10 300 python3 bench.py --full --gpus 2 --workload $W --steps 200 --warmup 20 > "$OUT/bench_2rank_$W.json" 2> "$OUT/bench_2rank_$W.err" || echo "2-rank $W failed"
 done
 echo "== parity margins"; date
 timeout -k 10 300 python3 -m pytest tests -m gpu -q -s -k "config5_checkpoint or two_term" 2>&1 | grep PARITY_MARGIN > "$OUT/parity_margins.txt"
