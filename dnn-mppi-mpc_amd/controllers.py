@@ -422,6 +422,11 @@ class MPPIAlgorithms(_ControllerBase):
     ``variant``: "numpy" (the CPU file, default), "cuda" (SEARCH_IDX_LEN 10 + terminal yaw wrap,
     mppi_differential_drive_cuda.py:201,:239) or "torch" (no clamp in the rollout, beta = lambda,
     terminal yaw wrap, mppi_differential_drive_torch.py:128,:187,:231).
+
+    ``learned_dynamics``: the residual model x + dt (f(x, v) + MLP([x, v])) as a ``state_dict`` (or the torch module) with
+    the keys ``input_layer.*``, ``hidden_layer.{i}.*``, ``out_layer.*``: Linear(5, H) -> n x [Linear(H, H), tanh] ->
+    Linear(H, 3) with H in {64, 128, 256, 512} and n in {1, 2, 3, 4} (`Engine.SUPPORTED_MLP`); ``learned_scalers``: its
+    ``StandardScaler`` statistics (`Engine.set_mlp`).
     """
 
     def __init__(self, delta_t, ref_path, max_speed, max_omega, num_samples_K, num_horizons_T, param_exploration,

@@ -39,7 +39,8 @@ struct mppi_handle {
     void *d_partials2 = nullptr;    // second level for large K (records merged 64:1)
     void *d_heads = nullptr, *d_heads2 = nullptr;  // compact {rho, eta, eta2, 0} of d_partials / d_partials2
     float *d_mlp = nullptr;         // packed residual-model weights (config 5)
-    unsigned short *d_mlp16 = nullptr;  // the same as f16 hi / lo planes (k_rollout_mlp_h3)
+    unsigned short *d_mlp16 = nullptr;  // the same as f16 hi / lo planes (k_rollout_mlp_h3, k_rollout_mlp_w)
+    size_t mlp_cap = 0, mlp16_cap = 0;  // their sizes in elements
     // one-launch resolution of the sequential waypoint index (LB_CAND in mppi_kernels.h)
     bool hyp = false;
     unsigned *d_hyp_slots = nullptr;  // one look-back word per workgroup (LB_COPIES copies)
@@ -369,59 +370,91 @@ extern "C" int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m) 
     return upload_real(h, h->d_obs, packed.data(), packed.size());
 }
 
+// (the caller has synchronised the device: no instance is running)
+static void drop_graph(mppi_handle *h) {
+    for (int i = 0; i < 2; ++i) {
+        if (h->graph_exec[i]) (void)hipGraphExecDestroy(h->graph_exec[i]);
+        h->graph_exec[i] = nullptr;
+    }
+    h->graph_key.clear();
+}
+
+#define MLP_SUPPORTED_SET "hidden H in {64, 128, 256, 512} x n_hidden in {1, 2, 3, 4}"
+
 extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, const float *w_in, const float *b_in,
                             const float *const *w_hidden, const float *const *b_hidden, const float *w_out,
                             const float *b_out) {
     if (!h || !w_in || !b_in || !w_hidden || !b_hidden || !w_out || !b_out)
         FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_mlp: null argument");
     if (h->cfg.model != MPPI_MODEL_DIFFDRIVE_MLP) FAIL(h, MPPI_ERR_STATE, "mppi_set_mlp needs MPPI_MODEL_DIFFDRIVE_MLP");
-    if (hidden != 512 || (n_hidden != 3 && n_hidden != 2))
-        FAIL(h, MPPI_ERR_SHAPE, "mppi_set_mlp: Linear(5,512) -> n x [Linear(512,512), tanh] -> Linear(512,3) with n = 3 or 2 is built "
-                                "(got hidden = %d, n = %d)", hidden, n_hidden);
+    if (!mlp_shape_supported(hidden, n_hidden))
+        FAIL(h, MPPI_ERR_SHAPE, "mppi_set_mlp: Linear(5,H) -> n x [Linear(H,H), tanh] -> Linear(H,3) is built for " MLP_SUPPORTED_SET
+                                " (got hidden = %d, n = %d)", hidden, n_hidden);
+    for (int l = 0; l < n_hidden; ++l)
+        if (!w_hidden[l] || !b_hidden[l]) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_mlp: null hidden layer %d", l);
+    const int H = hidden;
+    const bool h3_shape = mlp_shape_is_h3(H, n_hidden);  // 512 x 3, 512 x 2: k_rollout_mlp_h3 / k_rollout_mlp; else k_rollout_mlp_w
+    // The split kernels carry every WEIGHT as two f16 numbers: one beyond the f16 range (65504; e.g. W_in / in_scale with a
+    // StandardScaler scale near 1e-6) would become inf in the high plane.  At 512 x 3 and 512 x 2 such a model takes the
+    // f32-input MFMA kernel, which has no range limit, and the handle says so (mppi_last_error; mppi_get_mlp_kernel); the other
+    // shapes have no f32-input kernel and refuse it.  Inputs and first-layer pre-activations of any magnitude are handled
+    // inside the split kernels (per-sample power-of-two scales).
+    double wmax = 0.0;
+    for (size_t i = 0; i < (size_t)H * 5; ++i) wmax = fmax(wmax, fabs((double)w_in[i]));
+    for (int l = 0; l < n_hidden; ++l)
+        for (size_t i = 0; i < (size_t)H * H; ++i) wmax = fmax(wmax, fabs((double)w_hidden[l][i]));
+    const bool f16_range = wmax <= 65504.0;  // (false for NaN too)
+    if (!h3_shape && !f16_range)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: max |weight| = %.4g exceeds the f16 range, and only the 512 x 3 and 512 x 2 "
+                                      "models have an f32-input kernel to serve that (got hidden = %d, n = %d)", wmax, H, n_hidden);
+    if (!h3_shape && getenv("MPPI_MLP_F32"))
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: MPPI_MLP_F32 is set, and the f32-input kernel serves only the 512 x 3 and "
+                                      "512 x 2 models (got hidden = %d, n = %d)", H, n_hidden);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
-    const size_t n_in = 16 * 1 * 64 * 4, n_h = 16 * 64 * 64 * 4, total = n_in + 512 + 3 * (n_h + 512) + 3 * 512;
+    // A cached closed-loop graph (ensure_graph) holds the previous model's MlpParams -- device pointers into the buffers
+    // below, which may now move or be repacked for another shape: it is dropped here, before anything changes.
+    drop_graph(h);
+    const int CT = H / 32;  // column tiles of 32 outputs
+    // f32 fragment order (k_rollout_mlp, 512 only) plus the biases and the output layer that every kernel reads
+    const size_t n_in = (size_t)CT * 1 * 64 * 4, n_h = (size_t)CT * (H / 8) * 64 * 4;
+    const size_t total = n_in + H + MLP_MAX_HIDDEN * (n_h + H) + 3 * (size_t)H;
     std::vector<float> host(total);
     size_t o = 0;
-    const size_t o_win = o; pack_linear(w_in, 5, host.data() + o); o += n_in;
-    const size_t o_bin = o; memcpy(host.data() + o, b_in, 512 * sizeof(float)); o += 512;
-    size_t o_wh[3], o_bh[3];
-    for (int l = 0; l < 3; ++l) {  // (a two-layer model leaves the third slot unused)
+    const size_t o_win = o; pack_linear(w_in, 5, host.data() + o, H); o += n_in;
+    const size_t o_bin = o; memcpy(host.data() + o, b_in, H * sizeof(float)); o += H;
+    size_t o_wh[MLP_MAX_HIDDEN], o_bh[MLP_MAX_HIDDEN];
+    for (int l = 0; l < MLP_MAX_HIDDEN; ++l) {  // (a shallower model leaves the last slots unused)
         o_wh[l] = o; o_bh[l] = o + n_h;
         if (l < n_hidden) {
-            if (!w_hidden[l] || !b_hidden[l]) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_mlp: null hidden layer %d", l);
-            pack_linear(w_hidden[l], 512, host.data() + o);
-            memcpy(host.data() + o + n_h, b_hidden[l], 512 * sizeof(float));
+            pack_linear(w_hidden[l], H, host.data() + o, H);
+            memcpy(host.data() + o + n_h, b_hidden[l], H * sizeof(float));
         }
-        o += n_h + 512;
+        o += n_h + H;
     }
-    const size_t o_wo = o; memcpy(host.data() + o, w_out, 3 * 512 * sizeof(float)); o += 3 * 512;
-    if (!h->d_mlp) HIPCHECK(h, hipMalloc((void **)&h->d_mlp, total * sizeof(float)));
+    const size_t o_wo = o; memcpy(host.data() + o, w_out, 3 * (size_t)H * sizeof(float)); o += 3 * (size_t)H;
+    // (a later call may load a larger model: the buffers grow to it)
+    if (h->d_mlp && h->mlp_cap < total) { HIPCHECK(h, hipFree(h->d_mlp)); h->d_mlp = nullptr; }
+    if (!h->d_mlp) { HIPCHECK(h, hipMalloc((void **)&h->d_mlp, total * sizeof(float))); h->mlp_cap = total; }
     HIPCHECK(h, hipMemcpy(h->d_mlp, host.data(), total * sizeof(float), hipMemcpyHostToDevice));
     h->mlp.w_in = h->d_mlp + o_win;
     h->mlp.b_in = h->d_mlp + o_bin;
-    for (int l = 0; l < 3; ++l) { h->mlp.w_h[l] = h->d_mlp + o_wh[l]; h->mlp.b_h[l] = h->d_mlp + o_bh[l]; }
+    for (int l = 0; l < MLP_MAX_HIDDEN; ++l) { h->mlp.w_h[l] = h->d_mlp + o_wh[l]; h->mlp.b_h[l] = h->d_mlp + o_bh[l]; }
     h->mlp.w_out = h->d_mlp + o_wo;
     for (int i = 0; i < 3; ++i) h->mlp.b_out[i] = b_out[i];
-    {   // the same weights as f16 (hi, lo) planes for k_rollout_mlp_h3
-        const size_t n_in16 = (size_t)2 * 16 * 1 * 64 * 8, n_h16 = (size_t)2 * 16 * 32 * 64 * 8, tot16 = n_in16 + 3 * n_h16;
+    {   // the same weights as f16 (hi, lo) planes for the split kernels
+        const size_t n_in16 = (size_t)2 * CT * 1 * 64 * 8, n_h16 = (size_t)2 * CT * (H / 16) * 64 * 8;
+        const size_t tot16 = n_in16 + MLP_MAX_HIDDEN * n_h16;
         std::vector<unsigned short> h16(tot16);
-        pack_linear_h3(w_in, 5, h16.data());
-        for (int l = 0; l < n_hidden; ++l) pack_linear_h3(w_hidden[l], 512, h16.data() + n_in16 + (size_t)l * n_h16);
-        if (!h->d_mlp16) HIPCHECK(h, hipMalloc((void **)&h->d_mlp16, tot16 * sizeof(unsigned short)));
+        pack_linear_h3(w_in, 5, h16.data(), H);
+        for (int l = 0; l < n_hidden; ++l) pack_linear_h3(w_hidden[l], H, h16.data() + n_in16 + (size_t)l * n_h16, H);
+        if (h->d_mlp16 && h->mlp16_cap < tot16) { HIPCHECK(h, hipFree(h->d_mlp16)); h->d_mlp16 = nullptr; }
+        if (!h->d_mlp16) { HIPCHECK(h, hipMalloc((void **)&h->d_mlp16, tot16 * sizeof(unsigned short))); h->mlp16_cap = tot16; }
         HIPCHECK(h, hipMemcpy(h->d_mlp16, h16.data(), tot16 * sizeof(unsigned short), hipMemcpyHostToDevice));
         h->mlp.h3_w_in = h->d_mlp16;
-        for (int l = 0; l < 3; ++l) h->mlp.h3_w_h[l] = h->d_mlp16 + n_in16 + (size_t)l * n_h16;
+        for (int l = 0; l < MLP_MAX_HIDDEN; ++l) h->mlp.h3_w_h[l] = h->d_mlp16 + n_in16 + (size_t)l * n_h16;
         h->mlp.use_h3 = getenv("MPPI_MLP_F32") ? 0 : 1;
-        // The split kernel carries every WEIGHT as two f16 numbers: one beyond the f16 range (65504; e.g. W_in / in_scale with a
-        // StandardScaler scale near 1e-6) would become inf in the high plane.  Such a model takes the f32-input MFMA kernel,
-        // which has no range limit, and the handle says so (mppi_last_error; mppi_get_mlp_kernel).  Inputs and first-layer
-        // pre-activations of any magnitude are handled inside the split kernel (per-sample power-of-two scales).
-        double wmax = 0.0;
-        for (int i = 0; i < 512 * 5; ++i) wmax = fmax(wmax, fabs((double)w_in[i]));
-        for (int l = 0; l < n_hidden; ++l)
-            for (size_t i = 0; i < (size_t)512 * 512; ++i) wmax = fmax(wmax, fabs((double)w_hidden[l][i]));
-        if (!(wmax <= 65504.0)) {  // (also NaN)
+        if (!f16_range) {  // (512 x 3 / 512 x 2 only: refused above otherwise)
             h->mlp.use_h3 = 0;
             char b[256];
             snprintf(b, sizeof(b), "mppi_set_mlp: max |weight| = %.4g exceeds the f16 range: the f32-input MFMA kernel serves this model", wmax);
@@ -430,7 +463,7 @@ extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, co
     }
     {   // bounds the split kernel scales the first layer's output with: |W_in z + b_in|_inf <= in_gain |z|_inf + in_bias
         double gain = 0.0, bias = 0.0;
-        for (int n = 0; n < 512; ++n) {
+        for (int n = 0; n < H; ++n) {
             double row = 0.0;
             for (int j = 0; j < 5; ++j) row += fabs((double)w_in[n * 5 + j]);
             gain = fmax(gain, row);
@@ -440,6 +473,7 @@ extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, co
         h->mlp.in_bias = (float)(bias * (1.0 + 1e-6));
     }
     h->mlp.n_hidden = n_hidden;
+    h->mlp.hidden = H;
     h->n_part = mlp_blocks(h->cfg.K, mlp_tile(h->mlp));  // records the rollout kernel that serves this model leaves
     h->mlp_set = true;
     return MPPI_OK;
@@ -452,7 +486,9 @@ extern "C" int mppi_set_mlp_scaled(mppi_handle *h, int32_t hidden, int32_t n_hid
     if (!h || !w_in || !b_in || !w_out || !b_out) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_mlp_scaled: null argument");
     if ((in_mean == nullptr) != (in_scale == nullptr) || (out_mean == nullptr) != (out_scale == nullptr))
         FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_mlp_scaled: a mean without its scale (or the reverse)");
-    if (hidden != 512) FAIL(h, MPPI_ERR_SHAPE, "mppi_set_mlp: the hidden width must be 512 (got %d)", hidden);
+    if (!mlp_shape_supported(hidden, n_hidden))
+        FAIL(h, MPPI_ERR_SHAPE, "mppi_set_mlp_scaled: Linear(5,H) -> n x [Linear(H,H), tanh] -> Linear(H,3) is built for " MLP_SUPPORTED_SET
+                                " (got hidden = %d, n = %d)", hidden, n_hidden);
     std::vector<float> wi(w_in, w_in + (size_t)hidden * 5), bi(b_in, b_in + hidden), wo(w_out, w_out + (size_t)3 * hidden),
         bo(b_out, b_out + 3);
     if (in_mean) {
@@ -1477,11 +1513,13 @@ static int graph_slots() {
 #define GRAPH_SLOTS graph_slots()
 template <typename R>
 static bool ensure_graph(mppi_handle *h, const KParams<R> &P, const FinalizeParams &F) {
-    std::vector<char> key(sizeof(P) + sizeof(F) + 2 * sizeof(int));
+    // (the learned model's parameters too: its launches carry MlpParams -- weight pointers, shape, output bias -- by value)
+    std::vector<char> key(sizeof(P) + sizeof(F) + 2 * sizeof(int) + sizeof(MlpParams));
     memcpy(key.data(), &P, sizeof(P));
     memcpy(key.data() + sizeof(P), &F, sizeof(F));
     const int tail[2] = {h->rollout_repeats, (int)sizeof(R)};
     memcpy(key.data() + sizeof(P) + sizeof(F), tail, sizeof(tail));
+    memcpy(key.data() + sizeof(P) + sizeof(F) + sizeof(tail), &h->mlp, sizeof(MlpParams));
     if (h->graph_exec[0] && key == h->graph_key) return true;
     static const bool verbose = getenv("MPPI_GRAPH_VERBOSE") != nullptr;
     if (verbose) fprintf(stderr, "[mppi] capturing a graph of %d iterations\n", GRAPH_SLOTS);

@@ -166,22 +166,32 @@ struct FinalizeParams {
     unsigned lb_seq, pad_lb;
 };
 
-// learned residual dynamics (mppi_mlp.hip): device pointers to fragment-packed weights
+// learned residual dynamics (mppi_mlp.hip): device pointers to fragment-packed weights.  Hidden width H in {64, 128, 256, 512}
+// and depth n_hidden in {1, 2, 3, 4} (mppi_set_mlp); 512 x 3 and 512 x 2 run k_rollout_mlp_h3 / k_rollout_mlp, the other
+// shapes k_rollout_mlp_w<H, ...>
+constexpr int MLP_MAX_HIDDEN = 4;
 struct MlpParams {
-    const float *w_in, *b_in;        // Linear(5 -> 512): packed [16][1][64][4], bias [512]
-    const float *w_h[3], *b_h[3];    // Linear(512 -> 512) x 3: packed [16][64][64][4], bias [512]
-    const float *w_out;              // Linear(512 -> 3): [3][512] as in the checkpoint
+    const float *w_in, *b_in;        // Linear(5 -> H): packed [H / 32][1][64][4], bias [H]
+    const float *w_h[MLP_MAX_HIDDEN], *b_h[MLP_MAX_HIDDEN];  // Linear(H -> H): packed [H / 32][H / 8][64][4], bias [H]
+    const float *w_out;              // Linear(H -> 3): [3][H] as in the checkpoint
     float b_out[3];
-    // the f16-split kernel (k_rollout_mlp_h3): per layer two f16 planes (hi, then lo) in its fragment order
+    // the f16-split kernels (k_rollout_mlp_h3, k_rollout_mlp_w): per layer two f16 planes (hi, then lo) in their fragment order
     int use_h3;
-    const unsigned short *h3_w_in;   // [2][16][1][64][8]
-    const unsigned short *h3_w_h[3]; // [2][16][32][64][8]
+    const unsigned short *h3_w_in;   // [2][H / 32][1][64][8]
+    const unsigned short *h3_w_h[MLP_MAX_HIDDEN]; // [2][H / 32][H / 16][64][8]
     // |W_in z + b_in|_inf <= in_gain |z|_inf + in_bias: the split kernel derives the per-sample power-of-two scale of the
     // first layer's output from it, so that no f16 half overflows whatever the magnitude of the inputs
     float in_gain, in_bias;
-    int n_hidden;  // hidden Linear(512, 512) + tanh layers: 3 (the architecture train/train_diff_mlp.py:13-36 builds) or 2
-                   // (the reference's older checkpoints, saved_models/mlp_diff.pth, mlp_diff_300x100.pth, ..._v2.pth)
+    int n_hidden;  // hidden Linear(H, H) + tanh layers: 3 (the architecture train/train_diff_mlp.py:13-36 builds), 2 (the
+                   // reference's older checkpoints, saved_models/mlp_diff.pth, mlp_diff_300x100.pth, ..._v2.pth), 1 or 4
+    int hidden;    // H
 };
+
+// the shapes k_rollout_mlp_h3 (and the f32-input k_rollout_mlp) serve; every other supported shape runs k_rollout_mlp_w
+inline bool mlp_shape_is_h3(int hidden, int n_hidden) { return hidden == 512 && (n_hidden == 2 || n_hidden == 3); }
+inline bool mlp_shape_supported(int hidden, int n_hidden) {
+    return (hidden == 64 || hidden == 128 || hidden == 256 || hidden == 512) && n_hidden >= 1 && n_hidden <= MLP_MAX_HIDDEN;
+}
 
 struct VizParams {
     int K, T, model, clamp_rollout;
@@ -245,10 +255,10 @@ void launch_eval_mlp(const KParams<float> &P, const MlpParams &Q, const float *x
 void launch_viz_mlp(const KParams<float> &P, const MlpParams &Q, const float *u_before, const float *u_upd, long long iter,
                     float *opt, float *smp, hipStream_t s);
 int mlp_blocks(int K, int tile);            // workgroups = softmin records of a launch over K samples
-int mlp_tile(const MlpParams &Q);          // samples per workgroup of the rollout kernel that serves Q (32 or 64)
+int mlp_tile(const MlpParams &Q);          // samples per workgroup of the rollout kernel that serves Q (64)
 const char *mlp_kernel_name(const MlpParams &Q);  // as rocprofv3 spells the rollout kernel that serves Q
-void pack_linear(const float *w, int n_in, float *packed);  // host: [512][n_in] -> fragment order
-void pack_linear_h3(const float *w, int n_in, unsigned short *packed);  // host: -> two f16 planes in fragment order
+void pack_linear(const float *w, int n_in, float *packed, int n_out = 512);  // host: [n_out][n_in] -> fragment order
+void pack_linear_h3(const float *w, int n_in, unsigned short *packed, int n_out = 512);  // host: -> two f16 planes in fragment order
 constexpr int MODEL_DIFF_MLP = 2;
 
 }  // namespace mppi

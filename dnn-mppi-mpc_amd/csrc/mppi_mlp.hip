@@ -409,10 +409,13 @@ struct H3Pass { const half8 *hi, *lo; };
 // NW waves per workgroup (4: one per SIMD, each owns 128 output columns = two passes of two column tiles; 8: two per SIMD,
 // each owns 64 columns = one pass -- the same MFMAs, weight bytes and LDS reads per SIMD, but the two waves of a SIMD cover
 // each other's waits in the GEMMs and share the VALU in the epilogues, which a single wave issues at half the pipe's rate)
-template <int NW> __device__ __forceinline__ H3Pass h3_pass(const unsigned short *layer, int n_steps, int wid, int pass, int lane) {
+// H: the layer's width (k_rollout_mlp_w; the 512-wide kernel uses the default), H / 32 column tiles
+template <int NW, int H = MLP_H>
+__device__ __forceinline__ H3Pass h3_pass(const unsigned short *layer, int n_steps, int wid, int pass, int lane) {
+    constexpr int CT = H / 32;
     const half8 *w = reinterpret_cast<const half8 *>(layer);
-    const size_t off = (size_t)(wid * (16 / NW) + 2 * pass) * n_steps * 64 + lane;
-    return H3Pass{w + off, w + (size_t)16 * n_steps * 64 + off};
+    const size_t off = (size_t)(wid * (CT / NW) + 2 * pass) * n_steps * 64 + lane;
+    return H3Pass{w + off, w + (size_t)CT * n_steps * 64 + off};
 }
 __device__ __forceinline__ void h3_load_b(const H3Pass &w, int n_steps, int s, H3FragB &f) {
 #pragma unroll
@@ -456,12 +459,12 @@ template <int RT> __device__ __forceinline__ void h3_zero(f32x16 (&ac)[RT][2]) {
             for (int r = 0; r < 16; ++r) ac[rt][c2][r] = 0.f;
 }
 
-// one pass (two column tiles) of a 512-wide hidden layer: `ring` holds its k-steps 0..2 on entry and (HAS_NEXT) those of
+// one pass (two column tiles) of an H-wide hidden layer: `ring` holds its k-steps 0..2 on entry and (HAS_NEXT) those of
 // `next` on exit
-template <bool HAS_NEXT, int RT, int TERMS = 3>
+template <bool HAS_NEXT, int RT, int TERMS = 3, int H = MLP_H>
 __device__ __forceinline__ void gemm_pass_h3(f32x16 (&ac)[RT][2], const _Float16 *a_hi, const _Float16 *a_lo, const H3Pass &w,
                                              const H3Pass &next, H3Ring &ring, int lane) {
-    constexpr int n_steps = H3_STEPS, pitch = H3_PITCH;
+    constexpr int n_steps = H / 16, pitch = H + 8;  // (H3_STEPS, H3_PITCH at 512)
     const int aoff = (lane & 31) * pitch + 8 * (lane >> 5);
     auto load_a = [&](int s, H3FragA &f) {
 #pragma unroll
@@ -495,7 +498,7 @@ __device__ __forceinline__ void gemm_pass_h3(f32x16 (&ac)[RT][2], const _Float16
     load_a(0, a0);
     H3_FENCE();
 #pragma unroll 1
-    for (int s = 0; s < n_steps - 4; s += 4) {  // n_steps is a multiple of 4 (512 / 16 = 32)
+    for (int s = 0; s < n_steps - 4; s += 4) {  // n_steps is a multiple of 4 (H / 16, H >= 64)
         h3_load_b(w, n_steps, s + 3, b3);
         load_a(s + 1, a1);
         h3_mma<RT, TERMS>(ac, a0, ring.b0);
@@ -535,28 +538,29 @@ __device__ __forceinline__ void gemm_pass_h3(f32x16 (&ac)[RT][2], const _Float16
 #undef H3_FENCE
 }
 
-// a 512-wide hidden layer: this wave's 128 columns of all 64 samples.  `ring`: the first three k-steps of the layer,
-// requested by the caller (h3_prime_layer) once the previous layer's epilogue has let go of its registers -- they fly
+// a hidden layer: this wave's H / NW columns (one or two passes) of all 64 samples.  `ring`: the first three k-steps of the
+// layer, requested by the caller (h3_prime_layer) once the previous layer's epilogue has let go of its registers -- they fly
 // while the workgroup meets at the barrier in front of this layer.
-template <int NW> __device__ __forceinline__ void h3_prime_layer(const unsigned short *layer, int wid, int lane, H3Ring &ring) {
-    h3_prime(h3_pass<NW>(layer, H3_STEPS, wid, 0, lane), H3_STEPS, ring);
+template <int NW, int H = MLP_H>
+__device__ __forceinline__ void h3_prime_layer(const unsigned short *layer, int wid, int lane, H3Ring &ring) {
+    h3_prime(h3_pass<NW, H>(layer, H / 16, wid, 0, lane), H / 16, ring);
 }
-template <int NW, int RT, int TERMS = 3>
-__device__ __forceinline__ void gemm_layer_h3(f32x16 (&acc)[8 / NW][RT][2], const _Float16 *a_hi, const _Float16 *a_lo,
+template <int NW, int RT, int TERMS = 3, int H = MLP_H>
+__device__ __forceinline__ void gemm_layer_h3(f32x16 (&acc)[H / 64 / NW][RT][2], const _Float16 *a_hi, const _Float16 *a_lo,
                                               const unsigned short *layer, int wid, int lane, H3Ring &ring) {
-    const H3Pass w0 = h3_pass<NW>(layer, H3_STEPS, wid, 0, lane);
-    if (NW == 4) {
-        const H3Pass w1 = h3_pass<NW>(layer, H3_STEPS, wid, 1, lane);
-        gemm_pass_h3<true, RT, TERMS>(acc[0], a_hi, a_lo, w0, w1, ring, lane);
-        gemm_pass_h3<false, RT, TERMS>(acc[8 / NW - 1], a_hi, a_lo, w1, w1, ring, lane);
+    const H3Pass w0 = h3_pass<NW, H>(layer, H / 16, wid, 0, lane);
+    if (H / 64 / NW == 2) {
+        const H3Pass w1 = h3_pass<NW, H>(layer, H / 16, wid, 1, lane);
+        gemm_pass_h3<true, RT, TERMS, H>(acc[0], a_hi, a_lo, w0, w1, ring, lane);
+        gemm_pass_h3<false, RT, TERMS, H>(acc[H / 64 / NW - 1], a_hi, a_lo, w1, w1, ring, lane);
     } else {
-        gemm_pass_h3<false, RT, TERMS>(acc[0], a_hi, a_lo, w0, w0, ring, lane);
+        gemm_pass_h3<false, RT, TERMS, H>(acc[0], a_hi, a_lo, w0, w0, ring, lane);
     }
 }
 
-// Linear(5 -> 512) of the step's inputs: one k-step (z rows padded to 16), both passes
-template <int NW, int RT>
-__device__ __forceinline__ void gemm_input_h3(f32x16 (&acc)[8 / NW][RT][2], const _Float16 *z_hi, const _Float16 *z_lo,
+// Linear(5 -> H) of the step's inputs: one k-step (z rows padded to 16), every pass
+template <int NW, int RT, int H = MLP_H>
+__device__ __forceinline__ void gemm_input_h3(f32x16 (&acc)[H / 64 / NW][RT][2], const _Float16 *z_hi, const _Float16 *z_lo,
                                               const unsigned short *layer, int wid, int lane) {
     const int aoff = (lane & 31) * H3_ZPITCH + 8 * (lane >> 5);
     H3FragA a;
@@ -566,8 +570,8 @@ __device__ __forceinline__ void gemm_input_h3(f32x16 (&acc)[8 / NW][RT][2], cons
         a.l[rt] = *reinterpret_cast<const half8 *>(z_lo + rt * 32 * H3_ZPITCH + aoff);
     }
 #pragma unroll
-    for (int pass = 0; pass < 8 / NW; ++pass) {
-        const H3Pass w = h3_pass<NW>(layer, 1, wid, pass, lane);
+    for (int pass = 0; pass < H / 64 / NW; ++pass) {
+        const H3Pass w = h3_pass<NW, H>(layer, 1, wid, pass, lane);
         H3FragB b;
         h3_load_b(w, 1, 0, b);
         h3_zero<RT>(acc[pass]);
@@ -596,8 +600,8 @@ using half4v = __attribute__((ext_vector_type(4))) _Float16;
 // stored as h0 / s1: v = (acc s0 + b) / s1; 2 the first hidden layer -- its accumulators are those of h0 / s1: v = acc s1 + b.
 // `scale`: the per-sample {s0, 1 / s1, s1, 0} in LDS.  All three are 1 unless an input exceeds 2^15, and then exact powers
 // of two: the common case is bit for bit the unscaled arithmetic.
-template <int NW, int RT, bool TANH, bool LAST = false, int SCALE = 0>
-__device__ __forceinline__ void store_layer_h3(_Float16 *a_hi, _Float16 *a_lo, const f32x16 (&acc)[8 / NW][RT][2], const float *bias,
+template <int NW, int RT, bool TANH, bool LAST = false, int SCALE = 0, int H = MLP_H>
+__device__ __forceinline__ void store_layer_h3(_Float16 *a_hi, _Float16 *a_lo, const f32x16 (&acc)[H / 64 / NW][RT][2], const float *bias,
                                                int wid, int lane, const float *w_out = nullptr, float (*yo)[3] = nullptr,
                                                const float *scale = nullptr) {
     F4 sc[2] = {{{1.f, 1.f, 1.f, 0.f}}, {{1.f, 1.f, 1.f, 0.f}}};
@@ -605,13 +609,13 @@ __device__ __forceinline__ void store_layer_h3(_Float16 *a_hi, _Float16 *a_lo, c
         sc[0] = *reinterpret_cast<const F4 *>(scale + 4 * (lane & 31));
         if (RT == 2) sc[1] = *reinterpret_cast<const F4 *>(scale + 4 * (32 + (lane & 31)));
     }
-    constexpr int COLS = MLP_H / NW;  // this wave's output features: 16 / NW column tiles of 32
-    const int lane_off = (lane & 31) * H3_PITCH + wid * COLS + 4 * (lane >> 5);
-    _Float16 *const base[2][2] = {{a_hi + lane_off, a_hi + 32 * H3_PITCH + lane_off},
-                                  {a_lo + lane_off, a_lo + 32 * H3_PITCH + lane_off}};
+    constexpr int COLS = H / NW, PITCH = H + 8;  // this wave's output features: H / 32 / NW column tiles of 32
+    const int lane_off = (lane & 31) * PITCH + wid * COLS + 4 * (lane >> 5);
+    _Float16 *const base[2][2] = {{a_hi + lane_off, a_hi + 32 * PITCH + lane_off},
+                                  {a_lo + lane_off, a_lo + 32 * PITCH + lane_off}};
     const float *bl = bias + wid * COLS + 4 * (lane >> 5);
 #pragma unroll
-    for (int ct = 0; ct < 16 / NW; ++ct) {
+    for (int ct = 0; ct < H / 32 / NW; ++ct) {
         f32x2 bn[8];  // the biases of this lane's 16 features of the tile: four aligned 16-byte loads
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -625,7 +629,7 @@ __device__ __forceinline__ void store_layer_h3(_Float16 *a_hi, _Float16 *a_lo, c
 #pragma unroll
             for (int j = 0; j < 3; ++j)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) wo[j][q] = *reinterpret_cast<const F4 *>(wl + j * MLP_H + 8 * q);
+                for (int q = 0; q < 4; ++q) wo[j][q] = *reinterpret_cast<const F4 *>(wl + j * H + 8 * q);
         }
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
@@ -693,6 +697,11 @@ __device__ unsigned long long g_mlp_phase[16];
     do {      \
     } while (0)
 #endif
+// The path's room in LDS beside the buffers of a tile (mlp_stage_path): at H = 256 two workgroups share the CU's 160 KB,
+// 80 KB each, and the activations, inputs and partial outputs take 78.8 KB of it
+constexpr int W256_REF_LDS = 128;
+constexpr int h3_ref_cap(int rt, int h) { return rt == 1 ? H3_REF_LDS_32 : h == 256 ? W256_REF_LDS : MLP_REF_LDS_MAX; }
+
 template <bool VIZ, int NW, int RT, int TERMS = 3>
 __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3(const KParams<float> P, const MlpParams Q,
                                                                float *__restrict__ partials, const MlpViz V) {
@@ -810,6 +819,136 @@ __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3(con
         for (int i = 0; i < 10; ++i) g_mlp_phase[i] = ph[i];
 #endif
 }
+
+// ------------------------------------------------------------------------------------------
+// Every other supported shape, H in {64, 128, 256, 512} x n_hidden in {1, 2, 3, 4}: the same f16-split
+// arithmetic and the same step loop as k_rollout_mlp_h3 (kept apart so that the 512 x 3 / 512 x 2 kernels compile to the code
+// they always did; a shared inlined body changed their register allocation), with H / 64 waves per workgroup, each owning 64 output columns of every layer (one pass of
+// two 32-column tiles, as the 8-wave form of the 512-wide kernel), on a 64-sample tile: blockDim = H.  The LDS of a tile
+// shrinks with H (38 KB at 64, 56 KB at 128, 79 KB at 256), so two (H = 256, 128) or four (H = 64) workgroups share a CU
+// and one's serial part -- wave 0's controls, waypoint search, cost and Euler step -- runs under another's matrix work.
+// ------------------------------------------------------------------------------------------
+template <int H, bool VIZ>
+__global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w(const KParams<float> P, const MlpParams Q, float *__restrict__ partials,
+                                                                     const MlpViz V) {
+    constexpr int NW = H / 64, RT = 2, TERMS = 3;
+#ifdef MPPI_STAMPS
+    unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_t = clock64();
+#endif
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int M = 32 * RT;  // samples of this workgroup's tile
+    constexpr int PITCH = H + 8;                           // (H3_PITCH at 512)
+    _Float16 *a_hi = reinterpret_cast<_Float16 *>(smem);   // [M][H + 8]
+    _Float16 *a_lo = a_hi + M * PITCH;
+    _Float16 *z_hi = a_lo + M * PITCH;                     // [M][24] layer-0 input rows {x, y, yaw, v, w, 0 ...}: one k-step
+    _Float16 *z_lo = z_hi + M * H3_ZPITCH;
+    float *ypart = reinterpret_cast<float *>(z_lo + M * H3_ZPITCH);  // [NW][M][4]
+    float *zscale = ypart + NW * M * 4;                             // [M][4] per-sample {s0, 1 / s1, s1, 0} (H3Scale)
+    float *ref_lds = zscale + M * 4;                                // [n_ref][4] when the path fits
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int k0 = ((int)blockIdx.x + (VIZ ? V.block0 : 0)) * M, k = k0 + lane;
+    const KParams<float> PL = mlp_stage_path(P, ref_lds, h3_ref_cap(RT, H));
+    const DevState sv = load_state(P, P.st);
+    const ObsLanes<float> obs = load_obstacles(P, lane);
+    if (!VIZ && k0 + M <= sv.k_start) return;
+    const bool in_tile = lane < M;  // (a 32-sample tile: the upper half of wave 0 carries no sample)
+    const bool valid = in_tile && k < P.K, live = valid && k >= sv.k_start;
+    // VIZ: the workgroup behind the samples' carries the nominal sequence in its lane 0
+    const bool eval = VIZ && V.ex != nullptr, eval_row = eval && k < V.en;
+    const bool opt_row = VIZ && !eval && k0 >= P.K && lane == 0 && V.opt != nullptr;
+    const bool smp_row = VIZ && !eval && valid && V.smp != nullptr;
+    const int c = sv.c;
+    const unsigned iter = (unsigned)sv.iter;
+    MlpLane L{(float)sv.x0[0], (float)sv.x0[1], (float)sv.x0[2], 0.f, c};
+    if (eval_row) { L.x = V.ex[3 * k]; L.y = V.ex[3 * k + 1]; L.yaw = V.ex[3 * k + 2]; }
+    const int n_steps = eval ? 1 : P.T;
+    const bool exploit = (k + P.k_offset) < P.n_exploit;
+    f32x16 acc[H / 64 / NW][RT][2];
+    if (wid == 0 && in_tile) {  // the padding of the layer-0 rows stays zero
+        for (int q = 0; q < H3_ZPITCH; ++q) { z_hi[lane * H3_ZPITCH + q] = (_Float16)0.f; z_lo[lane * H3_ZPITCH + q] = (_Float16)0.f; }
+    }
+    for (int t = 0; t < n_steps; ++t) {
+        float u0 = 0, u1 = 0, v0 = 0, v1 = 0;
+        if (wid == 0) {
+            if (eval) {
+                if (eval_row) { v0 = V.ev[2 * k]; v1 = V.ev[2 * k + 1]; }
+            } else if (VIZ) mlp_controls_viz(P, V, k, t, smp_row, opt_row, exploit, v0, v1);
+            else mlp_controls(P, iter, k, t, valid, exploit, u0, u1, v0, v1);
+            const float z[5] = {L.x, L.y, L.yaw, v0, v1};
+            const H3Scale hs = h3_scale(z, Q.in_gain, Q.in_bias);
+            if (in_tile) {
+                *reinterpret_cast<F4 *>(zscale + 4 * lane) = F4{{hs.s0, hs.inv_s1, hs.s1, 0.f}};
+#pragma unroll
+                for (int q = 0; q < 5; ++q) split_h3(z[q] * hs.inv_s0, z_hi[lane * H3_ZPITCH + q], z_lo[lane * H3_ZPITCH + q]);
+            }
+        }
+        __syncthreads();
+        PH(0);
+        gemm_input_h3<NW, RT, H>(acc, z_hi, z_lo, Q.h3_w_in, wid, lane);
+        PH(1);
+        store_layer_h3<NW, RT, false, false, 1, H>(a_hi, a_lo, acc, Q.b_in, wid, lane, nullptr, nullptr, zscale);
+        H3Ring ring;
+        h3_prime_layer<NW, H>(Q.h3_w_h[0], wid, lane, ring);
+        PH(2);
+        __syncthreads();
+        PH(3);
+        const int l_last = Q.n_hidden - 1;  // (1 to 4 hidden layers, mppi_set_mlp)
+        for (int l = 0; l < l_last; ++l) {
+            gemm_layer_h3<NW, RT, TERMS, H>(acc, a_hi, a_lo, Q.h3_w_h[l], wid, lane, ring);
+            PH(4);
+            __syncthreads();
+            PH(5);
+            if (l == 0) store_layer_h3<NW, RT, true, false, 2, H>(a_hi, a_lo, acc, Q.b_h[l], wid, lane, nullptr, nullptr, zscale);
+            else store_layer_h3<NW, RT, true, false, 0, H>(a_hi, a_lo, acc, Q.b_h[l], wid, lane);
+            h3_prime_layer<NW, H>(Q.h3_w_h[l + 1], wid, lane, ring);
+            PH(6);
+            __syncthreads();
+            PH(7);
+        }
+        {   // the last hidden layer and out_layer (Linear(H -> 3), :35) in its epilogue: this wave's share of the H inputs
+            gemm_layer_h3<NW, RT, TERMS, H>(acc, a_hi, a_lo, Q.h3_w_h[l_last], wid, lane, ring);
+            PH(4);
+            float yo[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+            if (l_last == 0)  // one hidden layer: it is also the first, its accumulators those of h0 / s1
+                store_layer_h3<NW, RT, true, true, 2, H>(a_hi, a_lo, acc, Q.b_h[0], wid, lane, Q.w_out, yo, zscale);
+            else store_layer_h3<NW, RT, true, true, 0, H>(a_hi, a_lo, acc, Q.b_h[l_last], wid, lane, Q.w_out, yo);
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {  // the two lane halves hold the two halves of a sample's features
+                F4 o;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) o.v[j] = yo[rt][j] + __shfl_xor(yo[rt][j], 32);
+                o.v[3] = 0.f;
+                if (lane < 32) *reinterpret_cast<F4 *>(ypart + (wid * M + rt * 32 + lane) * 4) = o;
+            }
+        }
+        PH(8);
+        __syncthreads();
+        if (wid == 0) {
+            float r0 = Q.b_out[0], r1 = Q.b_out[1], r2 = Q.b_out[2];
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                const F4 o = *reinterpret_cast<const F4 *>(ypart + (w * M + (in_tile ? lane : 0)) * 4);
+                r0 += o.v[0];
+                r1 += o.v[1];
+                r2 += o.v[2];
+            }
+            if (VIZ) {
+                mlp_euler(P, r0, r1, r2, v0, v1, L);
+                float *dst = eval_row ? V.eout + (size_t)k * 3
+                             : opt_row ? V.opt + (size_t)t * 3 : smp_row ? V.smp + ((size_t)k * P.T + t) * 3 : nullptr;
+                if (dst) { dst[0] = L.x; dst[1] = L.y; dst[2] = L.yaw; }
+            } else {
+                mlp_advance(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
+            }
+        }
+        PH(9);
+    }
+    if (!VIZ && wid == 0) mlp_record(P, partials, iter, k, c, valid, live, L, lane);
+#ifdef MPPI_STAMPS
+    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && wid == (NW > 1 ? 1 : 0))
+        for (int i = 0; i < 10; ++i) g_mlp_phase[i] = ph[i];
+#endif
+}
 #undef PH
 #ifdef MPPI_STAMPS
 extern "C" int mppi_debug_mlp_phases(unsigned long long *out) {
@@ -836,14 +975,33 @@ static int h3_terms() {
     const char *e = getenv("MPPI_MLP_TERMS");
     return e && atoi(e) == 2 ? 2 : 3;
 }
-// samples per workgroup (= per softmin record) of the rollout kernel that serves Q
+// samples per workgroup (= per softmin record) of the rollout kernel that serves Q (every one of them: 64)
 int mlp_tile(const MlpParams &) { return MLP_M; }
 int mlp_blocks(int K, int tile) { return (K + tile - 1) / tile; }
 
-static size_t h3_shmem(int nw, int rt) {
+static size_t h3_shmem(int nw, int rt, int h = MLP_H) {
     const int m = 32 * rt;
-    return sizeof(_Float16) * 2 * (m * H3_PITCH + m * H3_ZPITCH) + sizeof(float) * (nw + 1) * m * 4 +
-           sizeof(float) * 4 * (rt == 1 ? H3_REF_LDS_32 : MLP_REF_LDS_MAX);
+    return sizeof(_Float16) * 2 * (m * (h + 8) + m * H3_ZPITCH) + sizeof(float) * (nw + 1) * m * 4 +
+           sizeof(float) * 4 * h3_ref_cap(rt, h);
+}
+// k_rollout_mlp_w<H, VIZ>: H / 64 waves, 64-sample tiles
+static size_t w_shmem(int h) { return h3_shmem(h / 64, 2, h); }
+static_assert(2 * (sizeof(_Float16) * 2 * (64 * (256 + 8) + 64 * H3_ZPITCH) + sizeof(float) * 5 * 64 * 4 + sizeof(float) * 4 * W256_REF_LDS)
+                  <= 160 * 1024, "two H = 256 workgroups per CU");
+static bool mlp_is_w(const MlpParams &Q) { return !mlp_shape_is_h3(Q.hidden, Q.n_hidden); }
+
+template <int H>
+static void launch_w(const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz &v, bool viz, dim3 grid, hipStream_t s) {
+    if (viz) hipLaunchKernelGGL((k_rollout_mlp_w<H, true>), grid, dim3(H), w_shmem(H), s, P, Q, (float *)partials, v);
+    else hipLaunchKernelGGL((k_rollout_mlp_w<H, false>), grid, dim3(H), w_shmem(H), s, P, Q, (float *)partials, v);
+}
+static void launch_w_any(const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz &v, bool viz, dim3 grid, hipStream_t s) {
+    switch (Q.hidden) {  // (mppi_set_mlp admits only these)
+    case 64: launch_w<64>(P, Q, partials, v, viz, grid, s); break;
+    case 128: launch_w<128>(P, Q, partials, v, viz, grid, s); break;
+    case 256: launch_w<256>(P, Q, partials, v, viz, grid, s); break;
+    case 512: launch_w<512>(P, Q, partials, v, viz, grid, s); break;
+    }
 }
 
 static void launch_mlp_any(const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz *viz, hipStream_t s) {
@@ -863,6 +1021,13 @@ static void launch_mlp_any(const KParams<float> &P, const MlpParams &Q, void *pa
 #undef H3_ATTR
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_h3<false, 8, 2, 2>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3_shmem(8, 2));
+#define W_ATTR(H_)                                                                                                       \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_w<H_, false>),                               \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_shmem(H_));                             \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_w<H_, true>),                                \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_shmem(H_))
+        W_ATTR(64); W_ATTR(128); W_ATTR(256); W_ATTR(512);
+#undef W_ATTR
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
     const MlpViz none{nullptr, nullptr, nullptr, nullptr, 0u, 0, nullptr, nullptr, nullptr, 0};
@@ -870,8 +1035,11 @@ static void launch_mlp_any(const KParams<float> &P, const MlpParams &Q, void *pa
     if (viz) {  // the samples' workgroups (when their trajectories are wanted) and one for the nominal sequence (likewise);
                 // always 64-sample tiles
         const dim3 grid(viz->ex ? mlp_blocks(viz->en, MLP_M) : (viz->smp ? mlp_blocks(P.K, MLP_M) : 0) + (viz->opt ? 1 : 0));
-        if (form == H3_FORM_8x64) hipLaunchKernelGGL((k_rollout_mlp_h3<true, 8, 2>), grid, dim3(512), h3_shmem(8, 2), s, P, Q, (float *)partials, *viz);
+        if (mlp_is_w(Q)) launch_w_any(P, Q, partials, *viz, true, grid, s);
+        else if (form == H3_FORM_8x64) hipLaunchKernelGGL((k_rollout_mlp_h3<true, 8, 2>), grid, dim3(512), h3_shmem(8, 2), s, P, Q, (float *)partials, *viz);
         else hipLaunchKernelGGL((k_rollout_mlp_h3<true, 4, 2>), grid, dim3(256), h3_shmem(4, 2), s, P, Q, (float *)partials, *viz);
+    } else if (mlp_is_w(Q)) {  // (MPPI_MLP_FORM / MPPI_MLP_TERMS / MPPI_MLP_F32 concern the 512 x 3 and 512 x 2 shapes only)
+        launch_w_any(P, Q, partials, none, false, dim3(mlp_blocks(P.K, mlp_tile(Q))), s);
     } else if (Q.use_h3) {
         const dim3 grid(mlp_blocks(P.K, mlp_tile(Q)));
         if (form == H3_FORM_8x64 && h3_terms() == 2)
@@ -884,6 +1052,13 @@ static void launch_mlp_any(const KParams<float> &P, const MlpParams &Q, void *pa
 }
 
 const char *mlp_kernel_name(const MlpParams &Q) {
+    if (mlp_is_w(Q))
+        switch (Q.hidden) {
+        case 64: return "k_rollout_mlp_w<64, false>";
+        case 128: return "k_rollout_mlp_w<128, false>";
+        case 256: return "k_rollout_mlp_w<256, false>";
+        default: return "k_rollout_mlp_w<512, false>";
+        }
     if (!Q.use_h3) return "k_rollout_mlp(";
     const int form = h3_form();
     if (form == H3_FORM_8x64 && h3_terms() == 2) return "k_rollout_mlp_h3<false, 8, 2, 2>";
@@ -906,11 +1081,11 @@ void launch_eval_mlp(const KParams<float> &P, const MlpParams &Q, const float *x
     launch_mlp_any(P, Q, nullptr, &e, s);
 }
 
-// Host-side packing of a torch Linear weight [n_out = 512][n_in] into fragment order:
-// packed[ct (16)][g (n_groups)][lane (64)][s (4)] = W[32 ct + (lane & 31)][8 g + 4 (lane >> 5) + s] (0 beyond n_in)
-void pack_linear(const float *w, int n_in, float *packed) {
+// Host-side packing of a torch Linear weight [n_out][n_in] (n_out a multiple of 32) into fragment order:
+// packed[ct (n_out / 32)][g (n_groups)][lane (64)][s (4)] = W[32 ct + (lane & 31)][8 g + 4 (lane >> 5) + s] (0 beyond n_in)
+void pack_linear(const float *w, int n_in, float *packed, int n_out) {
     const int n_groups = (n_in + 7) / 8;
-    for (int ct = 0; ct < MLP_H / 32; ++ct)
+    for (int ct = 0; ct < n_out / 32; ++ct)
         for (int g = 0; g < n_groups; ++g)
             for (int lane = 0; lane < 64; ++lane)
                 for (int s = 0; s < 4; ++s) {
@@ -960,12 +1135,12 @@ static float f16_bits_to_f32(unsigned short h) {
     return f;
 }
 
-// Host-side packing for k_rollout_mlp_h3: W [512][n_in] -> two f16 planes (hi, then lo) in fragment order
-// plane[ct (16)][s (n_steps)][lane (64)][j (8)] = W[32 ct + (lane & 31)][16 s + 8 (lane >> 5) + j]  (0 beyond n_in)
-void pack_linear_h3(const float *w, int n_in, unsigned short *packed) {
+// Host-side packing for the f16-split kernels: W [n_out][n_in] -> two f16 planes (hi, then lo) in fragment order
+// plane[ct (n_out / 32)][s (n_steps)][lane (64)][j (8)] = W[32 ct + (lane & 31)][16 s + 8 (lane >> 5) + j]  (0 beyond n_in)
+void pack_linear_h3(const float *w, int n_in, unsigned short *packed, int n_out) {
     const int n_steps = (n_in + 15) / 16;
-    const size_t plane = (size_t)(MLP_H / 32) * n_steps * 64 * 8;
-    for (int ct = 0; ct < MLP_H / 32; ++ct)
+    const size_t plane = (size_t)(n_out / 32) * n_steps * 64 * 8;
+    for (int ct = 0; ct < n_out / 32; ++ct)
         for (int s = 0; s < n_steps; ++s)
             for (int lane = 0; lane < 64; ++lane)
                 for (int j = 0; j < 8; ++j) {

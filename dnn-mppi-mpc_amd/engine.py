@@ -81,9 +81,15 @@ class Engine:
         c = np.ascontiguousarray(circles, dtype=np.float64).reshape(-1, 3)
         self._ck(self.lib.mppi_set_obstacles(self._h, _dp(c), c.shape[0]))
 
+    # the residual-model shapes the kernels serve: hidden width H x hidden layers n (512 x 3 and 512 x 2 on
+    # k_rollout_mlp_h3, every other one on k_rollout_mlp_w<H, ...>)
+    SUPPORTED_MLP = {"hidden": (64, 128, 256, 512), "n_hidden": (1, 2, 3, 4)}
+
     def set_mlp(self, weights, scalers=None):
         """Residual-model weights in the checkpoint's key layout (``state_dict`` of the reference's
-        ``MultiLayerPerceptron``, train/train_diff_mlp.py:13-36); tensors or arrays.
+        ``MultiLayerPerceptron``, train/train_diff_mlp.py:13-36); tensors or arrays.  Linear(5, H) -> n x [Linear(H, H),
+        tanh] -> Linear(H, 3) with H in {64, 128, 256, 512} and n in {1, 2, 3, 4} (`SUPPORTED_MLP`); any other shape is a
+        ``ValueError`` that names the set.
 
         ``scalers``: optional dict with the ``StandardScaler`` statistics the model was trained with
         (train/train_diff_mlp.py:72-86): ``in_mean``/``in_scale`` (5: state then control) and ``out_mean``/``out_scale``
@@ -103,6 +109,9 @@ class Engine:
         hidden = w_in.shape[0]
         if w_in.shape != (hidden, 5) or w_out.shape != (3, hidden) or any(w.shape != (hidden, hidden) for w in wh):
             raise ValueError("unexpected MLP shapes (expected Linear(5,H) -> n x Linear(H,H) -> Linear(H,3))")
+        if hidden not in self.SUPPORTED_MLP["hidden"] or n_hidden not in self.SUPPORTED_MLP["n_hidden"]:
+            raise ValueError(f"MLP of hidden width {hidden} with {n_hidden} hidden layers: the supported set is hidden H in "
+                             "{64, 128, 256, 512} x n_hidden in {1, 2, 3, 4}")
         PP = C.POINTER(C.c_float) * max(1, n_hidden)
         if scalers is None:
             self._ck(self.lib.mppi_set_mlp(self._h, hidden, n_hidden, fp(w_in), fp(b_in), PP(*[fp(w) for w in wh]),

@@ -44,7 +44,7 @@ typedef enum {
     MPPI_MODEL_DIFFDRIVE = 0,
     MPPI_MODEL_RACECAR = 1,
     /* unicycle + learned residual, x' = x + dt (f(x,v) + MLP([x,v])) (test/bullet_differential_drive_dnn.py:79-92);
-     * needs mppi_set_mlp; fp32 only (f32 MFMA) */
+     * needs mppi_set_mlp; fp32 only (MFMA) */
     MPPI_MODEL_DIFFDRIVE_MLP = 2
 } mppi_model;
 /* arithmetic type of the rollout/cost kernels (the noise tensor is always f32) */
@@ -171,14 +171,17 @@ int mppi_set_ref_path(mppi_handle *h, const double *path, int32_t n, int32_t nco
 int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m);
 /*
  * Weights of the residual model `MultiLayerPerceptron` (train/train_diff_mlp.py:13-36), host float arrays in the
- * checkpoint's own layout (saved_models/mlp_diff_300x100_3l.pth): input_layer.weight [512,5], .bias [512];
- * hidden_layer.{0..n_hidden-1}.weight [512,512], .bias [512]; out_layer.weight [3,512], .bias [3].
- * hidden must be 512; n_hidden 3 (the architecture the reference trains, mlp_diff_300x100_3l*.pth) or 2 (its older
- * checkpoints mlp_diff.pth, mlp_diff_300x100.pth, mlp_diff_300x100_v2.pth: hidden_layer.{0,1}).
- * Numeric range: the default kernel carries weights, inputs and activations as pairs of f16 numbers.  Inputs [x, y, yaw, v, w]
+ * checkpoint's own layout (saved_models/mlp_diff_300x100_3l.pth): input_layer.weight [H,5], .bias [H];
+ * hidden_layer.{0..n_hidden-1}.weight [H,H], .bias [H]; out_layer.weight [3,H], .bias [3].
+ * Supported: hidden H in {64, 128, 256, 512} x n_hidden in {1, 2, 3, 4}; anything else is MPPI_ERR_SHAPE, and
+ * mppi_last_error names the set.  512 x 3 (the architecture the reference trains, mlp_diff_300x100_3l*.pth) and 512 x 2 (its
+ * older checkpoints mlp_diff.pth, mlp_diff_300x100.pth, mlp_diff_300x100_v2.pth) run k_rollout_mlp_h3 (MPPI_MLP_FORM,
+ * MPPI_MLP_TERMS, MPPI_MLP_F32 apply); every other shape runs k_rollout_mlp_w<H, ...> (the same arithmetic, H / 64 waves).
+ * Numeric range: the default kernels carry weights, inputs and activations as pairs of f16 numbers.  Inputs [x, y, yaw, v, w]
  * and first-layer pre-activations of ANY finite magnitude are handled (per-sample power-of-two scales inside the kernel); a
- * WEIGHT beyond +-65504 cannot be, so such a model is served by the f32-input MFMA kernel instead (about 3x slower, same
- * results to the tolerance of the tests); mppi_last_error then says so and mppi_get_rollout_kernel returns "k_rollout_mlp(".
+ * WEIGHT beyond +-65504 cannot be: at 512 x 3 / 512 x 2 such a model is served by the f32-input MFMA kernel instead (about 3x
+ * slower, same results to the tolerance of the tests; mppi_last_error then says so and mppi_get_rollout_kernel returns
+ * "k_rollout_mlp("); the other shapes have no f32-input kernel and return MPPI_ERR_UNSUPPORTED, as they do with MPPI_MLP_F32=1.
  */
 int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, const float *w_in, const float *b_in,
                  const float *const *w_hidden, const float *const *b_hidden, const float *w_out, const float *b_out);
@@ -379,7 +382,8 @@ int mppi_get_rollout_layout(const mppi_handle *h, int32_t *layout);
  * "k_rollout_fused<float, 0, 1, false, 2, false>", "k_rollout_dual<float, 1, 1, false, 2, true>"): bench.py looks the
  * launch's counter figures up under this name in profiles/.  A learned-dynamics handle answers as soon as mppi_set_mlp has
  * run: "k_rollout_mlp_h3<false, 8, 2, 3>" (operands as two f16 halves, the default) or "k_rollout_mlp(" (f32-input MFMA: chosen by
- * MPPI_MLP_F32=1, or by mppi_set_mlp itself when a weight exceeds the f16 range). */
+ * MPPI_MLP_F32=1, or by mppi_set_mlp itself when a weight exceeds the f16 range) for 512 x 3 and 512 x 2;
+ * "k_rollout_mlp_w<H, false>" for every other shape. */
 int mppi_get_rollout_kernel(const mppi_handle *h, char *buf, int32_t n);
 
 /*
