@@ -186,11 +186,19 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     if (c.n_agents < 1) c.n_agents = 1;
     if (c.n_agents > 1) {
         if (c.n_agents > 4096) FAIL((mppi_handle *)nullptr, MPPI_ERR_SHAPE, "mppi_create: n_agents %d > 4096", c.n_agents);
-        if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL || c.K_global != c.K || c.model == MPPI_MODEL_DIFFDRIVE_MLP ||
-            !fused_supported(c.T) || fused_blocks(c.K, c.T, rollout_layout(c.K, c.T, c.n_agents, c.model == MPPI_MODEL_RACECAR ? MODEL_RACE : MODEL_DIFF, c.precision == MPPI_PREC_F64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT)) > 512)
+        if (c.model == MPPI_MODEL_DIFFDRIVE_MLP) {
+            // one learned model for every agent: k_rollout_mlp_h3_agents / k_rollout_mlp_w_agents, one 64-sample tile per
+            // workgroup and agent; at most 512 records per agent, which k_finalize merges itself (launch_merge is not agent-aware)
+            if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL || c.K_global != c.K || mlp_blocks(c.K, 64) > 512)
+                FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED,
+                     "several agents per learned-dynamics handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, at most 512 rollout "
+                     "workgroups of 64 samples per agent (K <= 32768) and no sharding (got K = %d, K_global = %d)", c.K, c.K_global);
+        } else if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL || c.K_global != c.K || !fused_supported(c.T) ||
+                   fused_blocks(c.K, c.T, rollout_layout(c.K, c.T, c.n_agents, c.model == MPPI_MODEL_RACECAR ? MODEL_RACE : MODEL_DIFF, c.precision == MPPI_PREC_F64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT)) > 512) {
             FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED,
-                 "several agents per handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, an analytic model, T <= 128, at most 512 "
-                 "rollout workgroups (K <= 8192) and no sharding");
+                 "several agents per handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, T <= 128, at most 512 rollout workgroups "
+                 "(K <= 8192) and no sharding");
+        }
     }
     const double det = c.sigma[0] * c.sigma[3] - c.sigma[1] * c.sigma[2];
     if (!(c.sigma[0] > 0) || !(det > 0))
@@ -212,7 +220,7 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         FAIL((mppi_handle *)nullptr, MPPI_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only",
              c.device, prop.gcnArchName);
 
-    if (c.n_agents > 1 && getenv("MPPI_FORCE_UNFUSED"))
+    if (c.n_agents > 1 && c.model != MPPI_MODEL_DIFFDRIVE_MLP && getenv("MPPI_FORCE_UNFUSED"))
         FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED, "several agents per handle need the fused rollout kernels");
     mppi_handle *h = new mppi_handle();
     h->cfg = c;
@@ -410,6 +418,13 @@ extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, co
     if (!h3_shape && getenv("MPPI_MLP_F32"))
         FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: MPPI_MLP_F32 is set, and the f32-input kernel serves only the 512 x 3 and "
                                       "512 x 2 models (got hidden = %d, n = %d)", H, n_hidden);
+    // several agents per handle run the split kernels only (k_rollout_mlp_h3_agents, k_rollout_mlp_w_agents)
+    if (h->B > 1 && !f16_range)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: max |weight| = %.4g exceeds the f16 range, and the f32-input kernel that "
+                                      "serves such a model runs one agent per handle (n_agents = %d)", wmax, h->B);
+    if (h->B > 1 && getenv("MPPI_MLP_F32"))
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: MPPI_MLP_F32 is set, and the f32-input kernel runs one agent per handle "
+                                      "(n_agents = %d)", h->B);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
     // A cached closed-loop graph (ensure_graph) holds the previous model's MlpParams -- device pointers into the buffers
@@ -754,7 +769,7 @@ static void launch_front(mppi_handle *h, const KParams<R> &P, double beta, hipSt
         else if (h->fused) launch_rollout_fused<R>(P, h->d_partials, s);
         else launch_rollout<R>(P, s);
     }
-    h->rollout_kernel = mlp ? mlp_kernel_name(h->mlp) : last_rollout_kernel();
+    h->rollout_kernel = mlp ? mlp_kernel_name(h->mlp, h->B) : last_rollout_kernel();
     if (tm) hipEventRecord(next_event(h), s);
     if (tm) hipEventRecord(next_event(h), s);
     if (!mlp && !h->fused) launch_reduce<R>(P, h->d_partials, h->n_blocks, s);
@@ -1921,7 +1936,7 @@ extern "C" int mppi_get_rollout_layout(const mppi_handle *h, int32_t *layout) {
 
 extern "C" int mppi_get_rollout_kernel(const mppi_handle *h, char *buf, int32_t n) {
     if (!h || !buf || n < 1) return MPPI_ERR_BAD_ARG;
-    const char *nm = h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP && h->mlp_set ? mlp_kernel_name(h->mlp) : h->rollout_kernel;
+    const char *nm = h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP && h->mlp_set ? mlp_kernel_name(h->mlp, h->B) : h->rollout_kernel;
     snprintf(buf, (size_t)n, "%s", nm ? nm : "");
     return MPPI_OK;
 }

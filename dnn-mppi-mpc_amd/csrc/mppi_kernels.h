@@ -256,7 +256,8 @@ void launch_viz_mlp(const KParams<float> &P, const MlpParams &Q, const float *u_
                     float *opt, float *smp, hipStream_t s);
 int mlp_blocks(int K, int tile);            // workgroups = softmin records of a launch over K samples
 int mlp_tile(const MlpParams &Q);          // samples per workgroup of the rollout kernel that serves Q (64)
-const char *mlp_kernel_name(const MlpParams &Q);  // as rocprofv3 spells the rollout kernel that serves Q
+// as rocprofv3 spells the rollout kernel that serves Q on a handle of n_agents agents (> 1: the batched kernels)
+const char *mlp_kernel_name(const MlpParams &Q, int n_agents = 1);
 void pack_linear(const float *w, int n_in, float *packed, int n_out = 512);  // host: [n_out][n_in] -> fragment order
 void pack_linear_h3(const float *w, int n_in, unsigned short *packed, int n_out = 512);  // host: -> two f16 planes in fragment order
 constexpr int MODEL_DIFF_MLP = 2;

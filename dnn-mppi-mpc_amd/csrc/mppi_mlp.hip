@@ -702,122 +702,40 @@ __device__ unsigned long long g_mlp_phase[16];
 constexpr int W256_REF_LDS = 128;
 constexpr int h3_ref_cap(int rt, int h) { return rt == 1 ? H3_REF_LDS_32 : h == 256 ? W256_REF_LDS : MLP_REF_LDS_MAX; }
 
+// Several agents per launch (mppi_config.n_agents > 1): workgroup row a = blockIdx.y runs agent a, which sees
+// the handle's parameters with its own nominal controls u + 2 T a, costs and waypoint outputs S / pout + K a, controller
+// state st + a (x0, x0 index, iteration), noise (Philox stream noise_stream + a, or its tensor of the caller's ring) and
+// record heads + 4 slots a -- the layout of k_rollout_fused<..., MULTI>, which k_finalize's batched path reads.  The
+// records themselves: mlp_agent_records.  The single-agent kernels never call these, so their code stays what it was.
+__device__ __forceinline__ KParams<float> mlp_agent(const KParams<float> &P, int a) {
+    KParams<float> A = P;
+    A.u += (size_t)a * 2 * P.T;
+    A.S += (size_t)a * P.K;
+    A.pout += (size_t)a * P.K;
+    A.st += a;
+    A.noise_stream += a;
+    if (P.eps) A.eps += (size_t)a * P.K * P.T * 2;  // eps_tensor(A, iter, 0) == eps_tensor(P, iter, a)
+    A.heads += (size_t)a * P.slots * 4;
+    return A;
+}
+__device__ __forceinline__ float *mlp_agent_records(const KParams<float> &P, float *partials, int a) {
+    return partials + (size_t)a * P.slots * record_len(P.T, 4);
+}
+
 template <bool VIZ, int NW, int RT, int TERMS = 3>
 __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3(const KParams<float> P, const MlpParams Q,
                                                                float *__restrict__ partials, const MlpViz V) {
-#ifdef MPPI_STAMPS
-    unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_t = clock64();
-#endif
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int M = 32 * RT;  // samples of this workgroup's tile
-    _Float16 *a_hi = reinterpret_cast<_Float16 *>(smem);   // [M][520]
-    _Float16 *a_lo = a_hi + M * H3_PITCH;
-    _Float16 *z_hi = a_lo + M * H3_PITCH;                  // [M][24] layer-0 input rows {x, y, yaw, v, w, 0 ...}: one k-step
-    _Float16 *z_lo = z_hi + M * H3_ZPITCH;
-    float *ypart = reinterpret_cast<float *>(z_lo + M * H3_ZPITCH);  // [NW][M][4]
-    float *zscale = ypart + NW * M * 4;                             // [M][4] per-sample {s0, 1 / s1, s1, 0} (H3Scale)
-    float *ref_lds = zscale + M * 4;                                // [n_ref][4] when the path fits
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int k0 = ((int)blockIdx.x + (VIZ ? V.block0 : 0)) * M, k = k0 + lane;
-    const KParams<float> PL = mlp_stage_path(P, ref_lds, RT == 1 ? H3_REF_LDS_32 : MLP_REF_LDS_MAX);
-    const DevState sv = load_state(P, P.st);
-    const ObsLanes<float> obs = load_obstacles(P, lane);
-    if (!VIZ && k0 + M <= sv.k_start) return;
-    const bool in_tile = lane < M;  // (a 32-sample tile: the upper half of wave 0 carries no sample)
-    const bool valid = in_tile && k < P.K, live = valid && k >= sv.k_start;
-    // VIZ: the workgroup behind the samples' carries the nominal sequence in its lane 0
-    const bool eval = VIZ && V.ex != nullptr, eval_row = eval && k < V.en;
-    const bool opt_row = VIZ && !eval && k0 >= P.K && lane == 0 && V.opt != nullptr;
-    const bool smp_row = VIZ && !eval && valid && V.smp != nullptr;
-    const int c = sv.c;
-    const unsigned iter = (unsigned)sv.iter;
-    MlpLane L{(float)sv.x0[0], (float)sv.x0[1], (float)sv.x0[2], 0.f, c};
-    if (eval_row) { L.x = V.ex[3 * k]; L.y = V.ex[3 * k + 1]; L.yaw = V.ex[3 * k + 2]; }
-    const int n_steps = eval ? 1 : P.T;
-    const bool exploit = (k + P.k_offset) < P.n_exploit;
-    f32x16 acc[8 / NW][RT][2];
-    if (wid == 0 && in_tile) {  // the padding of the layer-0 rows stays zero
-        for (int q = 0; q < H3_ZPITCH; ++q) { z_hi[lane * H3_ZPITCH + q] = (_Float16)0.f; z_lo[lane * H3_ZPITCH + q] = (_Float16)0.f; }
-    }
-    for (int t = 0; t < n_steps; ++t) {
-        float u0 = 0, u1 = 0, v0 = 0, v1 = 0;
-        if (wid == 0) {
-            if (eval) {
-                if (eval_row) { v0 = V.ev[2 * k]; v1 = V.ev[2 * k + 1]; }
-            } else if (VIZ) mlp_controls_viz(P, V, k, t, smp_row, opt_row, exploit, v0, v1);
-            else mlp_controls(P, iter, k, t, valid, exploit, u0, u1, v0, v1);
-            const float z[5] = {L.x, L.y, L.yaw, v0, v1};
-            const H3Scale hs = h3_scale(z, Q.in_gain, Q.in_bias);
-            if (in_tile) {
-                *reinterpret_cast<F4 *>(zscale + 4 * lane) = F4{{hs.s0, hs.inv_s1, hs.s1, 0.f}};
-#pragma unroll
-                for (int q = 0; q < 5; ++q) split_h3(z[q] * hs.inv_s0, z_hi[lane * H3_ZPITCH + q], z_lo[lane * H3_ZPITCH + q]);
-            }
-        }
-        __syncthreads();
-        PH(0);
-        gemm_input_h3<NW, RT>(acc, z_hi, z_lo, Q.h3_w_in, wid, lane);
-        PH(1);
-        store_layer_h3<NW, RT, false, false, 1>(a_hi, a_lo, acc, Q.b_in, wid, lane, nullptr, nullptr, zscale);
-        H3Ring ring;
-        h3_prime_layer<NW>(Q.h3_w_h[0], wid, lane, ring);
-        PH(2);
-        __syncthreads();
-        PH(3);
-        const int l_last = Q.n_hidden - 1;  // (2 or 3 hidden layers: mppi_set_mlp)
-        for (int l = 0; l < l_last; ++l) {
-            gemm_layer_h3<NW, RT, TERMS>(acc, a_hi, a_lo, Q.h3_w_h[l], wid, lane, ring);
-            PH(4);
-            __syncthreads();
-            PH(5);
-            if (l == 0) store_layer_h3<NW, RT, true, false, 2>(a_hi, a_lo, acc, Q.b_h[l], wid, lane, nullptr, nullptr, zscale);
-            else store_layer_h3<NW, RT, true>(a_hi, a_lo, acc, Q.b_h[l], wid, lane);
-            h3_prime_layer<NW>(Q.h3_w_h[l + 1], wid, lane, ring);
-            PH(6);
-            __syncthreads();
-            PH(7);
-        }
-        {   // the last hidden layer and out_layer (Linear(512 -> 3), :35) in its epilogue: this wave's share of the 512 inputs
-            gemm_layer_h3<NW, RT, TERMS>(acc, a_hi, a_lo, Q.h3_w_h[l_last], wid, lane, ring);
-            PH(4);
-            float yo[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-            store_layer_h3<NW, RT, true, true>(a_hi, a_lo, acc, Q.b_h[l_last], wid, lane, Q.w_out, yo);
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {  // the two lane halves hold the two halves of a sample's features
-                F4 o;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) o.v[j] = yo[rt][j] + __shfl_xor(yo[rt][j], 32);
-                o.v[3] = 0.f;
-                if (lane < 32) *reinterpret_cast<F4 *>(ypart + (wid * M + rt * 32 + lane) * 4) = o;
-            }
-        }
-        PH(8);
-        __syncthreads();
-        if (wid == 0) {
-            float r0 = Q.b_out[0], r1 = Q.b_out[1], r2 = Q.b_out[2];
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const F4 o = *reinterpret_cast<const F4 *>(ypart + (w * M + (in_tile ? lane : 0)) * 4);
-                r0 += o.v[0];
-                r1 += o.v[1];
-                r2 += o.v[2];
-            }
-            if (VIZ) {
-                mlp_euler(P, r0, r1, r2, v0, v1, L);
-                float *dst = eval_row ? V.eout + (size_t)k * 3
-                             : opt_row ? V.opt + (size_t)t * 3 : smp_row ? V.smp + ((size_t)k * P.T + t) * 3 : nullptr;
-                if (dst) { dst[0] = L.x; dst[1] = L.y; dst[2] = L.yaw; }
-            } else {
-                mlp_advance(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
-            }
-        }
-        PH(9);
-    }
-    if (!VIZ && wid == 0) mlp_record(P, partials, iter, k, c, valid, live, L, lane);
-#ifdef MPPI_STAMPS
-    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && wid == 1)
-        for (int i = 0; i < 10; ++i) g_mlp_phase[i] = ph[i];
-#endif
+#include "mppi_mlp_h3_body.h"
+}
+// several agents per launch, agent = blockIdx.y (grid (mlp_blocks(K, 64), n_agents)); no visualisation form
+template <int NW, int RT, int TERMS>
+__global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3_agents(const KParams<float> P_all, const MlpParams Q,
+                                                                      float *__restrict__ partials_all) {
+    constexpr bool VIZ = false;
+    const KParams<float> P = mlp_agent(P_all, (int)blockIdx.y);
+    float *__restrict__ partials = mlp_agent_records(P_all, partials_all, (int)blockIdx.y);
+    const MlpViz V{};
+#include "mppi_mlp_h3_body.h"
 }
 
 // ------------------------------------------------------------------------------------------
@@ -831,123 +749,17 @@ __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3(con
 template <int H, bool VIZ>
 __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w(const KParams<float> P, const MlpParams Q, float *__restrict__ partials,
                                                                      const MlpViz V) {
-    constexpr int NW = H / 64, RT = 2, TERMS = 3;
-#ifdef MPPI_STAMPS
-    unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_t = clock64();
-#endif
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int M = 32 * RT;  // samples of this workgroup's tile
-    constexpr int PITCH = H + 8;                           // (H3_PITCH at 512)
-    _Float16 *a_hi = reinterpret_cast<_Float16 *>(smem);   // [M][H + 8]
-    _Float16 *a_lo = a_hi + M * PITCH;
-    _Float16 *z_hi = a_lo + M * PITCH;                     // [M][24] layer-0 input rows {x, y, yaw, v, w, 0 ...}: one k-step
-    _Float16 *z_lo = z_hi + M * H3_ZPITCH;
-    float *ypart = reinterpret_cast<float *>(z_lo + M * H3_ZPITCH);  // [NW][M][4]
-    float *zscale = ypart + NW * M * 4;                             // [M][4] per-sample {s0, 1 / s1, s1, 0} (H3Scale)
-    float *ref_lds = zscale + M * 4;                                // [n_ref][4] when the path fits
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int k0 = ((int)blockIdx.x + (VIZ ? V.block0 : 0)) * M, k = k0 + lane;
-    const KParams<float> PL = mlp_stage_path(P, ref_lds, h3_ref_cap(RT, H));
-    const DevState sv = load_state(P, P.st);
-    const ObsLanes<float> obs = load_obstacles(P, lane);
-    if (!VIZ && k0 + M <= sv.k_start) return;
-    const bool in_tile = lane < M;  // (a 32-sample tile: the upper half of wave 0 carries no sample)
-    const bool valid = in_tile && k < P.K, live = valid && k >= sv.k_start;
-    // VIZ: the workgroup behind the samples' carries the nominal sequence in its lane 0
-    const bool eval = VIZ && V.ex != nullptr, eval_row = eval && k < V.en;
-    const bool opt_row = VIZ && !eval && k0 >= P.K && lane == 0 && V.opt != nullptr;
-    const bool smp_row = VIZ && !eval && valid && V.smp != nullptr;
-    const int c = sv.c;
-    const unsigned iter = (unsigned)sv.iter;
-    MlpLane L{(float)sv.x0[0], (float)sv.x0[1], (float)sv.x0[2], 0.f, c};
-    if (eval_row) { L.x = V.ex[3 * k]; L.y = V.ex[3 * k + 1]; L.yaw = V.ex[3 * k + 2]; }
-    const int n_steps = eval ? 1 : P.T;
-    const bool exploit = (k + P.k_offset) < P.n_exploit;
-    f32x16 acc[H / 64 / NW][RT][2];
-    if (wid == 0 && in_tile) {  // the padding of the layer-0 rows stays zero
-        for (int q = 0; q < H3_ZPITCH; ++q) { z_hi[lane * H3_ZPITCH + q] = (_Float16)0.f; z_lo[lane * H3_ZPITCH + q] = (_Float16)0.f; }
-    }
-    for (int t = 0; t < n_steps; ++t) {
-        float u0 = 0, u1 = 0, v0 = 0, v1 = 0;
-        if (wid == 0) {
-            if (eval) {
-                if (eval_row) { v0 = V.ev[2 * k]; v1 = V.ev[2 * k + 1]; }
-            } else if (VIZ) mlp_controls_viz(P, V, k, t, smp_row, opt_row, exploit, v0, v1);
-            else mlp_controls(P, iter, k, t, valid, exploit, u0, u1, v0, v1);
-            const float z[5] = {L.x, L.y, L.yaw, v0, v1};
-            const H3Scale hs = h3_scale(z, Q.in_gain, Q.in_bias);
-            if (in_tile) {
-                *reinterpret_cast<F4 *>(zscale + 4 * lane) = F4{{hs.s0, hs.inv_s1, hs.s1, 0.f}};
-#pragma unroll
-                for (int q = 0; q < 5; ++q) split_h3(z[q] * hs.inv_s0, z_hi[lane * H3_ZPITCH + q], z_lo[lane * H3_ZPITCH + q]);
-            }
-        }
-        __syncthreads();
-        PH(0);
-        gemm_input_h3<NW, RT, H>(acc, z_hi, z_lo, Q.h3_w_in, wid, lane);
-        PH(1);
-        store_layer_h3<NW, RT, false, false, 1, H>(a_hi, a_lo, acc, Q.b_in, wid, lane, nullptr, nullptr, zscale);
-        H3Ring ring;
-        h3_prime_layer<NW, H>(Q.h3_w_h[0], wid, lane, ring);
-        PH(2);
-        __syncthreads();
-        PH(3);
-        const int l_last = Q.n_hidden - 1;  // (1 to 4 hidden layers, mppi_set_mlp)
-        for (int l = 0; l < l_last; ++l) {
-            gemm_layer_h3<NW, RT, TERMS, H>(acc, a_hi, a_lo, Q.h3_w_h[l], wid, lane, ring);
-            PH(4);
-            __syncthreads();
-            PH(5);
-            if (l == 0) store_layer_h3<NW, RT, true, false, 2, H>(a_hi, a_lo, acc, Q.b_h[l], wid, lane, nullptr, nullptr, zscale);
-            else store_layer_h3<NW, RT, true, false, 0, H>(a_hi, a_lo, acc, Q.b_h[l], wid, lane);
-            h3_prime_layer<NW, H>(Q.h3_w_h[l + 1], wid, lane, ring);
-            PH(6);
-            __syncthreads();
-            PH(7);
-        }
-        {   // the last hidden layer and out_layer (Linear(H -> 3), :35) in its epilogue: this wave's share of the H inputs
-            gemm_layer_h3<NW, RT, TERMS, H>(acc, a_hi, a_lo, Q.h3_w_h[l_last], wid, lane, ring);
-            PH(4);
-            float yo[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-            if (l_last == 0)  // one hidden layer: it is also the first, its accumulators those of h0 / s1
-                store_layer_h3<NW, RT, true, true, 2, H>(a_hi, a_lo, acc, Q.b_h[0], wid, lane, Q.w_out, yo, zscale);
-            else store_layer_h3<NW, RT, true, true, 0, H>(a_hi, a_lo, acc, Q.b_h[l_last], wid, lane, Q.w_out, yo);
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {  // the two lane halves hold the two halves of a sample's features
-                F4 o;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) o.v[j] = yo[rt][j] + __shfl_xor(yo[rt][j], 32);
-                o.v[3] = 0.f;
-                if (lane < 32) *reinterpret_cast<F4 *>(ypart + (wid * M + rt * 32 + lane) * 4) = o;
-            }
-        }
-        PH(8);
-        __syncthreads();
-        if (wid == 0) {
-            float r0 = Q.b_out[0], r1 = Q.b_out[1], r2 = Q.b_out[2];
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const F4 o = *reinterpret_cast<const F4 *>(ypart + (w * M + (in_tile ? lane : 0)) * 4);
-                r0 += o.v[0];
-                r1 += o.v[1];
-                r2 += o.v[2];
-            }
-            if (VIZ) {
-                mlp_euler(P, r0, r1, r2, v0, v1, L);
-                float *dst = eval_row ? V.eout + (size_t)k * 3
-                             : opt_row ? V.opt + (size_t)t * 3 : smp_row ? V.smp + ((size_t)k * P.T + t) * 3 : nullptr;
-                if (dst) { dst[0] = L.x; dst[1] = L.y; dst[2] = L.yaw; }
-            } else {
-                mlp_advance(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
-            }
-        }
-        PH(9);
-    }
-    if (!VIZ && wid == 0) mlp_record(P, partials, iter, k, c, valid, live, L, lane);
-#ifdef MPPI_STAMPS
-    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && wid == (NW > 1 ? 1 : 0))
-        for (int i = 0; i < 10; ++i) g_mlp_phase[i] = ph[i];
-#endif
+#include "mppi_mlp_w_body.h"
+}
+// several agents per launch (see k_rollout_mlp_h3_agents)
+template <int H>
+__global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_agents(const KParams<float> P_all, const MlpParams Q,
+                                                                            float *__restrict__ partials_all) {
+    constexpr bool VIZ = false;
+    const KParams<float> P = mlp_agent(P_all, (int)blockIdx.y);
+    float *__restrict__ partials = mlp_agent_records(P_all, partials_all, (int)blockIdx.y);
+    const MlpViz V{};
+#include "mppi_mlp_w_body.h"
 }
 #undef PH
 #ifdef MPPI_STAMPS
@@ -993,6 +805,7 @@ static bool mlp_is_w(const MlpParams &Q) { return !mlp_shape_is_h3(Q.hidden, Q.n
 template <int H>
 static void launch_w(const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz &v, bool viz, dim3 grid, hipStream_t s) {
     if (viz) hipLaunchKernelGGL((k_rollout_mlp_w<H, true>), grid, dim3(H), w_shmem(H), s, P, Q, (float *)partials, v);
+    else if (grid.y > 1) hipLaunchKernelGGL((k_rollout_mlp_w_agents<H>), grid, dim3(H), w_shmem(H), s, P, Q, (float *)partials);
     else hipLaunchKernelGGL((k_rollout_mlp_w<H, false>), grid, dim3(H), w_shmem(H), s, P, Q, (float *)partials, v);
 }
 static void launch_w_any(const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz &v, bool viz, dim3 grid, hipStream_t s) {
@@ -1021,10 +834,14 @@ static void launch_mlp_any(const KParams<float> &P, const MlpParams &Q, void *pa
 #undef H3_ATTR
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_h3<false, 8, 2, 2>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3_shmem(8, 2));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_h3_agents<8, 2, 3>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3_shmem(8, 2));
 #define W_ATTR(H_)                                                                                                       \
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_w<H_, false>),                               \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_shmem(H_));                             \
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_w<H_, true>),                                \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_shmem(H_));                             \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_w_agents<H_>),                                \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_shmem(H_))
         W_ATTR(64); W_ATTR(128); W_ATTR(256); W_ATTR(512);
 #undef W_ATTR
@@ -1039,7 +856,10 @@ static void launch_mlp_any(const KParams<float> &P, const MlpParams &Q, void *pa
         else if (form == H3_FORM_8x64) hipLaunchKernelGGL((k_rollout_mlp_h3<true, 8, 2>), grid, dim3(512), h3_shmem(8, 2), s, P, Q, (float *)partials, *viz);
         else hipLaunchKernelGGL((k_rollout_mlp_h3<true, 4, 2>), grid, dim3(256), h3_shmem(4, 2), s, P, Q, (float *)partials, *viz);
     } else if (mlp_is_w(Q)) {  // (MPPI_MLP_FORM / MPPI_MLP_TERMS / MPPI_MLP_F32 concern the 512 x 3 and 512 x 2 shapes only)
-        launch_w_any(P, Q, partials, none, false, dim3(mlp_blocks(P.K, mlp_tile(Q))), s);
+        launch_w_any(P, Q, partials, none, false, dim3(mlp_blocks(P.K, mlp_tile(Q)), P.n_agents > 1 ? P.n_agents : 1), s);
+    } else if (P.n_agents > 1) {  // several agents: the default form always (mppi_set_mlp refuses the f32-input kernel)
+        const dim3 grid(mlp_blocks(P.K, mlp_tile(Q)), P.n_agents);
+        hipLaunchKernelGGL((k_rollout_mlp_h3_agents<8, 2, 3>), grid, dim3(512), h3_shmem(8, 2), s, P, Q, (float *)partials);
     } else if (Q.use_h3) {
         const dim3 grid(mlp_blocks(P.K, mlp_tile(Q)));
         if (form == H3_FORM_8x64 && h3_terms() == 2)
@@ -1051,7 +871,16 @@ static void launch_mlp_any(const KParams<float> &P, const MlpParams &Q, void *pa
     }
 }
 
-const char *mlp_kernel_name(const MlpParams &Q) {
+const char *mlp_kernel_name(const MlpParams &Q, int n_agents) {
+    if (n_agents > 1) {
+        if (!mlp_is_w(Q)) return "k_rollout_mlp_h3_agents<8, 2, 3>";
+        switch (Q.hidden) {
+        case 64: return "k_rollout_mlp_w_agents<64>";
+        case 128: return "k_rollout_mlp_w_agents<128>";
+        case 256: return "k_rollout_mlp_w_agents<256>";
+        default: return "k_rollout_mlp_w_agents<512>";
+        }
+    }
     if (mlp_is_w(Q))
         switch (Q.hidden) {
         case 64: return "k_rollout_mlp_w<64, false>";

@@ -94,7 +94,12 @@ class Engine:
         ``scalers``: optional dict with the ``StandardScaler`` statistics the model was trained with
         (train/train_diff_mlp.py:72-86): ``in_mean``/``in_scale`` (5: state then control) and ``out_mean``/``out_scale``
         (3).  The affine maps are folded into the first and last Linear on the host (`mppi_set_mlp_scaled`), so the kernel
-        is unchanged: MLP((z - m_in) / s_in) * s_out + m_out."""
+        is unchanged: MLP((z - m_in) / s_in) * s_out + m_out.
+
+        A handle of ``n_agents`` > 1 (frozen or per-rollout index, K <= 32768) runs every agent with this one model in one
+        launch per stage (k_rollout_mlp_h3_agents / k_rollout_mlp_w_agents); there a model only the f32-input kernel can
+        serve (512 x 2 / 512 x 3 with weights beyond the f16 range, or MPPI_MLP_F32=1) is refused (``MppiError``,
+        MPPI_ERR_UNSUPPORTED)."""
         def arr(k):
             v = weights[k]
             if hasattr(v, "detach"):

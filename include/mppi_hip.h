@@ -121,7 +121,9 @@ typedef struct {
     uint64_t seed;               /* Philox key for the on-device sampler */
     /* Several independent MPPI problems ("agents") in one handle and one launch per stage:
      * same parameters, reference path and obstacles, separate state, nominal controls, waypoint index and noise.
-     * 0/1 = one agent (every entry point).  > 1: needs MPPI_WAYPOINT_FROZEN, T <= 128, K <= 8192 and no sharding;
+     * 0/1 = one agent (every entry point).  > 1: needs MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT and no sharding; the analytic
+     * models T <= 128 and K <= 8192; MPPI_MODEL_DIFFDRIVE_MLP K <= 32768 (one mppi_set_mlp serves every agent, on the
+     * f16-split kernels only: MPPI_MLP_F32 and weights beyond the f16 range are MPPI_ERR_UNSUPPORTED there);
      * mppi_set_state / mppi_get_state / mppi_set_u_prev / mppi_get_u_prev / mppi_get_costs then take [n_agents][...]
      * arrays and mppi_run_closed_loop advances all agents (stats: agent 0; an agent that reaches the end of its path
      * stops the call with MPPI_ERR_PATH_END); mppi_set_waypoint_idx / mppi_set_iteration apply to every agent; the
