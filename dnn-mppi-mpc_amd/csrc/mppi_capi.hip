@@ -26,10 +26,44 @@ static double now_s() {
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
+// Every environment switch of the library (INTEGRATION.md section 4 lists them and when each is read): the one place that
+// looks at the environment.  mppi_create keeps the result in the handle; mppi_set_mlp takes the three learned-dynamics
+// switches from a fresh reading and mppi_comm_connect the exchange timeout.
+static Switches read_switches() {
+    const auto set = [](const char *name) { return getenv(name) != nullptr; };
+    const auto num = [](const char *name, int unset) {
+        const char *e = getenv(name);
+        return e ? atoi(e) : unset;
+    };
+    const auto on_off = [&](const char *name) { return set(name) ? (int)(num(name, 0) != 0) : -1; };  // -1 unset, else 0 / 1
+    Switches sw;
+    sw.dual = on_off("MPPI_DUAL");
+    sw.pair = on_off("MPPI_PAIR");
+    sw.tri = on_off("MPPI_TRI");
+    sw.seq = set("MPPI_SEQ") ? (num("MPPI_SEQ", 0) == 2 ? 2 : 1) : -1;
+    sw.no_stream = set("MPPI_NO_STREAM");
+    sw.stream_passes = num("MPPI_STREAM_PASSES", 0);
+    sw.force_unfused = set("MPPI_FORCE_UNFUSED");
+    sw.no_hyp = set("MPPI_NO_HYP");
+    sw.no_poll = set("MPPI_NO_POLL");
+    sw.no_args = set("MPPI_NO_ARGS");
+    sw.traj_per_block = num("MPPI_TRAJ_PER_BLOCK", 0);
+    sw.graph = on_off("MPPI_GRAPH") == 1;  // (opt-in: see ensure_graph)
+    sw.graph_verbose = set("MPPI_GRAPH_VERBOSE");
+    sw.graph_slots = std::max(1, num("MPPI_GRAPH_SLOTS", 64));
+    sw.mlp.f32 = set("MPPI_MLP_F32");
+    sw.mlp.terms = num("MPPI_MLP_TERMS", 3) == 2 ? 2 : 3;
+    const char *form = getenv("MPPI_MLP_FORM");
+    sw.mlp.form = form && !strcmp(form, "4x64") ? 0 : form && !strcmp(form, "8x64") ? 1 : -1;
+    if (const char *e = getenv("MPPI_EXCHANGE_TIMEOUT_MS")) sw.exchange_timeout_ms = atoll(e);
+    return sw;
+}
+
 struct RcclUniqueId { char internal[128]; };  // ncclUniqueId (rccl.h: NCCL_UNIQUE_ID_BYTES), passed by value to ncclCommInitRank
 
 struct mppi_handle {
     mppi_config cfg;
+    Switches sw;              // the environment as mppi_create found it (sw.mlp: as the last mppi_set_mlp did)
     bool f64 = false;
     int nx = 3, n_ref = 0, n_obs = 0, n_blocks = 0, traj_per_block = 0;
     bool fused = false;       // rollout + softmin partial in one launch (T <= 128)
@@ -48,9 +82,9 @@ struct mppi_handle {
     std::vector<double> ref_host;   // [n_ref][4] as the kernels see it (rounded to the handle's precision)
     StepResult *res_mapped = nullptr;  // device-side address of the pinned host result (polled completion)
     long long seq = 0;
-    bool poll = true, idx_valid = true, by_args_ok = true;
+    bool idx_valid = true;
     int layout = 0;  // rollout_layout(K, T): which fused rollout kernel serves this handle
-    const char *rollout_kernel = "";  // the instantiation the last rollout-class launch took (mppi_get_rollout_kernel)
+    const char *rollout_kernel = "";  // RolloutPlan::name of the last rollout launch, or of the model mppi_set_mlp loaded (mppi_get_rollout_kernel)
     MlpParams mlp;
     bool mlp_set = false;
     void *d_ref = nullptr, *d_obs = nullptr, *d_u = nullptr, *d_uhist = nullptr, *d_S = nullptr;
@@ -122,6 +156,20 @@ extern "C" int mppi_device_count(void) {
 
 static size_t rsz(const mppi_handle *h) { return h->f64 ? sizeof(double) : sizeof(float); }
 
+// ABI model -> the kernels' model (the learned model rolls the diff-drive state)
+static int kernel_model(const mppi_config &c) { return c.model == MPPI_MODEL_RACECAR ? MODEL_RACE : MODEL_DIFF; }
+// the softmin rate
+static double softmin_beta(const mppi_config &c) {
+    return c.beta_mode == MPPI_BETA_INV_EXPLORATION ? 1.0 / c.param_exploration
+           : c.beta_mode == MPPI_BETA_INV_LAMBDA    ? 1.0 / c.param_lambda
+                                                    : c.param_lambda;
+}
+// The sequential index only grows: once it sits on the last waypoint every search window holds one candidate and nothing
+// can move.  index_can_move: the handle runs the kernels that resolve the index in one launch, and it has not got there.
+static bool at_path_end(const mppi_handle *h, int idx) { return idx >= h->n_ref - 1; }
+static bool index_can_move(const mppi_handle *h) { return h->hyp && !(h->idx_valid && h->n_ref > 0 && at_path_end(h, h->idx)); }
+template <typename R> static KParams<R> make_params(const mppi_handle *h, const float *eps);
+
 // host double[] -> device array in the kernel precision
 static int upload_real(mppi_handle *h, void *dst, const double *src, size_t n) {
     if (h->f64) {
@@ -151,6 +199,7 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         FAIL((mppi_handle *)nullptr, MPPI_ERR_BAD_ARG, "mppi_create: struct_size %d != %zu (ABI mismatch)",
              cfg->struct_size, sizeof(mppi_config));
     mppi_config c = *cfg;
+    const Switches sw = read_switches();
     if (c.K_global == 0) c.K_global = c.K;
     if (c.K > (1 << 20) || c.T > 2048)
         FAIL((mppi_handle *)nullptr, MPPI_ERR_SHAPE, "K=%d / T=%d beyond the supported 2^20 samples / 2048 steps", c.K, c.T);
@@ -194,7 +243,7 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
                      "several agents per learned-dynamics handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, at most 512 rollout "
                      "workgroups of 64 samples per agent (K <= 32768) and no sharding (got K = %d, K_global = %d)", c.K, c.K_global);
         } else if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL || c.K_global != c.K || !fused_supported(c.T) ||
-                   fused_blocks(c.K, c.T, rollout_layout(c.K, c.T, c.n_agents, c.model == MPPI_MODEL_RACECAR ? MODEL_RACE : MODEL_DIFF, c.precision == MPPI_PREC_F64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT)) > 512) {
+                   fused_blocks(c.K, c.T, rollout_layout(sw, c.K, c.T, c.n_agents, kernel_model(c), c.precision == MPPI_PREC_F64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT)) > 512) {
             FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED,
                  "several agents per handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, T <= 128, at most 512 rollout workgroups "
                  "(K <= 8192) and no sharding");
@@ -220,26 +269,25 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         FAIL((mppi_handle *)nullptr, MPPI_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only",
              c.device, prop.gcnArchName);
 
-    if (c.n_agents > 1 && c.model != MPPI_MODEL_DIFFDRIVE_MLP && getenv("MPPI_FORCE_UNFUSED"))
+    if (c.n_agents > 1 && c.model != MPPI_MODEL_DIFFDRIVE_MLP && sw.force_unfused)
         FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED, "several agents per handle need the fused rollout kernels");
     mppi_handle *h = new mppi_handle();
     h->cfg = c;
+    h->sw = sw;
     h->f64 = c.precision == MPPI_PREC_F64;
     h->nx = c.model == MPPI_MODEL_RACECAR ? 4 : 3;
-    int tpb = 0;
-    if (const char *e = getenv("MPPI_TRAJ_PER_BLOCK")) tpb = atoi(e);
+    int tpb = sw.traj_per_block;
     if (tpb < 1) tpb = (c.K + 127) / 128;
     tpb = ((tpb + 3) / 4) * 4;
     if (tpb > 2048) tpb = 2048;
     h->traj_per_block = tpb;
     h->n_blocks = reduce_blocks(c.K, tpb);
-    h->fused = fused_supported(c.T) && !getenv("MPPI_FORCE_UNFUSED");
-    h->graph_on = getenv("MPPI_GRAPH") && atoi(getenv("MPPI_GRAPH")) != 0;  // (opt-in: see ensure_graph)
+    h->fused = fused_supported(c.T) && !sw.force_unfused;
+    h->graph_on = sw.graph;
     // (k_rollout_tri: the race car as the reference runs it -- frozen index, `S[k] +=` -- one agent, f32)
     const bool tri_ok = c.model == MPPI_MODEL_RACECAR && !h->f64 && c.n_agents == 1 && c.waypoint_mode == MPPI_WAYPOINT_FROZEN &&
                         c.accumulate_stage_cost;
-    h->layout = rollout_layout(c.K, c.T, c.n_agents, c.model == MPPI_MODEL_RACECAR ? MODEL_RACE : MODEL_DIFF, h->f64,
-                               c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT, tri_ok);
+    h->layout = rollout_layout(sw, c.K, c.T, c.n_agents, kernel_model(c), h->f64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT, tri_ok);
     h->n_part = h->fused ? fused_blocks(c.K, c.T, h->layout) : h->n_blocks;
     if (c.model == MPPI_MODEL_DIFFDRIVE_MLP) h->n_part = mlp_blocks(c.K, 64);  // (mppi_set_mlp sets it again for the kernel that serves the model)
     h->res_bytes = sizeof(StepResult) + sizeof(double) * 2 * c.T;
@@ -258,9 +306,8 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     if ((e = hipMalloc((void **)&h->d_pout, B * sizeof(int) * c.K)) != hipSuccess) return fail(e, "hipMalloc(pout)");
     const size_t rec_bytes = sizeof(double) * (size_t)record_len(c.T, 8);  // enough for either precision
     // zero-filled and padded by 256 records: the merge kernels read 256 slots unconditionally
-    // (the streaming kernel that serves noise tensors in the two-samples-per-wave layout leaves up to one record per 32
-    // samples whatever the handle's own count is: room for the larger of the two)
-    const size_t n_rec_max = std::max<size_t>((size_t)h->n_part, (h->layout & LAYOUT_KIND) == LAYOUT_DUAL ? ((size_t)c.K + 31) / 32 : 0);
+    // (a launch may leave more records than the handle's own count -- fused_max_records: room for the larger of the two)
+    const size_t n_rec_max = (size_t)std::max(h->n_part, fused_max_records(c.K, c.T, h->layout));
     const size_t slots = n_rec_max + 256, n1 = B * slots, n2 = n_rec_max / 64 + 2 + 256;
     h->slots = (int)slots;
     if ((e = hipMalloc(&h->d_partials, rec_bytes * n1)) != hipSuccess) return fail(e, "hipMalloc(partials)");
@@ -278,7 +325,7 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     const bool lb_layout = (h->layout & LAYOUT_KIND) == LAYOUT_FUSED || h->layout == LAYOUT_DUAL;  // (one pass per workgroup)
     h->hyp = h->fused && lb_layout && c.T <= 64 && c.model == MPPI_MODEL_DIFFDRIVE &&
              c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL && !c.accumulate_stage_cost && (c.search_window == HYP_WINDOW || c.search_window == HYP_WINDOW_CUDA) &&
-             c.n_agents == 1 && h->n_part <= HYP_MAX_BLOCKS && !getenv("MPPI_NO_HYP");
+             c.n_agents == 1 && h->n_part <= HYP_MAX_BLOCKS && !sw.no_hyp;
     if (h->hyp) {
         const size_t lb_bytes = sizeof(unsigned) * (size_t)LB_COPIES * LB_COPY_STRIDE;
         if ((e = hipMalloc((void **)&h->d_hyp_slots, lb_bytes)) != hipSuccess) return fail(e, "hipMalloc(look-back words)");
@@ -292,8 +339,6 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         return fail(e, "hipHostMalloc(result)");
     if ((e = hipHostGetDevicePointer((void **)&h->res_mapped, h->h_res, 0)) != hipSuccess)
         return fail(e, "hipHostGetDevicePointer(result)");
-    h->poll = !getenv("MPPI_NO_POLL");
-    h->by_args_ok = !getenv("MPPI_NO_ARGS");
     if ((e = hipMemset(h->d_u, 0, B * r * 2 * c.T)) != hipSuccess) return fail(e, "hipMemset");    // u_prev = 0 (:82)
     if ((e = hipMemset(h->d_uhist, 0, B * r * 4 * c.T)) != hipSuccess) return fail(e, "hipMemset");
     if ((e = hipMemset(h->d_S, 0, B * r * c.K)) != hipSuccess) return fail(e, "hipMemset");
@@ -412,17 +457,18 @@ extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, co
     for (int l = 0; l < n_hidden; ++l)
         for (size_t i = 0; i < (size_t)H * H; ++i) wmax = fmax(wmax, fabs((double)w_hidden[l][i]));
     const bool f16_range = wmax <= 65504.0;  // (false for NaN too)
+    const Switches sw = read_switches();     // (MPPI_MLP_F32 / _TERMS / _FORM hold for this model until the next mppi_set_mlp)
     if (!h3_shape && !f16_range)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: max |weight| = %.4g exceeds the f16 range, and only the 512 x 3 and 512 x 2 "
                                       "models have an f32-input kernel to serve that (got hidden = %d, n = %d)", wmax, H, n_hidden);
-    if (!h3_shape && getenv("MPPI_MLP_F32"))
+    if (!h3_shape && sw.mlp.f32)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: MPPI_MLP_F32 is set, and the f32-input kernel serves only the 512 x 3 and "
                                       "512 x 2 models (got hidden = %d, n = %d)", H, n_hidden);
     // several agents per handle run the split kernels only (k_rollout_mlp_h3_agents, k_rollout_mlp_w_agents)
     if (h->B > 1 && !f16_range)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: max |weight| = %.4g exceeds the f16 range, and the f32-input kernel that "
                                       "serves such a model runs one agent per handle (n_agents = %d)", wmax, h->B);
-    if (h->B > 1 && getenv("MPPI_MLP_F32"))
+    if (h->B > 1 && sw.mlp.f32)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: MPPI_MLP_F32 is set, and the f32-input kernel runs one agent per handle "
                                       "(n_agents = %d)", h->B);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
@@ -468,7 +514,7 @@ extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, co
         HIPCHECK(h, hipMemcpy(h->d_mlp16, h16.data(), tot16 * sizeof(unsigned short), hipMemcpyHostToDevice));
         h->mlp.h3_w_in = h->d_mlp16;
         for (int l = 0; l < MLP_MAX_HIDDEN; ++l) h->mlp.h3_w_h[l] = h->d_mlp16 + n_in16 + (size_t)l * n_h16;
-        h->mlp.use_h3 = getenv("MPPI_MLP_F32") ? 0 : 1;
+        h->mlp.use_h3 = sw.mlp.f32 ? 0 : 1;
         if (!f16_range) {  // (512 x 3 / 512 x 2 only: refused above otherwise)
             h->mlp.use_h3 = 0;
             char b[256];
@@ -489,7 +535,11 @@ extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, co
     }
     h->mlp.n_hidden = n_hidden;
     h->mlp.hidden = H;
-    h->n_part = mlp_blocks(h->cfg.K, mlp_tile(h->mlp));  // records the rollout kernel that serves this model leaves
+    h->sw.mlp = sw.mlp;
+    // the rollout kernel that serves this model: the records it leaves, and its name before the first launch already
+    const RolloutPlan plan = plan_mlp(make_params<float>(h, nullptr), h->mlp, h->sw);
+    h->n_part = plan.records;
+    h->rollout_kernel = plan.name;
     h->mlp_set = true;
     return MPPI_OK;
 }
@@ -617,7 +667,7 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.n_ref = h->n_ref;
     P.n_obs = c.obstacle_model == MPPI_OBSTACLE_NONE ? 0 : h->n_obs;
     P.window = c.search_window;
-    P.model = c.model == MPPI_MODEL_RACECAR ? MODEL_RACE : MODEL_DIFF;
+    P.model = kernel_model(c);
     P.accumulate = c.accumulate_stage_cost;
     P.sequential = c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL;
     P.per_rollout = c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT;
@@ -636,10 +686,7 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.umax0 = (R)c.u_max[0];
     P.umax1 = (R)c.u_max[1];
     P.wheel_base = (R)c.wheel_base;
-    const double beta = c.beta_mode == MPPI_BETA_INV_EXPLORATION ? 1.0 / c.param_exploration
-                        : c.beta_mode == MPPI_BETA_INV_LAMBDA    ? 1.0 / c.param_lambda
-                                                                 : c.param_lambda;
-    P.beta = (R)beta;
+    P.beta = (R)softmin_beta(c);
     P.gamma = (R)(c.param_lambda * (1.0 - c.param_alpha));  // :74
     P.penalty = (R)c.collision_penalty;
     P.two_pi = (R)(2.0 * M_PI);
@@ -674,9 +721,9 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.n_agents = h->B;
     P.layout = h->layout;
     P.heads = (R *)h->d_heads;
-    // the kernels that can resolve the sequential index in one launch -- while that index can still move: once it sits
-    // on the last waypoint (it only grows) every search window holds one candidate and the lean kernels serve
-    P.hyp = h->hyp && !(h->idx_valid && h->n_ref > 0 && h->idx >= h->n_ref - 1);
+    // the kernels that can resolve the sequential index in one launch -- while that index can still move: after that the
+    // lean kernels serve
+    P.hyp = index_can_move(h);
     P.lb_seq = 0;
     P.hyp_slots = h->d_hyp_slots;
     return P;
@@ -693,16 +740,14 @@ static FinalizeParams make_finalize(const mppi_handle *h, const void *partials, 
     F.filter_window = c.filter_window;
     F.clamp_u = c.clamp_u_after_update;
     F.raise_at_path_end = c.raise_at_path_end;
-    F.model = c.model == MPPI_MODEL_RACECAR ? MODEL_RACE : MODEL_DIFF;
+    F.model = kernel_model(c);
     F.sequential = c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL;
     F.plant = plant;
     F.n_ref = h->n_ref;
     F.window = c.search_window;
     F.is_f64 = h->f64;
     F.count_hits = c.obstacle_model != MPPI_OBSTACLE_NONE && h->n_obs > 0;
-    F.beta = c.beta_mode == MPPI_BETA_INV_EXPLORATION ? 1.0 / c.param_exploration
-             : c.beta_mode == MPPI_BETA_INV_LAMBDA    ? 1.0 / c.param_lambda
-                                                      : c.param_lambda;
+    F.beta = softmin_beta(c);
     if (!h->f64) F.beta = (double)(float)F.beta;  // the block partials were scaled with the f32 rate
     F.dt = c.delta_t;
     F.wheel_base = c.wheel_base;
@@ -722,7 +767,7 @@ static FinalizeParams make_finalize(const mppi_handle *h, const void *partials, 
     F.n_agents = h->B;
     F.res_stride = h->res_bytes;
     F.u0_trace = nullptr;
-    F.hyp = h->hyp && partials == h->d_partials && !(h->idx_valid && h->n_ref > 0 && h->idx >= h->n_ref - 1);
+    F.hyp = partials == h->d_partials && index_can_move(h);
     F.hyp_blocks = h->n_part;
     F.hyp_slots = h->d_hyp_slots;
     F.lb_seq = 0;
@@ -753,28 +798,30 @@ static bool timing_on(const mppi_handle *h) { return h->timing && h->ev_used + E
 constexpr int MAX_FINAL_PARTS = 256;   // = MERGE_MAX_RECORDS of the kernels (ABI records: one per rank)
 constexpr int MAX_DIRECT_PARTS = 512;  // block records k_finalize merges itself (two windows of 256)
 
-static void launch_mlp(mppi_handle *h, const KParams<float> &P, hipStream_t s) {
-    launch_rollout_mlp(P, h->mlp, h->d_partials, s);
+// the rollout launch of this handle (the learned model: f32 handles only, mppi_create refuses the rest)
+template <typename R> static RolloutPlan front_plan(const mppi_handle *h, const KParams<R> &P) {
+    if constexpr (sizeof(R) == 4)
+        if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) return plan_mlp(P, h->mlp, h->sw);
+    return plan_rollout<R>(P, h->fused, h->sw);
 }
-static void launch_mlp(mppi_handle *, const KParams<double> &, hipStream_t) {}  // rejected at create
+template <typename R> static void launch_front_plan(mppi_handle *h, const RolloutPlan &plan, const KParams<R> &P, hipStream_t s) {
+    if constexpr (sizeof(R) == 4)
+        if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) return launch_mlp(plan, P, h->mlp, h->d_partials, nullptr, s);
+    launch_rollout<R>(plan, P, h->d_partials, s);
+}
 
 template <typename R>
 static void launch_front(mppi_handle *h, const KParams<R> &P, double beta, hipStream_t s, const void **recs,
                          const void **heads, int *n_recs, bool tm) {
     if (tm) hipEventRecord(next_event(h), s);
-    const bool mlp = h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP;
+    const RolloutPlan plan = front_plan<R>(h, P);
     h->n_rollout_launches += h->rollout_repeats;
-    for (int rep = 0; rep < h->rollout_repeats; ++rep) {
-        if (mlp) launch_mlp(h, P, s);
-        else if (h->fused) launch_rollout_fused<R>(P, h->d_partials, s);
-        else launch_rollout<R>(P, s);
-    }
-    h->rollout_kernel = mlp ? mlp_kernel_name(h->mlp, h->B) : last_rollout_kernel();
+    for (int rep = 0; rep < h->rollout_repeats; ++rep) launch_front_plan<R>(h, plan, P, s);
+    h->rollout_kernel = plan.name;
     if (tm) hipEventRecord(next_event(h), s);
     if (tm) hipEventRecord(next_event(h), s);
-    if (!mlp && !h->fused) launch_reduce<R>(P, h->d_partials, h->n_blocks, s);
-    // (records per agent this launch left: the handle's count, or the streaming kernel's when that one served)
-    const int n_part = (!mlp && h->fused) ? fused_records<R>(P) : h->n_part;
+    if (h->cfg.model != MPPI_MODEL_DIFFDRIVE_MLP && !h->fused) launch_reduce<R>(P, h->d_partials, plan.records, s);
+    const int n_part = plan.records;  // (per agent)
     *recs = h->d_partials;
     *heads = h->d_heads;
     *n_recs = n_part;
@@ -939,21 +986,21 @@ static int step_impl(mppi_handle *h, const double *x0, const double *x0_dev, con
     const double t_call = now_s();
     KParams<R> P = make_params<R>(h, eps);
     FinalizeParams F = make_finalize(h, h->d_partials, h->n_part, 0);
-    const bool by_args = x0 && h->idx_valid && h->by_args_ok;
+    const bool by_args = x0 && h->idx_valid && !h->sw.no_args;
     if (!x0) {
         if (!h->idx_valid) FAIL(h, MPPI_ERR_STATE, "mppi_step_device_x0 after an asynchronous split step: call mppi_sync_result first");
         launch_set_state_dev<R>(P, x0_dev, h->nx, s);
     } else if (by_args) {
         P.use_args = F.use_args = 1;
         P.c_arg = F.c_arg = host_x0_call(h, x0);
-        P.hyp = F.hyp = h->hyp && P.c_arg < h->n_ref - 1;  // (a window of one candidate: nothing can move)
+        P.hyp = F.hyp = h->hyp && !at_path_end(h, P.c_arg);
         for (int i = 0; i < 4; ++i) P.x0_arg[i] = F.x0_arg[i] = x0[i];
     } else {
         launch_set_state<R>(P, x0, s);
     }
-    if (h->poll) F.res = h->res_mapped;
+    if (!h->sw.no_poll) F.res = h->res_mapped;
     for (int round = 0;; ++round) {
-        F.seq = h->poll ? ++h->seq : 0;
+        F.seq = !h->sw.no_poll ? ++h->seq : 0;
         launch_slot<R>(h, P, F, s);
         HIPCHECK(h, hipGetLastError());  // a refused launch would otherwise show only as the poll's timeout
         int rc = wait_result(h, F.seq, s);
@@ -1188,7 +1235,7 @@ extern "C" int mppi_rollout_viz(mppi_handle *h, float *optimal_traj, float *samp
     if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) {  // (fp32 only, checked at create)
         KParams<float> P = make_params<float>(h, eps);
         const float *hist = (const float *)h->d_uhist;
-        launch_viz_mlp(P, h->mlp, hist, hist + 2 * T, h->iter - 1, optimal_traj, sampled_traj, (hipStream_t)stream);
+        launch_viz_mlp(P, h->mlp, h->sw, hist, hist + 2 * T, h->iter - 1, optimal_traj, sampled_traj, (hipStream_t)stream);
     } else if (h->f64) {
         KParams<double> P = make_params<double>(h, eps);
         const double *hist = (const double *)h->d_uhist;
@@ -1476,10 +1523,7 @@ extern "C" int mppi_comm_connect(mppi_handle *h, int32_t rank, int32_t nranks, c
     HIPCHECK(h, hipMalloc((void **)&h->d_xerr, sizeof(int)));
     HIPCHECK(h, hipMalloc((void **)&h->d_xok, sizeof(int)));
     HIPCHECK(h, hipMemset(h->d_xerr, 0, sizeof(int)));
-    if (const char *e = getenv("MPPI_EXCHANGE_TIMEOUT_MS")) {
-        const long long ms = atoll(e);
-        if (ms > 0) h->x_timeout = ms * 100000LL;  // the wall clock counts at 100 MHz
-    }
+    if (const long long ms = read_switches().exchange_timeout_ms; ms > 0) h->x_timeout = ms * 100000LL;  // the wall clock counts at 100 MHz
     h->x_rank = rank;
     h->x_nranks = nranks;
     h->xseq = 0;
@@ -1521,11 +1565,7 @@ extern "C" int mppi_comm_probe(mppi_handle *h, void *stream) {
 // one wanders between 9.7 and 11.2, but over whole episodes (restarts, the eager traversal, re-captures when an argument
 // changes) it came out 0.1-0.4 us per iteration behind, so eager launches stay the default.  MPPI_GRAPH_SLOTS: iterations
 // per graph (experiments).
-static int graph_slots() {
-    static const int n = getenv("MPPI_GRAPH_SLOTS") ? atoi(getenv("MPPI_GRAPH_SLOTS")) : 64;
-    return n < 1 ? 1 : n;
-}
-#define GRAPH_SLOTS graph_slots()
+#define GRAPH_SLOTS (h->sw.graph_slots)
 template <typename R>
 static bool ensure_graph(mppi_handle *h, const KParams<R> &P, const FinalizeParams &F) {
     // (the learned model's parameters too: its launches carry MlpParams -- weight pointers, shape, output bias -- by value)
@@ -1536,8 +1576,7 @@ static bool ensure_graph(mppi_handle *h, const KParams<R> &P, const FinalizePara
     memcpy(key.data() + sizeof(P) + sizeof(F), tail, sizeof(tail));
     memcpy(key.data() + sizeof(P) + sizeof(F) + sizeof(tail), &h->mlp, sizeof(MlpParams));
     if (h->graph_exec[0] && key == h->graph_key) return true;
-    static const bool verbose = getenv("MPPI_GRAPH_VERBOSE") != nullptr;
-    if (verbose) fprintf(stderr, "[mppi] capturing a graph of %d iterations\n", GRAPH_SLOTS);
+    if (h->sw.graph_verbose) fprintf(stderr, "[mppi] capturing a graph of %d iterations\n", GRAPH_SLOTS);
     for (int i = 0; i < 2; ++i) {
         if (h->graph_exec[i]) hipGraphExecDestroy(h->graph_exec[i]);
         h->graph_exec[i] = nullptr;
@@ -1604,11 +1643,11 @@ static int closed_loop_impl(mppi_handle *h, int n_iters, double *u0_trace, mppi_
         // The last slot of the batch writes its result straight into mapped host memory and publishes a sequence word
         // the host polls (as mppi_step does): no copy launch and no stream synchronisation at the end of the call
         // (14 -> 7 us of fixed cost per call).  Several agents per handle: one result per agent, copied as before.
-        const bool poll = h->poll && h->B == 1;
+        const bool poll = !h->sw.no_poll && h->B == 1;
         const double t_enq = now_s();
         // the bulk of a long batch from the cached graph (see ensure_graph), the rest -- and the slot that publishes the
         // result -- eagerly behind it, all on the graph's stream, which waits for and is waited for by the caller's
-        const bool rests = h->cfg.waypoint_mode != MPPI_WAYPOINT_SEQUENTIAL || (idx_now >= 0 && idx_now >= h->n_ref - 1);
+        const bool rests = h->cfg.waypoint_mode != MPPI_WAYPOINT_SEQUENTIAL || (idx_now >= 0 && at_path_end(h, idx_now));
         hipStream_t ls = s;
         long long i = 0;
         if (h->graph_on && rests && !P.hyp && !u0_trace && h->x_nranks <= 1 && !timing_on(h) && todo > GRAPH_SLOTS &&
@@ -1659,7 +1698,7 @@ static int closed_loop_impl(mppi_handle *h, int n_iters, double *u0_trace, mppi_
         done = h->h_res->iter;  // slots spent on speculation rounds did not complete an iteration
         idx_now = h->h_res->idx_after;
         if (P.hyp) {
-            if (h->B == 1 && h->h_res->idx_after >= h->n_ref - 1) {
+            if (h->B == 1 && at_path_end(h, h->h_res->idx_after)) {
                 P.hyp = F.hyp = 0;
                 batch = 1LL << 62;
             } else {
@@ -1706,7 +1745,7 @@ template <typename R>
 static int time_rollout_impl(mppi_handle *h, int n_slots, int extra, hipStream_t s, double *us_out) {
     KParams<R> P = make_params<R>(h, nullptr);
     FinalizeParams F = make_finalize(h, h->d_partials, h->n_part, 1);
-    if (P.hyp || (h->cfg.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL && h->idx < h->n_ref - 1))
+    if (P.hyp || (h->cfg.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL && !at_path_end(h, h->idx)))
         FAIL(h, MPPI_ERR_STATE, "mppi_time_rollout_launch: the sequential waypoint index can still move (speculation rounds "
                                 "cannot be replayed from a graph); call it once the index rests at the end of the path");
     if (timing_on(h))
@@ -1749,7 +1788,7 @@ static int time_rollout_impl(mppi_handle *h, int n_slots, int extra, hipStream_t
         for (int r = 0; r < reps && e == hipSuccess; ++r) e = hipGraphLaunch(exec, gs);
         if (e == hipSuccess) e = hipEventRecord(e1, gs);
         if (e == hipSuccess) e = hipStreamSynchronize(gs);
-        if (getenv("MPPI_GRAPH_VERBOSE")) fprintf(stderr, "[mppi] variant %d: wall %.2f us per iteration\n", v, 1e6 * (now_s() - w0) / (reps * n_slots));
+        if (h->sw.graph_verbose) fprintf(stderr, "[mppi] variant %d: wall %.2f us per iteration\n", v, 1e6 * (now_s() - w0) / (reps * n_slots));
         float t = 0.f;
         if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
         ms[v] = t;
@@ -1800,7 +1839,7 @@ struct DevBuf {  // scratch device buffer released at scope exit
 };
 
 static void eval_transition_mlp(mppi_handle *h, const KParams<float> &P, const void *x, const void *v, int n, void *out) {
-    launch_eval_mlp(P, h->mlp, (const float *)x, (const float *)v, n, (float *)out, nullptr);
+    launch_eval_mlp(P, h->mlp, h->sw, (const float *)x, (const float *)v, n, (float *)out, nullptr);
 }
 static void eval_transition_mlp(mppi_handle *, const KParams<double> &, const void *, const void *, int, void *) {}  // rejected at create
 
@@ -1902,11 +1941,7 @@ extern "C" int mppi_eval_weights(mppi_handle *h, const double *S, int32_t n, dou
     HIPCHECK(h, in.alloc(sizeof(double) * (size_t)n));
     HIPCHECK(h, o.alloc(sizeof(double) * (size_t)n));
     HIPCHECK(h, hipMemcpy(in.p, S, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    const mppi_config &c = h->cfg;
-    const double beta = c.beta_mode == MPPI_BETA_INV_EXPLORATION ? 1.0 / c.param_exploration
-                        : c.beta_mode == MPPI_BETA_INV_LAMBDA    ? 1.0 / c.param_lambda
-                                                                 : c.param_lambda;
-    launch_eval_weights((const double *)in.p, n, beta, (double *)o.p, nullptr);
+    launch_eval_weights((const double *)in.p, n, softmin_beta(h->cfg), (double *)o.p, nullptr);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipDeviceSynchronize());
     HIPCHECK(h, hipMemcpy(w, o.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
@@ -1936,8 +1971,7 @@ extern "C" int mppi_get_rollout_layout(const mppi_handle *h, int32_t *layout) {
 
 extern "C" int mppi_get_rollout_kernel(const mppi_handle *h, char *buf, int32_t n) {
     if (!h || !buf || n < 1) return MPPI_ERR_BAD_ARG;
-    const char *nm = h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP && h->mlp_set ? mlp_kernel_name(h->mlp, h->B) : h->rollout_kernel;
-    snprintf(buf, (size_t)n, "%s", nm ? nm : "");
+    snprintf(buf, (size_t)n, "%s", h->rollout_kernel);
     return MPPI_OK;
 }
 

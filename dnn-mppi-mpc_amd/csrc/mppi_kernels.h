@@ -1,7 +1,9 @@
 // Internal interface between the C ABI (mppi_capi.hip) and the gfx950 kernels (mppi_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdint.h>
+#include <stdio.h>
 
 namespace mppi {
 
@@ -201,24 +203,94 @@ struct VizParams {
 };
 
 template <typename R> void launch_set_state(const KParams<R> &P, const double *x0_or_null, hipStream_t s);
-template <typename R> void launch_rollout(const KParams<R> &P, hipStream_t s);
 // softmin partial records are stored in the handle's precision R (block partials) or as double (the
 // per-rank record of the split step, include/mppi_hip.h)
 template <typename R> void launch_reduce(const KParams<R> &P, void *partials, int n_blocks, hipStream_t s);
-// rollout + cost + per-block softmin partial in one launch (T <= 128); fused_blocks(K) records
-template <typename R> void launch_rollout_fused(const KParams<R> &P, void *partials, hipStream_t s);
 bool fused_supported(int T);
-// the instantiation this thread's last rollout-class launch took, as rocprofv3 spells it ("k_rollout_dual<float, 1, 1, false, 2, true>")
-const char *last_rollout_kernel();
-// Which fused rollout kernel serves (K, T): decided ONCE per handle (it reads the MPPI_DUAL / MPPI_PAIR / MPPI_SEQ
-// overrides) and carried in KParams::layout, so that a launch costs no environment lookups.
+
+// The environment switches, read in ONE place -- read_switches() in mppi_capi.hip -- when a handle is
+// created (the learned-dynamics ones again at mppi_set_mlp, the exchange timeout at mppi_comm_connect) and kept in the
+// handle: rollout_layout() and the planners below take them as an argument, so that a launch costs no environment lookups
+// and the plan, the launch and the reported kernel name cannot disagree.
+struct Switches {
+    int dual = -1, pair = -1, tri = -1;  // MPPI_DUAL / MPPI_PAIR / MPPI_TRI: -1 unset, else 0 / 1
+    int seq = -1;                        // MPPI_SEQ: -1 unset, else its value (2: two passes per workgroup, else one)
+    bool no_stream = false;              // MPPI_NO_STREAM
+    int stream_passes = 0;               // MPPI_STREAM_PASSES (> 0: forced)
+    bool force_unfused = false, no_hyp = false, no_poll = false, no_args = false;  // MPPI_FORCE_UNFUSED / _NO_HYP / _NO_POLL / _NO_ARGS
+    int traj_per_block = 0;              // MPPI_TRAJ_PER_BLOCK
+    bool graph = false, graph_verbose = false;  // MPPI_GRAPH / MPPI_GRAPH_VERBOSE
+    int graph_slots = 64;                // MPPI_GRAPH_SLOTS
+    // the learned-dynamics switches, as the last mppi_set_mlp found them: MPPI_MLP_F32, MPPI_MLP_TERMS (2 or 3), MPPI_MLP_FORM
+    // (-1 the default form, 0 "4x64", 1 "8x64")
+    struct Mlp { bool f32 = false; int terms = 3, form = -1; } mlp;
+    long long exchange_timeout_ms = 0;   // MPPI_EXCHANGE_TIMEOUT_MS (> 0: set)
+};
+
+// One rollout launch, resolved once: which instantiation, how it is launched, what it is called and what it leaves.  Made by
+// plan_rollout (mppi_kernels.hip) / plan_mlp (mppi_mlp.hip) -- pure functions of the kernel parameters and the switches,
+// a handful of branches -- and executed by launch_plan.  A new kernel variant is one more entry in its family's planner.
+struct RolloutPlan {
+    const void *fn = nullptr;    // the __global__ instantiation
+    const char *name = "";       // as rocprofv3 spells it ("k_rollout_dual<float, 1, 1, false, 2, true, false>"); static storage
+    dim3 grid, block;
+    size_t lds = 0;              // dynamic LDS bytes
+    int records = 0;             // softmin records per agent the launch leaves (k_rollout: what launch_reduce leaves behind it)
+    int passes = 0;              // k_rollout_stream's batches per workgroup, else 0
+    bool *lds_raised = nullptr;  // per device: hipFuncAttributeMaxDynamicSharedMemorySize was raised to `lds` (null: not needed)
+};
+constexpr int PLAN_MAX_DEVICES = 64;
+// What is static about one instantiation, kept as a function-local static of its *_entry template beside the function
+// pointer: the name, formatted once from the template arguments it is launched with, and the `lds_raised` flags
+struct KernelEntry {
+    char name[96];
+    bool lds_raised[PLAN_MAX_DEVICES] = {};
+    __attribute__((format(printf, 2, 3))) explicit KernelEntry(const char *fmt, ...) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(name, sizeof(name), fmt, ap);
+        va_end(ap);
+    }
+    static const char *of(bool b) { return b ? "true" : "false"; }
+};
+inline RolloutPlan plan_entry(const void *fn, KernelEntry &e, int threads, size_t lds = 0) {
+    RolloutPlan p;
+    p.fn = fn;
+    p.name = e.name;
+    p.block = dim3(threads);
+    p.lds = lds;
+    p.lds_raised = lds ? e.lds_raised : nullptr;
+    return p;
+}
+// `args`: the kernel's arguments in order (a kernel with a shorter list takes the first ones).  Every kernel is launched
+// from the file that defines it: this is inline so that each of the two files carries its own copy.
+inline void launch_plan(const RolloutPlan &p, void **args, hipStream_t s) {
+    if (p.lds_raised) {  // (the attribute belongs to the device's copy of the code object: one process may drive several GPUs)
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        const bool known = dev >= 0 && dev < PLAN_MAX_DEVICES;
+        if (!known || !p.lds_raised[dev]) {
+            (void)hipFuncSetAttribute(p.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+            if (known) p.lds_raised[dev] = true;
+        }
+    }
+    (void)hipLaunchKernel(p.fn, p.grid, p.block, args, p.lds, s);
+}
+
+// Which fused rollout kernel serves (K, T): decided ONCE per handle (the MPPI_DUAL / MPPI_PAIR / MPPI_TRI / MPPI_SEQ
+// overrides arrive in `sw`) and carried in KParams::layout.
 enum { LAYOUT_FUSED = 0, LAYOUT_DUAL = 1, LAYOUT_PAIR = 2, LAYOUT_TRI = 3, LAYOUT_KIND = 3, LAYOUT_TWICE = 4 };  // (KIND: mask)
 // n_agents: problems batched in one launch; tri_ok: the handle is what k_rollout_tri serves (race car, f32, frozen index,
 // `S[k] +=`, one agent) -- it takes horizons of 65 .. 96 steps then
-int rollout_layout(int K, int T, int n_agents, int model, bool f64, bool per_rollout = false, bool tri_ok = false);
-int fused_blocks(int K, int T, int layout);  // workgroups = block records of one launch
-// records launch_rollout_fused(P) leaves (the streaming kernel, which serves tensors of noise, leaves fewer: see k_rollout_stream)
-template <typename R> int fused_records(const KParams<R> &P);
+int rollout_layout(const Switches &sw, int K, int T, int n_agents, int model, bool f64, bool per_rollout = false, bool tri_ok = false);
+int fused_blocks(int K, int T, int layout);  // workgroups = block records of a launch of the layout's own kernels
+// the most records per agent any fused launch of this layout can leave (the streaming kernel, which serves the two-samples-
+// per-wave layout where it can, leaves up to one per batch): what a handle sizes its record buffers by
+int fused_max_records(int K, int T, int layout);
+// the rollout launch of an analytic-model handle: k_rollout (fused false; launch_reduce follows, `records` is its count),
+// else k_rollout_fused / _dual / _tri by P.layout, or k_rollout_stream where it serves (T <= 128)
+template <typename R> RolloutPlan plan_rollout(const KParams<R> &P, bool fused, const Switches &sw);
+template <typename R> void launch_rollout(const RolloutPlan &plan, const KParams<R> &P, void *partials, hipStream_t s);
 // merges groups of `group` <= 256 records (precision R) of `recs[n]` into out[ceil(n/group)]
 // (`heads` / `out_heads`: the compact head arrays of the input / internal-layout output records)
 template <typename R>
@@ -246,18 +318,19 @@ template <typename R>
 void launch_viz(const KParams<R> &P, const R *u_before, const R *u_after_pre_shift, long long iter, float *opt,
                 float *smp, hipStream_t s);
 int reduce_blocks(int K, int traj_per_block);
-// config 5: rollout through the residual MLP on MFMA, one record per 64-sample tile
-void launch_rollout_mlp(const KParams<float> &P, const MlpParams &Q, void *partials, hipStream_t s);
+// config 5: rollout through the residual MLP on MFMA, one record per 64-sample tile.  plan_mlp covers the three forms of
+// that launch: the rollout (viz null; `records` per agent), the visualisation rollouts and the batched transition
+struct MlpViz;
+RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const MlpViz *viz = nullptr);
+void launch_mlp(const RolloutPlan &plan, const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz *viz, hipStream_t s);
 // the visualisation rollouts (mppi_differential_drive.py:144-159) with the learned model: opt [T][3], smp [K][T][3] (either
 // may be null); u_before / u_upd: the nominal controls before the update and the updated, unshifted ones
+void launch_viz_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const float *u_before, const float *u_upd,
+                    long long iter, float *opt, float *smp, hipStream_t s);
 // `_state_transition` with the learned model for n (state, control) rows: x [n][3], v [n][2] -> out [n][3]
-void launch_eval_mlp(const KParams<float> &P, const MlpParams &Q, const float *x, const float *v, int n, float *out, hipStream_t s);
-void launch_viz_mlp(const KParams<float> &P, const MlpParams &Q, const float *u_before, const float *u_upd, long long iter,
-                    float *opt, float *smp, hipStream_t s);
+void launch_eval_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const float *x, const float *v, int n,
+                     float *out, hipStream_t s);
 int mlp_blocks(int K, int tile);            // workgroups = softmin records of a launch over K samples
-int mlp_tile(const MlpParams &Q);          // samples per workgroup of the rollout kernel that serves Q (64)
-// as rocprofv3 spells the rollout kernel that serves Q on a handle of n_agents agents (> 1: the batched kernels)
-const char *mlp_kernel_name(const MlpParams &Q, int n_agents = 1);
 void pack_linear(const float *w, int n_in, float *packed, int n_out = 512);  // host: [n_out][n_in] -> fragment order
 void pack_linear_h3(const float *w, int n_in, unsigned short *packed, int n_out = 512);  // host: -> two f16 planes in fragment order
 constexpr int MODEL_DIFF_MLP = 2;

@@ -14,11 +14,6 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <string>
 
 #include "mppi_device.h"
 
@@ -2654,25 +2649,32 @@ __global__ __launch_bounds__(64) void k_set_state_dev(const R *ref, int n_ref, i
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-// Which instantiation the last rollout launch of this thread took, spelled as rocprofv3 prints it (bench.py looks its
-// counters up by this name): one static string per launch site, a pointer store per launch.
-static thread_local const char *g_last_rollout_kernel = "";
-const char *last_rollout_kernel() { return g_last_rollout_kernel; }
+// Plan entries: the one place per kernel family where template arguments turn into the function to launch and its name as
+// rocprofv3 prints it (bench.py looks its counters up by this name) -- both from the same arguments, the name formatted once.
 template <typename R> static const char *type_name() { return sizeof(R) == 8 ? "double" : "float"; }
-static std::string kernel_name(const char *fmt, ...) {
-    char b[160];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(b, sizeof(b), fmt, ap);
-    va_end(ap);
-    return b;
+template <typename R, int MODEL> static RolloutPlan rollout_entry() {
+    static KernelEntry e("k_rollout<%s, %d>", type_name<R>(), MODEL);
+    return plan_entry(reinterpret_cast<const void *>(k_rollout<R, MODEL>), e, 256);
 }
-#define MPPI_NOTE_KERNEL(...)                                       \
-    do {                                                            \
-        static const std::string _nm = kernel_name(__VA_ARGS__);    \
-        g_last_rollout_kernel = _nm.c_str();                        \
-    } while (0)
-static const char *tf(bool b) { return b ? "true" : "false"; }
+template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK> static RolloutPlan fused_entry() {
+    static KernelEntry e("k_rollout_fused<%s, %d, %d, %s, %d, %s>", type_name<R>(), MODEL, NCH, KernelEntry::of(MULTI), SPEC,
+                                 KernelEntry::of(HYPK));
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_fused<R, MODEL, NCH, MULTI, SPEC, HYPK>), e, 64 * FUSED_WAVES);
+}
+template <typename R, int MODEL, int SPW, bool MULTI, int SEQ, bool PLAIN, bool LB = false> static RolloutPlan dual_entry() {
+    static KernelEntry e("k_rollout_dual<%s, %d, %d, %s, %d, %s, %s>", type_name<R>(), MODEL, SPW, KernelEntry::of(MULTI), SEQ,
+                                 KernelEntry::of(PLAIN), KernelEntry::of(LB));
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_dual<R, MODEL, SPW, MULTI, SEQ, PLAIN, LB>), e, 64 * DUAL_WAVES);
+}
+template <bool PLAIN, bool SHARE> static RolloutPlan tri_entry() {
+    static KernelEntry e("k_rollout_tri<%s, %s>", KernelEntry::of(PLAIN), KernelEntry::of(SHARE));
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_tri<PLAIN, SHARE>), e, 64 * DUAL_WAVES);
+}
+template <typename R, bool MULTI, bool OBS, bool PHILOX> static RolloutPlan stream_entry() {
+    static KernelEntry e("k_rollout_stream<%s, %s, %s, %s>", type_name<R>(), KernelEntry::of(MULTI), KernelEntry::of(OBS),
+                                 KernelEntry::of(PHILOX));
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_stream<R, MULTI, OBS, PHILOX>), e, 64 * DUAL_WAVES);
+}
 
 int reduce_blocks(int K, int traj_per_block) { return (K + traj_per_block - 1) / traj_per_block; }
 
@@ -2684,17 +2686,6 @@ template <typename R> void launch_set_state(const KParams<R> &P, const double *x
                        v[1], v[2], v[3], x ? 1 : 0);
 }
 
-template <typename R> void launch_rollout(const KParams<R> &P, hipStream_t s) {
-    const int waves_per_block = 4, blocks = (P.K + waves_per_block - 1) / waves_per_block;
-    if (P.model == MODEL_DIFF) {
-        MPPI_NOTE_KERNEL("k_rollout<%s, 0>", type_name<R>());
-        hipLaunchKernelGGL((k_rollout<R, MODEL_DIFF>), dim3(blocks), dim3(64 * waves_per_block), 0, s, P.st, P);
-    } else {
-        MPPI_NOTE_KERNEL("k_rollout<%s, 1>", type_name<R>());
-        hipLaunchKernelGGL((k_rollout<R, MODEL_RACE>), dim3(blocks), dim3(64 * waves_per_block), 0, s, P.st, P);
-    }
-}
-
 bool fused_supported(int T) { return T <= 128; }
 // Two samples per wave pays once there are enough samples to keep >= 4 waves per SIMD with it (K >= 8192):
 // it issues ~45 % fewer instructions per sample but halves the number of waves, and at K = 4096 the
@@ -2702,27 +2693,27 @@ bool fused_supported(int T) { return T <= 128; }
 // 5.7 us against 5.0 us for one sample per wave).  MPPI_DUAL=0/1 overrides for experiments.
 // Several agents per launch (blockIdx.y) count together: what matters is the number of waves the LAUNCH brings (32 agents
 // of K = 4096: 6.7e10 -> 1.0e11 trajectory-steps/s with two samples per wave, 4 agents: 4.4e10 -> 5.6e10).
-static bool dual_layout(int K, int T, int n_agents) {
+static bool dual_layout(const Switches &sw, int K, int T, int n_agents) {
     if (T > 64) return false;
-    if (const char *e = getenv("MPPI_DUAL")) return atoi(e) != 0;
+    if (sw.dual >= 0) return sw.dual != 0;
     return (long long)K * n_agents >= 8192;
 }
 // 64 < T <= 128: one sample per wave, two steps per lane (k_rollout_dual<.., 1>) instead of two 64-step chunks
-static bool pair_layout(int T) {
+static bool pair_layout(const Switches &sw, int T) {
     if (T <= 64 || T > 128) return false;
-    if (const char *e = getenv("MPPI_PAIR")) return atoi(e) != 0;
+    if (sw.pair >= 0) return sw.pair != 0;
     return true;
 }
 // 64 < T <= 96, race car: two samples per wave, three steps per lane (k_rollout_tri).  MPPI_TRI=0 keeps the pair layout (A/B).
-static bool tri_layout(int T, bool tri_ok) {
+static bool tri_layout(const Switches &sw, int T, bool tri_ok) {
     if (!tri_ok || T <= 64 || T > 32 * TRI_STEPS) return false;
-    if (const char *e = getenv("MPPI_TRI")) return atoi(e) != 0;
+    if (sw.tri >= 0) return sw.tri != 0;
     return true;
 }
-int rollout_layout(int K, int T, int n_agents, int model, bool f64, bool per_rollout, bool tri_ok) {
-    if (!per_rollout && model == MODEL_RACE && !f64 && n_agents <= 1 && tri_layout(T, tri_ok)) return LAYOUT_TRI;
+int rollout_layout(const Switches &sw, int K, int T, int n_agents, int model, bool f64, bool per_rollout, bool tri_ok) {
+    if (!per_rollout && model == MODEL_RACE && !f64 && n_agents <= 1 && tri_layout(sw, T, tri_ok)) return LAYOUT_TRI;
     // (per-rollout index threading lives in the one-sample-per-wave kernels: Rollout::chunk)
-    const int kind = per_rollout ? LAYOUT_FUSED : dual_layout(K, T, n_agents) ? LAYOUT_DUAL : pair_layout(T) ? LAYOUT_PAIR : LAYOUT_FUSED;
+    const int kind = per_rollout ? LAYOUT_FUSED : dual_layout(sw, K, T, n_agents) ? LAYOUT_DUAL : pair_layout(sw, T) ? LAYOUT_PAIR : LAYOUT_FUSED;
     if (kind == LAYOUT_FUSED) return kind;
     // k_rollout_dual's SEQ: two samples per (half-)wave once one sample each would need more than one workgroup per
     // CU, and at most 512 records after halving (what k_finalize merges directly).  Beyond that the longer live
@@ -2733,7 +2724,7 @@ int rollout_layout(int K, int T, int n_agents, int model, bool f64, bool per_rol
     const int blocks = fused_blocks(K, T, kind);
     const bool shares_cu = kind == LAYOUT_DUAL && model == MODEL_DIFF && !f64;
     bool twice = blocks > (shares_cu ? 512 : 256) && blocks <= 1024;
-    if (const char *e = getenv("MPPI_SEQ")) twice = atoi(e) == 2;
+    if (sw.seq >= 0) twice = sw.seq == 2;
     return kind | (twice ? LAYOUT_TWICE : 0);
 }
 int fused_blocks(int K, int T, int layout) {
@@ -2745,130 +2736,97 @@ int fused_blocks(int K, int T, int layout) {
 
 // The streaming kernel serves: diff-drive, the two-samples-per-wave layout, frozen index, `S[k] =`, windows of <= 32 candidates.
 // Batches of 32 samples per workgroup: as many as leave about 1024 workgroups (two rounds of two per CU), at most 16.
-template <typename R> static int stream_passes(const KParams<R> &P) {
+static int stream_batches(int K) { return (K + DUAL_SAMPLES - 1) / DUAL_SAMPLES; }
+template <typename R> static int stream_passes(const KParams<R> &P, const Switches &sw) {
     if (P.model != MODEL_DIFF || P.sequential || P.accumulate || P.T > 64 || P.window > 32 ||
         (P.layout & LAYOUT_KIND) != LAYOUT_DUAL)
         return 0;
-    static const bool off = getenv("MPPI_NO_STREAM") != nullptr;  // (A/B runs)
-    if (off) return 0;
-    const long long batches = (long long)((P.K + DUAL_SAMPLES - 1) / DUAL_SAMPLES) * (P.n_agents > 1 ? P.n_agents : 1);
-    static const int forced = getenv("MPPI_STREAM_PASSES") ? atoi(getenv("MPPI_STREAM_PASSES")) : 0;  // (experiments)
-    if (forced > 0) return forced;
+    if (sw.no_stream) return 0;  // (A/B runs)
+    const long long batches = (long long)stream_batches(P.K) * (P.n_agents > 1 ? P.n_agents : 1);
+    if (sw.stream_passes > 0) return sw.stream_passes;  // (experiments)
     int np = (int)(batches / 1024);  // (measured, 32 agents of K = 4096: 2 / 4 / 8 / 16 batches -> 32.8 / 30.8 / 31.3 / 35.6 us)
     return np < 1 ? 1 : np > 16 ? 16 : np;
 }
-template <typename R> int fused_records(const KParams<R> &P) {
-    const int np = stream_passes(P);
-    if (np == 0) return fused_blocks(P.K, P.T, P.layout);
-    const int batches = (P.K + DUAL_SAMPLES - 1) / DUAL_SAMPLES;
-    return (batches + np - 1) / np;
+int fused_max_records(int K, int T, int layout) {  // (one pass per workgroup is the most the streaming kernel leaves)
+    const int blocks = fused_blocks(K, T, layout), batches = (layout & LAYOUT_KIND) == LAYOUT_DUAL ? stream_batches(K) : 0;
+    return blocks > batches ? blocks : batches;
 }
-template int fused_records<float>(const KParams<float> &);
-template int fused_records<double>(const KParams<double> &);
 
-template <typename R, int MODEL, bool MULTI> static void launch_fused_mm(const KParams<R> &P, R *partials, hipStream_t s) {
-    if (const int np = stream_passes(P)) {
-        const dim3 sgrid(fused_records(P), MULTI ? P.n_agents : 1);
-#define MPPI_LAUNCH_STREAM(OBS_, PHILOX_)                                                                              \
-    do {                                                                                                               \
-        MPPI_NOTE_KERNEL("k_rollout_stream<%s, %s, %s, %s>", type_name<R>(), tf(MULTI), tf(OBS_), tf(PHILOX_));        \
-        hipLaunchKernelGGL((k_rollout_stream<R, MULTI, OBS_, PHILOX_>), sgrid, dim3(64 * DUAL_WAVES), 0, s, P.st, P, partials, np); \
-    } while (0)
+// k_rollout_dual<R, MODEL, SPW, MULTI, ...>: the LB form resolves the sequential index in the launch (diff-drive, one agent,
+// two samples per wave, one pass); PLAIN: every single-agent form, and for batched agents the one the default layout takes
+// -- two samples per wave, one pass
+template <typename R, int MODEL, bool MULTI, int SPW> static RolloutPlan dual_plan(bool twice, bool plain, bool lb) {
+    if constexpr (!MULTI && MODEL == MODEL_DIFF && SPW == 2)
+        if (lb && !twice) return plain ? dual_entry<R, MODEL_DIFF, 2, false, 1, true, true>() : dual_entry<R, MODEL_DIFF, 2, false, 1, false, true>();
+    if constexpr (!MULTI)
+        if (plain) return twice ? dual_entry<R, MODEL, SPW, false, 2, true>() : dual_entry<R, MODEL, SPW, false, 1, true>();
+    if constexpr (MULTI && SPW == 2)
+        if (plain && !twice) return dual_entry<R, MODEL, 2, true, 1, true>();
+    return twice ? dual_entry<R, MODEL, SPW, MULTI, 2, false>() : dual_entry<R, MODEL, SPW, MULTI, 1, false>();
+}
+// k_rollout_fused<R, MODEL, NCH, MULTI, SPEC, HYPK>: SPEC 2 the plain form, 1 no obstacles, 0 everything
+template <typename R, int MODEL, int NCH, bool MULTI, bool HYPK> static RolloutPlan fused_plan(int spec) {
+    return spec == 2   ? fused_entry<R, MODEL, NCH, MULTI, 2, HYPK>()
+           : spec == 1 ? fused_entry<R, MODEL, NCH, MULTI, 1, HYPK>()
+                       : fused_entry<R, MODEL, NCH, MULTI, 0, HYPK>();
+}
+template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const KParams<R> &P, const Switches &sw) {
+    RolloutPlan p;
+    if (const int np = stream_passes(P, sw)) {
         const bool obs = P.obstacle_model != OBS_NONE;
-        if (P.use_philox) { if (obs) MPPI_LAUNCH_STREAM(true, true); else MPPI_LAUNCH_STREAM(false, true); }
-        else { if (obs) MPPI_LAUNCH_STREAM(true, false); else MPPI_LAUNCH_STREAM(false, false); }
-#undef MPPI_LAUNCH_STREAM
-        return;
+        p = P.use_philox ? (obs ? stream_entry<R, MULTI, true, true>() : stream_entry<R, MULTI, false, true>())
+                         : (obs ? stream_entry<R, MULTI, true, false>() : stream_entry<R, MULTI, false, false>());
+        p.passes = np;
+        p.records = (stream_batches(P.K) + np - 1) / np;
+        p.grid = dim3(p.records, MULTI ? P.n_agents : 1);
+        return p;
     }
-    const dim3 grid(fused_blocks(P.K, P.T, P.layout), MULTI ? P.n_agents : 1);
+    const int blocks = fused_blocks(P.K, P.T, P.layout);
     const bool twice = (P.layout & LAYOUT_TWICE) != 0;
     const bool race = MODEL == MODEL_RACE;
-    // (the PLAIN instantiations of k_rollout_dual: every single-agent form, and for batched agents the one the default
-    // layout takes -- two samples per wave, one pass)
     const bool plain_ok = P.use_philox && P.clamp_rollout && (bool)P.wrap_stage == race && (bool)P.wrap_term == race;
-    const bool plain_dual = !MULTI && plain_ok;
     switch (P.layout & LAYOUT_KIND) {
-#define MPPI_LAUNCH_DUAL(SPW_, SEQ_, PLAIN_)                                                                                  \
-    do {                                                                                                                      \
-        MPPI_NOTE_KERNEL("k_rollout_dual<%s, %d, %d, %s, %d, %s, false>", type_name<R>(), MODEL, SPW_, tf(MULTI), SEQ_, tf(PLAIN_)); \
-        hipLaunchKernelGGL((k_rollout_dual<R, MODEL, SPW_, MULTI, SEQ_, PLAIN_>), grid, dim3(64 * DUAL_WAVES), 0, s, P.st, P, \
-                           partials);                                                                                         \
-    } while (0)
-    case LAYOUT_DUAL:
-        if (P.hyp && !MULTI && MODEL == MODEL_DIFF && !twice) {  // the sequential index resolved in the launch (LB)
-            if constexpr (!MULTI && MODEL == MODEL_DIFF) {
-                if (plain_ok) {
-                    MPPI_NOTE_KERNEL("k_rollout_dual<%s, 0, 2, false, 1, true, true>", type_name<R>());
-                    hipLaunchKernelGGL((k_rollout_dual<R, MODEL_DIFF, 2, false, 1, true, true>), grid, dim3(64 * DUAL_WAVES), 0, s, P.st, P, partials);
-                } else {
-                    MPPI_NOTE_KERNEL("k_rollout_dual<%s, 0, 2, false, 1, false, true>", type_name<R>());
-                    hipLaunchKernelGGL((k_rollout_dual<R, MODEL_DIFF, 2, false, 1, false, true>), grid, dim3(64 * DUAL_WAVES), 0, s, P.st, P, partials);
-                }
-            }
-        } else if (plain_dual) { if (twice) MPPI_LAUNCH_DUAL(2, 2, !MULTI); else MPPI_LAUNCH_DUAL(2, 1, !MULTI); }
-        else if (MULTI && plain_ok && !twice) MPPI_LAUNCH_DUAL(2, 1, true);
-        else { if (twice) MPPI_LAUNCH_DUAL(2, 2, false); else MPPI_LAUNCH_DUAL(2, 1, false); }
-        break;
+    case LAYOUT_DUAL: p = dual_plan<R, MODEL, MULTI, 2>(twice, plain_ok, P.hyp != 0); break;
+    case LAYOUT_PAIR: p = dual_plan<R, MODEL, MULTI, 1>(twice, plain_ok, false); break;
     case LAYOUT_TRI:
         if constexpr (sizeof(R) == 4 && MODEL == MODEL_RACE && !MULTI) {
-#define MPPI_LAUNCH_TRI(PLAIN_, SHARE_)                                                                                   \
-    do {                                                                                                                  \
-        MPPI_NOTE_KERNEL("k_rollout_tri<%s, %s>", tf(PLAIN_), tf(SHARE_));                                                \
-        hipLaunchKernelGGL((k_rollout_tri<PLAIN_, SHARE_>), grid, dim3(64 * DUAL_WAVES), 0, s, P.st, P, partials);        \
-    } while (0)
-            const bool share = grid.x > 256;  // (more than one workgroup per CU)
-            if (plain_ok) { if (share) MPPI_LAUNCH_TRI(true, true); else MPPI_LAUNCH_TRI(true, false); }
-            else { if (share) MPPI_LAUNCH_TRI(false, true); else MPPI_LAUNCH_TRI(false, false); }
-#undef MPPI_LAUNCH_TRI
+            const bool share = blocks > 256;  // (more than one workgroup per CU)
+            p = plain_ok ? (share ? tri_entry<true, true>() : tri_entry<true, false>())
+                         : (share ? tri_entry<false, true>() : tri_entry<false, false>());
         }
         break;
-    case LAYOUT_PAIR:
-        if (plain_dual) { if (twice) MPPI_LAUNCH_DUAL(1, 2, !MULTI); else MPPI_LAUNCH_DUAL(1, 1, !MULTI); }
-        else { if (twice) MPPI_LAUNCH_DUAL(1, 2, false); else MPPI_LAUNCH_DUAL(1, 1, false); }
-        break;
-#undef MPPI_LAUNCH_DUAL
     default:
         {
             const bool plain = P.obstacle_model == OBS_NONE && P.use_philox && P.clamp_rollout && !P.wrap_stage && !P.wrap_term &&
                                !P.per_rollout;
             const int spec = plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
-            const dim3 block(64 * FUSED_WAVES);
-#define MPPI_LAUNCH_FUSED(NCH_, SPEC_)                                                                                  \
-    do {                                                                                                                \
-        MPPI_NOTE_KERNEL("k_rollout_fused<%s, %d, %d, %s, %d, false>", type_name<R>(), MODEL, NCH_, tf(MULTI), SPEC_);  \
-        hipLaunchKernelGGL((k_rollout_fused<R, MODEL, NCH_, MULTI, SPEC_>), grid, block, 0, s, P.st, P, partials);      \
-    } while (0)
-#define MPPI_LAUNCH_FUSED_HYP(SPEC_)                                                                                        \
-    do {                                                                                                                    \
-        MPPI_NOTE_KERNEL("k_rollout_fused<%s, 0, 1, false, %d, true>", type_name<R>(), SPEC_);                              \
-        hipLaunchKernelGGL((k_rollout_fused<R, MODEL_DIFF, 1, false, SPEC_, true>), grid, block, 0, s, P.st, P, partials);  \
-    } while (0)
-            if (P.hyp && P.T <= 64 && !MULTI && MODEL == MODEL_DIFF) {
-                if (spec == 2) MPPI_LAUNCH_FUSED_HYP(2);
-                else if (spec == 1) MPPI_LAUNCH_FUSED_HYP(1);
-                else MPPI_LAUNCH_FUSED_HYP(0);
-            } else if (P.T <= 64) {
-                if (spec == 2) MPPI_LAUNCH_FUSED(1, 2);
-                else if (spec == 1) MPPI_LAUNCH_FUSED(1, 1);
-                else MPPI_LAUNCH_FUSED(1, 0);
-            } else {
-                if (spec == 2) MPPI_LAUNCH_FUSED(2, 2);
-                else if (spec == 1) MPPI_LAUNCH_FUSED(2, 1);
-                else MPPI_LAUNCH_FUSED(2, 0);
-            }
-#undef MPPI_LAUNCH_FUSED
-#undef MPPI_LAUNCH_FUSED_HYP
+            // (HYPK: the sequential index resolved in the launch)
+            p = P.hyp && P.T <= 64 && !MULTI && MODEL == MODEL_DIFF ? fused_plan<R, MODEL_DIFF, 1, false, true>(spec)
+                : P.T <= 64                                         ? fused_plan<R, MODEL, 1, MULTI, false>(spec)
+                                                                    : fused_plan<R, MODEL, 2, MULTI, false>(spec);
         }
     }
-}
-template <typename R, int MODEL> static void launch_fused_m(const KParams<R> &P, R *partials, hipStream_t s) {
-    if (P.n_agents > 1) launch_fused_mm<R, MODEL, true>(P, partials, s);
-    else launch_fused_mm<R, MODEL, false>(P, partials, s);
+    p.records = blocks;
+    p.grid = dim3(blocks, MULTI ? P.n_agents : 1);
+    return p;
 }
 
-template <typename R> void launch_rollout_fused(const KParams<R> &P, void *partials, hipStream_t s) {
-    if (P.model == MODEL_DIFF) launch_fused_m<R, MODEL_DIFF>(P, (R *)partials, s);
-    else launch_fused_m<R, MODEL_RACE>(P, (R *)partials, s);
+template <typename R> RolloutPlan plan_rollout(const KParams<R> &P, bool fused, const Switches &sw) {
+    const bool diff = P.model == MODEL_DIFF;
+    if (fused) {
+        if (P.n_agents > 1) return diff ? plan_fused<R, MODEL_DIFF, true>(P, sw) : plan_fused<R, MODEL_RACE, true>(P, sw);
+        return diff ? plan_fused<R, MODEL_DIFF, false>(P, sw) : plan_fused<R, MODEL_RACE, false>(P, sw);
+    }
+    RolloutPlan p = diff ? rollout_entry<R, MODEL_DIFF>() : rollout_entry<R, MODEL_RACE>();
+    p.grid = dim3((P.K + 3) / 4);  // four waves per workgroup, a sample each
+    p.records = reduce_blocks(P.K, P.traj_per_block);
+    return p;
+}
+template <typename R> void launch_rollout(const RolloutPlan &plan, const KParams<R> &P, void *partials, hipStream_t s) {
+    const DevState *st = P.st;
+    int n_pass = plan.passes;
+    void *args[] = {&st, const_cast<KParams<R> *>(&P), &partials, &n_pass};  // (k_rollout: the first two; n_pass: k_rollout_stream)
+    launch_plan(plan, args, s);
 }
 
 template <typename R> void launch_reduce(const KParams<R> &P, void *partials, int n_blocks, hipStream_t s) {
@@ -2979,9 +2937,9 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
 
 #define INSTANTIATE(R)                                                                                    \
     template void launch_set_state<R>(const KParams<R> &, const double *, hipStream_t);                   \
-    template void launch_rollout<R>(const KParams<R> &, hipStream_t);                                     \
+    template RolloutPlan plan_rollout<R>(const KParams<R> &, bool, const Switches &);                     \
+    template void launch_rollout<R>(const RolloutPlan &, const KParams<R> &, void *, hipStream_t);        \
     template void launch_reduce<R>(const KParams<R> &, void *, int, hipStream_t);                         \
-    template void launch_rollout_fused<R>(const KParams<R> &, void *, hipStream_t);                       \
     template void launch_merge<R>(const void *, const void *, int, int, int, double, void *, void *, bool, hipStream_t);        \
     template void launch_finalize<R>(const FinalizeParams &, bool, hipStream_t);                          \
     template void launch_weights<R>(const KParams<R> &, double, double, double *, hipStream_t);           \

@@ -16,7 +16,6 @@
 // groups).  Per k-group: 2 LDS reads + 4 global loads feed 32 MFMAs (2048 cycles), so the loop is
 // MFMA-bound; the next group's operands are loaded before the current group's MFMAs issue.
 // 1 581 056 flop per trajectory-step.
-#include <stdlib.h>
 #include <string.h>
 
 #include "mppi_device.h"
@@ -359,7 +358,7 @@ __global__ __launch_bounds__(64 * MLP_WAVES, 1) void k_rollout_mlp(const KParams
 // ------------------------------------------------------------------------------------------
 using half8 = __attribute__((ext_vector_type(8))) _Float16;
 constexpr int H3_PITCH = 520, H3_ZPITCH = 24, H3_STEPS = MLP_H / 16;
-constexpr int H3_FORM_DEFAULT = 1;  // (H3_FORM_8x64, see h3_form)
+constexpr int H3_FORM_DEFAULT = 1;  // (H3_FORM_8x64, see the forms below)
 
 __device__ __forceinline__ void split_h3(float v, _Float16 &hi, _Float16 &lo) {
     hi = (_Float16)v;
@@ -772,23 +771,10 @@ extern "C" int mppi_debug_mlp_phases(unsigned long long *out) {
 // SIMD, both on one 64-sample tile per workgroup.  (Tried and dropped: 32-sample tiles with two workgroups per CU, so that one
 // workgroup's epilogues run under the other's GEMMs -- every weight byte then feeds half as many MFMAs, the weight stream
 // from L2 doubles to ~85 B per clock and CU, and the launch went from 6.3 to 8.7 ms.)
+// mppi_set_mlp captures the switch (Switches::mlp.form, these values; -1: H3_FORM_DEFAULT) together with MPPI_MLP_TERMS=2 --
+// the split product without the a_lo b_hi term (see h3_mma) -- and MPPI_MLP_F32: a process compares forms with one
+// handle, or one mppi_set_mlp call, per setting.
 enum { H3_FORM_4x64 = 0, H3_FORM_8x64 = 1 };
-static int h3_form() {
-    static const int f = [] {
-        const char *e = getenv("MPPI_MLP_FORM");
-        if (e && !strcmp(e, "4x64")) return (int)H3_FORM_4x64;
-        if (e && !strcmp(e, "8x64")) return (int)H3_FORM_8x64;
-        return (int)H3_FORM_DEFAULT;
-    }();
-    return f;
-}
-// MPPI_MLP_TERMS=2: the split product without the a_lo b_hi term (see h3_mma); read at every launch, so a process can compare
-static int h3_terms() {
-    const char *e = getenv("MPPI_MLP_TERMS");
-    return e && atoi(e) == 2 ? 2 : 3;
-}
-// samples per workgroup (= per softmin record) of the rollout kernel that serves Q (every one of them: 64)
-int mlp_tile(const MlpParams &) { return MLP_M; }
 int mlp_blocks(int K, int tile) { return (K + tile - 1) / tile; }
 
 static size_t h3_shmem(int nw, int rt, int h = MLP_H) {
@@ -802,112 +788,80 @@ static_assert(2 * (sizeof(_Float16) * 2 * (64 * (256 + 8) + 64 * H3_ZPITCH) + si
                   <= 160 * 1024, "two H = 256 workgroups per CU");
 static bool mlp_is_w(const MlpParams &Q) { return !mlp_shape_is_h3(Q.hidden, Q.n_hidden); }
 
-template <int H>
-static void launch_w(const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz &v, bool viz, dim3 grid, hipStream_t s) {
-    if (viz) hipLaunchKernelGGL((k_rollout_mlp_w<H, true>), grid, dim3(H), w_shmem(H), s, P, Q, (float *)partials, v);
-    else if (grid.y > 1) hipLaunchKernelGGL((k_rollout_mlp_w_agents<H>), grid, dim3(H), w_shmem(H), s, P, Q, (float *)partials);
-    else hipLaunchKernelGGL((k_rollout_mlp_w<H, false>), grid, dim3(H), w_shmem(H), s, P, Q, (float *)partials, v);
-}
-static void launch_w_any(const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz &v, bool viz, dim3 grid, hipStream_t s) {
-    switch (Q.hidden) {  // (mppi_set_mlp admits only these)
-    case 64: launch_w<64>(P, Q, partials, v, viz, grid, s); break;
-    case 128: launch_w<128>(P, Q, partials, v, viz, grid, s); break;
-    case 256: launch_w<256>(P, Q, partials, v, viz, grid, s); break;
-    case 512: launch_w<512>(P, Q, partials, v, viz, grid, s); break;
-    }
-}
-
-static void launch_mlp_any(const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz *viz, hipStream_t s) {
+// Plan entries: the one place per kernel where template arguments turn into the function to launch, its name as rocprofv3
+// prints it, its workgroup and its dynamic LDS (beyond 64 KB: launch_plan raises the attribute before the first launch on
+// a device).
+static RolloutPlan f32_entry() {
+    static KernelEntry e("k_rollout_mlp(");  // (up to the parenthesis: the other kernels' names begin with this one's)
     const size_t ref_lds = sizeof(float) * 4 * MLP_REF_LDS_MAX;  // the path (mlp_stage_path)
-    const size_t shmem_f32 = sizeof(float) * (MLP_M * MLP_PITCH + MLP_M * 8 + MLP_WAVES * MLP_M * 4) + ref_lds;
-    // (the attribute belongs to the device's copy of the code object: one process may drive several GPUs)
-    static bool attr_set[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)shmem_f32);
-#define H3_ATTR(VIZ_, NW_, RT_)                                                                                          \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_h3<VIZ_, NW_, RT_>),                          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3_shmem(NW_, RT_))
-        H3_ATTR(false, 4, 2); H3_ATTR(true, 4, 2); H3_ATTR(false, 8, 2); H3_ATTR(true, 8, 2);
-#undef H3_ATTR
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_h3<false, 8, 2, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3_shmem(8, 2));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_h3_agents<8, 2, 3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)h3_shmem(8, 2));
-#define W_ATTR(H_)                                                                                                       \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_w<H_, false>),                               \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_shmem(H_));                             \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_w<H_, true>),                                \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_shmem(H_));                             \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rollout_mlp_w_agents<H_>),                                \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_shmem(H_))
-        W_ATTR(64); W_ATTR(128); W_ATTR(256); W_ATTR(512);
-#undef W_ATTR
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
-    const MlpViz none{nullptr, nullptr, nullptr, nullptr, 0u, 0, nullptr, nullptr, nullptr, 0};
-    const int form = h3_form();
-    if (viz) {  // the samples' workgroups (when their trajectories are wanted) and one for the nominal sequence (likewise);
-                // always 64-sample tiles
-        const dim3 grid(viz->ex ? mlp_blocks(viz->en, MLP_M) : (viz->smp ? mlp_blocks(P.K, MLP_M) : 0) + (viz->opt ? 1 : 0));
-        if (mlp_is_w(Q)) launch_w_any(P, Q, partials, *viz, true, grid, s);
-        else if (form == H3_FORM_8x64) hipLaunchKernelGGL((k_rollout_mlp_h3<true, 8, 2>), grid, dim3(512), h3_shmem(8, 2), s, P, Q, (float *)partials, *viz);
-        else hipLaunchKernelGGL((k_rollout_mlp_h3<true, 4, 2>), grid, dim3(256), h3_shmem(4, 2), s, P, Q, (float *)partials, *viz);
-    } else if (mlp_is_w(Q)) {  // (MPPI_MLP_FORM / MPPI_MLP_TERMS / MPPI_MLP_F32 concern the 512 x 3 and 512 x 2 shapes only)
-        launch_w_any(P, Q, partials, none, false, dim3(mlp_blocks(P.K, mlp_tile(Q)), P.n_agents > 1 ? P.n_agents : 1), s);
-    } else if (P.n_agents > 1) {  // several agents: the default form always (mppi_set_mlp refuses the f32-input kernel)
-        const dim3 grid(mlp_blocks(P.K, mlp_tile(Q)), P.n_agents);
-        hipLaunchKernelGGL((k_rollout_mlp_h3_agents<8, 2, 3>), grid, dim3(512), h3_shmem(8, 2), s, P, Q, (float *)partials);
-    } else if (Q.use_h3) {
-        const dim3 grid(mlp_blocks(P.K, mlp_tile(Q)));
-        if (form == H3_FORM_8x64 && h3_terms() == 2)
-            hipLaunchKernelGGL((k_rollout_mlp_h3<false, 8, 2, 2>), grid, dim3(512), h3_shmem(8, 2), s, P, Q, (float *)partials, none);
-        else if (form == H3_FORM_8x64) hipLaunchKernelGGL((k_rollout_mlp_h3<false, 8, 2>), grid, dim3(512), h3_shmem(8, 2), s, P, Q, (float *)partials, none);
-        else hipLaunchKernelGGL((k_rollout_mlp_h3<false, 4, 2>), grid, dim3(256), h3_shmem(4, 2), s, P, Q, (float *)partials, none);
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp), e, 64 * MLP_WAVES,
+                      sizeof(float) * (MLP_M * MLP_PITCH + MLP_M * 8 + MLP_WAVES * MLP_M * 4) + ref_lds);
+}
+template <bool VIZ, int NW, int RT, int TERMS = 3> static RolloutPlan h3_entry() {
+    static KernelEntry e("k_rollout_mlp_h3<%s, %d, %d, %d>", KernelEntry::of(VIZ), NW, RT, TERMS);
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_h3<VIZ, NW, RT, TERMS>), e, 64 * NW, h3_shmem(NW, RT));
+}
+template <int NW, int RT, int TERMS> static RolloutPlan h3_agents_entry() {
+    static KernelEntry e("k_rollout_mlp_h3_agents<%d, %d, %d>", NW, RT, TERMS);
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_h3_agents<NW, RT, TERMS>), e, 64 * NW, h3_shmem(NW, RT));
+}
+template <int H, bool VIZ> static RolloutPlan w_entry() {
+    static KernelEntry e("k_rollout_mlp_w<%d, %s>", H, KernelEntry::of(VIZ));
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w<H, VIZ>), e, H, w_shmem(H));
+}
+template <int H> static RolloutPlan w_agents_entry() {
+    static KernelEntry e("k_rollout_mlp_w_agents<%d>", H);
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w_agents<H>), e, H, w_shmem(H));
+}
+template <int H> static RolloutPlan w_plan(bool viz, bool agents) {
+    return viz ? w_entry<H, true>() : agents ? w_agents_entry<H>() : w_entry<H, false>();
+}
+
+RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const MlpViz *viz) {
+    const int form = sw.mlp.form < 0 ? H3_FORM_DEFAULT : sw.mlp.form;
+    const int agents = !viz && P.n_agents > 1 ? P.n_agents : 1;
+    RolloutPlan p;
+    if (mlp_is_w(Q)) {  // (MPPI_MLP_FORM / MPPI_MLP_TERMS / MPPI_MLP_F32 concern the 512 x 3 and 512 x 2 shapes only)
+        switch (Q.hidden) {  // (mppi_set_mlp admits only these)
+        case 64: p = w_plan<64>(viz, agents > 1); break;
+        case 128: p = w_plan<128>(viz, agents > 1); break;
+        case 256: p = w_plan<256>(viz, agents > 1); break;
+        case 512: p = w_plan<512>(viz, agents > 1); break;
+        }
+    } else if (viz) {  // (the f16-split kernel, whichever rollout kernel MPPI_MLP_F32 selects: both weight sets are packed)
+        p = form == H3_FORM_8x64 ? h3_entry<true, 8, 2>() : h3_entry<true, 4, 2>();
+    } else if (agents > 1) {  // several agents: the default form always (mppi_set_mlp refuses the f32-input kernel)
+        p = h3_agents_entry<8, 2, 3>();
+    } else if (!Q.use_h3) {
+        p = f32_entry();
+    } else if (form == H3_FORM_8x64) {
+        p = sw.mlp.terms == 2 ? h3_entry<false, 8, 2, 2>() : h3_entry<false, 8, 2>();
     } else {
-        hipLaunchKernelGGL(k_rollout_mlp, dim3(mlp_blocks(P.K, MLP_M)), dim3(64 * MLP_WAVES), shmem_f32, s, P, Q, (float *)partials);
+        p = h3_entry<false, 4, 2>();
     }
+    p.records = mlp_blocks(P.K, MLP_M);  // every kernel: one 64-sample tile, one softmin record, per workgroup
+    // viz: the samples' workgroups (when their trajectories are wanted) and one for the nominal sequence (likewise)
+    if (viz) p.grid = dim3(viz->ex ? mlp_blocks(viz->en, MLP_M) : (viz->smp ? p.records : 0) + (viz->opt ? 1 : 0));
+    else p.grid = dim3(p.records, agents);
+    return p;
+}
+void launch_mlp(const RolloutPlan &plan, const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz *viz, hipStream_t s) {
+    const MlpViz none{};
+    void *args[] = {const_cast<KParams<float> *>(&P), const_cast<MlpParams *>(&Q), &partials, const_cast<MlpViz *>(viz ? viz : &none)};
+    launch_plan(plan, args, s);  // (k_rollout_mlp and the _agents kernels take no MlpViz)
 }
 
-const char *mlp_kernel_name(const MlpParams &Q, int n_agents) {
-    if (n_agents > 1) {
-        if (!mlp_is_w(Q)) return "k_rollout_mlp_h3_agents<8, 2, 3>";
-        switch (Q.hidden) {
-        case 64: return "k_rollout_mlp_w_agents<64>";
-        case 128: return "k_rollout_mlp_w_agents<128>";
-        case 256: return "k_rollout_mlp_w_agents<256>";
-        default: return "k_rollout_mlp_w_agents<512>";
-        }
-    }
-    if (mlp_is_w(Q))
-        switch (Q.hidden) {
-        case 64: return "k_rollout_mlp_w<64, false>";
-        case 128: return "k_rollout_mlp_w<128, false>";
-        case 256: return "k_rollout_mlp_w<256, false>";
-        default: return "k_rollout_mlp_w<512, false>";
-        }
-    if (!Q.use_h3) return "k_rollout_mlp(";
-    const int form = h3_form();
-    if (form == H3_FORM_8x64 && h3_terms() == 2) return "k_rollout_mlp_h3<false, 8, 2, 2>";
-    return form == H3_FORM_8x64 ? "k_rollout_mlp_h3<false, 8, 2, 3>" : "k_rollout_mlp_h3<false, 4, 2, 3>";
-}
-void launch_rollout_mlp(const KParams<float> &P, const MlpParams &Q, void *partials, hipStream_t s) {
-    launch_mlp_any(P, Q, partials, nullptr, s);
-}
-
-// (the f16-split kernel serves the visualisation whichever rollout kernel MPPI_MLP_F32 selects: both weight sets are packed)
-void launch_viz_mlp(const KParams<float> &P, const MlpParams &Q, const float *u_before, const float *u_upd, long long iter,
-                    float *opt, float *smp, hipStream_t s) {
+void launch_viz_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const float *u_before, const float *u_upd,
+                    long long iter, float *opt, float *smp, hipStream_t s) {
     if (!opt && !smp) return;
     const MlpViz v{u_before, u_upd, opt, smp, (unsigned)iter, smp ? 0 : mlp_blocks(P.K, MLP_M), nullptr, nullptr, nullptr, 0};
-    launch_mlp_any(P, Q, nullptr, &v, s);
+    launch_mlp(plan_mlp(P, Q, sw, &v), P, Q, nullptr, &v, s);
 }
 
-void launch_eval_mlp(const KParams<float> &P, const MlpParams &Q, const float *x, const float *v, int n, float *out, hipStream_t s) {
+void launch_eval_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const float *x, const float *v, int n,
+                     float *out, hipStream_t s) {
     const MlpViz e{nullptr, nullptr, nullptr, nullptr, 0u, 0, x, v, out, n};
-    launch_mlp_any(P, Q, nullptr, &e, s);
+    launch_mlp(plan_mlp(P, Q, sw, &e), P, Q, nullptr, &e, s);
 }
 
 // Host-side packing of a torch Linear weight [n_out][n_in] (n_out a multiple of 32) into fragment order:
