@@ -95,10 +95,10 @@ struct mppi_handle {
     DevState *d_st = nullptr;
     StepResult *d_res = nullptr, *h_res = nullptr;
     size_t res_bytes = 0;
-    const float *last_eps = nullptr;
+    const float *last_eps = nullptr;    // the tensor the last iteration drew its noise from (null: the in-kernel sampler)
     const float *noise_ring = nullptr;  // mppi_set_noise_ring: [noise_slots][n_agents][K][T][2] device floats (caller's)
     int noise_slots = 0;
-    bool last_philox = true, begun = false, timing = false, dev_loop_primed = false, slot_timed = false;
+    bool begun = false, timing = false, dev_loop_primed = false, slot_timed = false;
     long long iter = 0;
     int idx = 0, rollout_repeats = 1;
     std::vector<hipEvent_t> ev;  // pairs around the rollout / reduce / finalize kernels
@@ -154,7 +154,11 @@ extern "C" int mppi_device_count(void) {
     return n;
 }
 
-static size_t rsz(const mppi_handle *h) { return h->f64 ? sizeof(double) : sizeof(float); }
+// The one precision dispatch: f is called with float{} or double{}, the handle's real type (`using R = decltype(r)`).  Every
+// entry point that launches goes through it once per ABI call; below it everything is a template on R.
+template <typename Fn> static auto with_real(const mppi_handle *h, Fn &&f) { return h->f64 ? f(double{}) : f(float{}); }
+
+static size_t rsz(const mppi_handle *h) { return with_real(h, [](auto r) { return sizeof(r); }); }
 
 // ABI model -> the kernels' model (the learned model rolls the diff-drive state)
 static int kernel_model(const mppi_config &c) { return c.model == MPPI_MODEL_RACECAR ? MODEL_RACE : MODEL_DIFF; }
@@ -172,25 +176,22 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
 
 // host double[] -> device array in the kernel precision
 static int upload_real(mppi_handle *h, void *dst, const double *src, size_t n) {
-    if (h->f64) {
-        HIPCHECK(h, hipMemcpy(dst, src, n * sizeof(double), hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> tmp(n);
-        for (size_t i = 0; i < n; ++i) tmp[i] = (float)src[i];
-        HIPCHECK(h, hipMemcpy(dst, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    }
-    return MPPI_OK;
+    return with_real(h, [&](auto r) -> int {
+        using R = decltype(r);
+        const std::vector<R> tmp(src, src + n);
+        HIPCHECK(h, hipMemcpy(dst, tmp.data(), n * sizeof(R), hipMemcpyHostToDevice));
+        return MPPI_OK;
+    });
 }
 
 static int download_real(mppi_handle *h, double *dst, const void *src, size_t n) {
-    if (h->f64) {
-        HIPCHECK(h, hipMemcpy(dst, src, n * sizeof(double), hipMemcpyDeviceToHost));
-    } else {
-        std::vector<float> tmp(n);
-        HIPCHECK(h, hipMemcpy(tmp.data(), src, n * sizeof(float), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i) dst[i] = (double)tmp[i];
-    }
-    return MPPI_OK;
+    return with_real(h, [&](auto r) -> int {
+        using R = decltype(r);
+        std::vector<R> tmp(n);
+        HIPCHECK(h, hipMemcpy(tmp.data(), src, n * sizeof(R), hipMemcpyDeviceToHost));
+        std::copy(tmp.begin(), tmp.end(), dst);
+        return MPPI_OK;
+    });
 }
 
 extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
@@ -296,28 +297,31 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         mppi_destroy(h);
         return (int)MPPI_ERR_HIP;
     };
+    // a device buffer, allocated and zero-filled; a failure names the call that failed
+    const auto zeroed = [&](void **p, size_t bytes, const char *malloc_call) -> int {
+        hipError_t e;
+        if ((e = hipMalloc(p, bytes)) != hipSuccess) return fail(e, malloc_call);
+        if ((e = hipMemset(*p, 0, bytes)) != hipSuccess) return fail(e, "hipMemset");
+        return MPPI_OK;
+    };
     hipError_t e;
     if ((e = hipSetDevice(c.device)) != hipSuccess) return fail(e, "hipSetDevice");
     const size_t r = rsz(h), B = (size_t)c.n_agents;
     h->B = c.n_agents;
-    if ((e = hipMalloc(&h->d_u, B * r * 2 * c.T)) != hipSuccess) return fail(e, "hipMalloc(u)");
-    if ((e = hipMalloc(&h->d_uhist, B * r * 4 * c.T)) != hipSuccess) return fail(e, "hipMalloc(u history)");
-    if ((e = hipMalloc(&h->d_S, B * r * c.K)) != hipSuccess) return fail(e, "hipMalloc(S)");
-    if ((e = hipMalloc((void **)&h->d_pout, B * sizeof(int) * c.K)) != hipSuccess) return fail(e, "hipMalloc(pout)");
+    if (int rc = zeroed(&h->d_u, B * r * 2 * c.T, "hipMalloc(u)")) return rc;  // u_prev = 0 (:82)
+    if (int rc = zeroed(&h->d_uhist, B * r * 4 * c.T, "hipMalloc(u history)")) return rc;
+    if (int rc = zeroed(&h->d_S, B * r * c.K, "hipMalloc(S)")) return rc;
+    if (int rc = zeroed((void **)&h->d_pout, B * sizeof(int) * c.K, "hipMalloc(pout)")) return rc;
     const size_t rec_bytes = sizeof(double) * (size_t)record_len(c.T, 8);  // enough for either precision
     // zero-filled and padded by 256 records: the merge kernels read 256 slots unconditionally
     // (a launch may leave more records than the handle's own count -- fused_max_records: room for the larger of the two)
     const size_t n_rec_max = (size_t)std::max(h->n_part, fused_max_records(c.K, c.T, h->layout));
     const size_t slots = n_rec_max + 256, n1 = B * slots, n2 = n_rec_max / 64 + 2 + 256;
     h->slots = (int)slots;
-    if ((e = hipMalloc(&h->d_partials, rec_bytes * n1)) != hipSuccess) return fail(e, "hipMalloc(partials)");
-    if ((e = hipMalloc(&h->d_partials2, rec_bytes * n2)) != hipSuccess) return fail(e, "hipMalloc(partials2)");
-    if ((e = hipMemset(h->d_partials, 0, rec_bytes * n1)) != hipSuccess) return fail(e, "hipMemset");
-    if ((e = hipMemset(h->d_partials2, 0, rec_bytes * n2)) != hipSuccess) return fail(e, "hipMemset");
-    if ((e = hipMalloc(&h->d_heads, 32 * n1)) != hipSuccess) return fail(e, "hipMalloc(heads)");
-    if ((e = hipMalloc(&h->d_heads2, 32 * n2)) != hipSuccess) return fail(e, "hipMalloc(heads2)");
-    if ((e = hipMemset(h->d_heads, 0, 32 * n1)) != hipSuccess) return fail(e, "hipMemset");
-    if ((e = hipMemset(h->d_heads2, 0, 32 * n2)) != hipSuccess) return fail(e, "hipMemset");
+    if (int rc = zeroed(&h->d_partials, rec_bytes * n1, "hipMalloc(partials)")) return rc;
+    if (int rc = zeroed(&h->d_partials2, rec_bytes * n2, "hipMalloc(partials2)")) return rc;
+    if (int rc = zeroed(&h->d_heads, 32 * n1, "hipMalloc(heads)")) return rc;
+    if (int rc = zeroed(&h->d_heads2, 32 * n2, "hipMalloc(heads2)")) return rc;
     // The sequential index in one launch (look-back, LB_CAND in mppi_kernels.h): horizons of one 64-step pass in the
     // one-sample-per-wave layout or the two-samples-per-wave layout with one pass per workgroup, the reference's 20- / 10-
     // candidate windows, `S[k] =`, one agent, at most 512 workgroups (K <= 16384: configs 2 and 3).  Anything else keeps the
@@ -326,23 +330,15 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     h->hyp = h->fused && lb_layout && c.T <= 64 && c.model == MPPI_MODEL_DIFFDRIVE &&
              c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL && !c.accumulate_stage_cost && (c.search_window == HYP_WINDOW || c.search_window == HYP_WINDOW_CUDA) &&
              c.n_agents == 1 && h->n_part <= HYP_MAX_BLOCKS && !sw.no_hyp;
-    if (h->hyp) {
-        const size_t lb_bytes = sizeof(unsigned) * (size_t)LB_COPIES * LB_COPY_STRIDE;
-        if ((e = hipMalloc((void **)&h->d_hyp_slots, lb_bytes)) != hipSuccess) return fail(e, "hipMalloc(look-back words)");
-        if ((e = hipMemset(h->d_hyp_slots, 0, lb_bytes)) != hipSuccess) return fail(e, "hipMemset");
-    }
+    if (h->hyp)
+        if (int rc = zeroed((void **)&h->d_hyp_slots, sizeof(unsigned) * (size_t)LB_COPIES * LB_COPY_STRIDE, "hipMalloc(look-back words)")) return rc;
     h->res_bytes = (h->res_bytes + 15) & ~(size_t)15;  // (the agents' results are stored back to back)
-    if ((e = hipMalloc((void **)&h->d_st, B * sizeof(DevState))) != hipSuccess) return fail(e, "hipMalloc(state)");
-    if ((e = hipMalloc((void **)&h->d_res, B * h->res_bytes)) != hipSuccess) return fail(e, "hipMalloc(result)");
-    if ((e = hipMemset(h->d_res, 0, B * h->res_bytes)) != hipSuccess) return fail(e, "hipMemset");
+    if ((e = hipMalloc((void **)&h->d_st, B * sizeof(DevState))) != hipSuccess) return fail(e, "hipMalloc(state)");  // (filled below)
+    if (int rc = zeroed((void **)&h->d_res, B * h->res_bytes, "hipMalloc(result)")) return rc;
     if ((e = hipHostMalloc((void **)&h->h_res, B * h->res_bytes, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
         return fail(e, "hipHostMalloc(result)");
     if ((e = hipHostGetDevicePointer((void **)&h->res_mapped, h->h_res, 0)) != hipSuccess)
         return fail(e, "hipHostGetDevicePointer(result)");
-    if ((e = hipMemset(h->d_u, 0, B * r * 2 * c.T)) != hipSuccess) return fail(e, "hipMemset");    // u_prev = 0 (:82)
-    if ((e = hipMemset(h->d_uhist, 0, B * r * 4 * c.T)) != hipSuccess) return fail(e, "hipMemset");
-    if ((e = hipMemset(h->d_S, 0, B * r * c.K)) != hipSuccess) return fail(e, "hipMemset");
-    if ((e = hipMemset(h->d_pout, 0, B * sizeof(int) * c.K)) != hipSuccess) return fail(e, "hipMemset");
     DevState st0;
     memset(&st0, 0, sizeof(st0));  // prev_way_point_idx = 0 (:85)
     st0.first_k = NO_TRIGGER;
@@ -940,6 +936,15 @@ static int host_x0_call(const mppi_handle *h, const double *x0) {
     return p + best_j;
 }
 
+// The result path, first half: `bytes` of the device-side result (one agent's, or every agent's of a batched handle) copied
+// into h_res behind the launches on s, and the stream synchronised.
+static int fetch_result(mppi_handle *h, size_t bytes, hipStream_t s, bool check_launches = true) {
+    HIPCHECK(h, hipMemcpyAsync(h->h_res, h->d_res, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    if (check_launches) HIPCHECK(h, hipGetLastError());
+    return MPPI_OK;
+}
+
 // wait for the result of the launches just enqueued: poll the completion word the finalize kernel writes into
 // mapped host memory (saves the device-to-host copy launch and the stream synchronisation), or copy + synchronise
 static int wait_result(mppi_handle *h, long long seq, hipStream_t s) {
@@ -964,9 +969,38 @@ static int wait_result(mppi_handle *h, long long seq, hipStream_t s) {
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
         return MPPI_OK;
     }
-    HIPCHECK(h, hipMemcpyAsync(h->h_res, h->d_res, h->res_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    HIPCHECK(h, hipGetLastError());
+    return fetch_result(h, h->res_bytes, s);
+}
+
+// What the iteration just enqueued drew its noise from (mppi_rollout_viz replays it).  observed_state: the iteration took its
+// state from the caller, so the next closed-loop call has to make its own x0 call.
+static void note_noise(mppi_handle *h, const float *eps, bool observed_state) {
+    h->last_eps = eps;
+    if (observed_state) h->dev_loop_primed = false;
+}
+
+// The result path, second half: the finished result in h_res becomes the handle's state and the caller's outputs -- waypoint
+// index, stats, the kernel's status as an error code, then the iteration counter and the controls.  An iteration refused at
+// the end of the path has moved the index but is not counted.  Every entry point that ends an iteration on the host calls
+// this; what the entry points do differently (kept as it was) comes in through `keep`.
+enum : unsigned {
+    KEEP_IDX_VALID = 1u,  // leave idx_valid as it is (otherwise: the index is the host's again)
+    KEEP_GOING = 2u,      // ignore the kernel's status
+};
+static int adopt_result(mppi_handle *h, unsigned keep, double *u_out, double *u0_out, mppi_stats *stats) {
+    const StepResult *res = h->h_res;
+    h->idx = res->idx_after;
+    if (!(keep & KEEP_IDX_VALID)) h->idx_valid = true;
+    fill_stats(h, stats);
+    if (!(keep & KEEP_GOING)) {
+        // (only a finalize launch that carries the peer-to-peer exchange writes this status: k_finalize, MODE 2)
+        if (res->status == STATUS_EXCHANGE_FAILED)
+            FAIL(h, MPPI_ERR_COMM, "peer-to-peer exchange: a rank did not arrive within the timeout");
+        if (res->status == STATUS_PATH_END) FAIL(h, MPPI_ERR_PATH_END, "[ERROR] Reached the end of the reference path.");
+    }
+    h->iter = res->iter;
+    if (u_out) memcpy(u_out, reinterpret_cast<const double *>(h->h_res + 1), sizeof(double) * 2 * h->cfg.T);  // u[T][2] follows the header
+    if (u0_out) { u0_out[0] = res->u0[0]; u0_out[1] = res->u0[1]; }
     return MPPI_OK;
 }
 
@@ -1009,22 +1043,9 @@ static int step_impl(mppi_handle *h, const double *x0, const double *x0_dev, con
         if (round > h->cfg.K + 1) FAIL(h, MPPI_ERR_STATE, "waypoint speculation did not converge");
         P.use_args = 0;  // repair rounds take the state the finalize kernel left in *st
     }
-    h->dev_loop_primed = false;
-    h->last_eps = eps;
-    h->last_philox = eps == nullptr;
-    h->idx = h->h_res->idx_after;
-    h->idx_valid = true;
+    note_noise(h, eps, true);
     h->last_iter_us = 1e6 * (now_s() - t_call);
-    fill_stats(h, stats);
-    if (h->h_res->status == STATUS_EXCHANGE_FAILED)
-        FAIL(h, MPPI_ERR_COMM, "peer-to-peer exchange: a rank did not arrive within the timeout");
-    if (h->h_res->status == STATUS_PATH_END)
-        FAIL(h, MPPI_ERR_PATH_END, "[ERROR] Reached the end of the reference path.");
-    h->iter = h->h_res->iter;
-    const double *ru = reinterpret_cast<const double *>(h->h_res + 1);
-    if (u_out) memcpy(u_out, ru, sizeof(double) * 2 * h->cfg.T);
-    if (u0_out) { u0_out[0] = h->h_res->u0[0]; u0_out[1] = h->h_res->u0[1]; }
-    return MPPI_OK;
+    return adopt_result(h, 0, u_out, u0_out, stats);
 }
 
 extern "C" int mppi_step(mppi_handle *h, const double *x0, const float *eps, double *u_out, double *u0_out,
@@ -1036,8 +1057,7 @@ extern "C" int mppi_step(mppi_handle *h, const double *x0, const float *eps, dou
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     double x[4] = {0, 0, 0, 0};
     for (int i = 0; i < h->nx; ++i) x[i] = x0[i];
-    return h->f64 ? step_impl<double>(h, x, nullptr, eps, u_out, u0_out, stats, (hipStream_t)stream)
-                  : step_impl<float>(h, x, nullptr, eps, u_out, u0_out, stats, (hipStream_t)stream);
+    return with_real(h, [&](auto r) { return step_impl<decltype(r)>(h, x, nullptr, eps, u_out, u0_out, stats, (hipStream_t)stream); });
 }
 
 extern "C" int mppi_step_device_x0(mppi_handle *h, const double *x0_device, const float *eps, double *u_out, double *u0_out,
@@ -1047,8 +1067,7 @@ extern "C" int mppi_step_device_x0(mppi_handle *h, const double *x0_device, cons
     SINGLE_AGENT_ONLY(h, "mppi_step_device_x0");
     if (!x0_device) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_step_device_x0: x0 is null");
     HIPCHECK(h, hipSetDevice(h->cfg.device));
-    return h->f64 ? step_impl<double>(h, nullptr, x0_device, eps, u_out, u0_out, stats, (hipStream_t)stream)
-                  : step_impl<float>(h, nullptr, x0_device, eps, u_out, u0_out, stats, (hipStream_t)stream);
+    return with_real(h, [&](auto r) { return step_impl<decltype(r)>(h, nullptr, x0_device, eps, u_out, u0_out, stats, (hipStream_t)stream); });
 }
 
 extern "C" int mppi_partial_len(const mppi_handle *h, int32_t *n) {
@@ -1082,8 +1101,7 @@ static int begin_impl(mppi_handle *h, const double *x0, const float *eps, double
     h->slot_timed = timing_on(h);
     launch_rank_record<R>(h, P, F.beta, partial, s, h->slot_timed);
     HIPCHECK(h, hipGetLastError());
-    h->last_eps = eps;
-    h->last_philox = eps == nullptr;
+    note_noise(h, eps, false);  // (dev_loop_primed: set above)
     h->begun = true;
     return MPPI_OK;
 }
@@ -1099,8 +1117,7 @@ extern "C" int mppi_step_begin(mppi_handle *h, const double *x0, const float *ep
     double x[4] = {0, 0, 0, 0};
     if (x0)
         for (int i = 0; i < h->nx; ++i) x[i] = x0[i];
-    return h->f64 ? begin_impl<double>(h, x0 ? x : nullptr, eps, partial, (hipStream_t)stream)
-                  : begin_impl<float>(h, x0 ? x : nullptr, eps, partial, (hipStream_t)stream);
+    return with_real(h, [&](auto r) { return begin_impl<decltype(r)>(h, x0 ? x : nullptr, eps, partial, (hipStream_t)stream); });
 }
 
 extern "C" int mppi_step_end(mppi_handle *h, const double *partials, int32_t nranks, double *u_out, double *u0_out,
@@ -1114,22 +1131,12 @@ extern "C" int mppi_step_end(mppi_handle *h, const double *partials, int32_t nra
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     FinalizeParams F = make_finalize(h, partials, nranks, 0);
-    if (h->f64) launch_back<double>(h, F, true, s, h->slot_timed);
-    else launch_back<float>(h, F, true, s, h->slot_timed);
-    HIPCHECK(h, hipMemcpyAsync(h->h_res, h->d_res, h->res_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    HIPCHECK(h, hipGetLastError());
+    with_real(h, [&](auto r) { launch_back<decltype(r)>(h, F, true, s, h->slot_timed); });
+    if ((rc = fetch_result(h, h->res_bytes, s))) return rc;
     h->begun = false;
     h->dev_loop_primed = false;  // no plant ran: the next device-state step makes its own x0 call
-    h->idx = h->h_res->idx_after;
-    fill_stats(h, stats);
-    if (h->h_res->status == STATUS_PATH_END)
-        FAIL(h, MPPI_ERR_PATH_END, "[ERROR] Reached the end of the reference path.");
-    h->iter = h->h_res->iter;
-    const double *ru = reinterpret_cast<const double *>(h->h_res + 1);
-    if (u_out) memcpy(u_out, ru, sizeof(double) * 2 * h->cfg.T);
-    if (u0_out) { u0_out[0] = h->h_res->u0[0]; u0_out[1] = h->h_res->u0[1]; }
-    return MPPI_OK;
+    // kept: after an asynchronous split step this does not hand the index back to the host (idx_valid stays as it is)
+    return adopt_result(h, KEEP_IDX_VALID, u_out, u0_out, stats);
 }
 
 extern "C" int mppi_step_end_async(mppi_handle *h, const double *partials, int32_t nranks, void *stream) {
@@ -1141,8 +1148,7 @@ extern "C" int mppi_step_end_async(mppi_handle *h, const double *partials, int32
     if (!h->begun) FAIL(h, MPPI_ERR_STATE, "mppi_step_end_async without mppi_step_begin");
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     FinalizeParams F = make_finalize(h, partials, nranks, 1);  // plant on: the state advances on the device
-    if (h->f64) launch_back<double>(h, F, true, (hipStream_t)stream, h->slot_timed);
-    else launch_back<float>(h, F, true, (hipStream_t)stream, h->slot_timed);
+    with_real(h, [&](auto r) { launch_back<decltype(r)>(h, F, true, (hipStream_t)stream, h->slot_timed); });
     HIPCHECK(h, hipGetLastError());
     h->begun = false;
     h->idx_valid = false;  // the waypoint index now advances on the device until mppi_sync_result
@@ -1152,19 +1158,9 @@ extern "C" int mppi_step_end_async(mppi_handle *h, const double *partials, int32
 extern "C" int mppi_sync_result(mppi_handle *h, double *u_out, double *u0_out, mppi_stats *stats, void *stream) {
     if (!h) return MPPI_ERR_BAD_ARG;
     HIPCHECK(h, hipSetDevice(h->cfg.device));
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHECK(h, hipMemcpyAsync(h->h_res, h->d_res, h->res_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    h->idx = h->h_res->idx_after;
-    h->idx_valid = true;
-    fill_stats(h, stats);
-    if (h->h_res->status == STATUS_PATH_END)
-        FAIL(h, MPPI_ERR_PATH_END, "[ERROR] Reached the end of the reference path.");
-    h->iter = h->h_res->iter;
-    const double *ru = reinterpret_cast<const double *>(h->h_res + 1);
-    if (u_out) memcpy(u_out, ru, sizeof(double) * 2 * h->cfg.T);
-    if (u0_out) { u0_out[0] = h->h_res->u0[0]; u0_out[1] = h->h_res->u0[1]; }
-    return MPPI_OK;
+    // kept: no hipGetLastError after the synchronise (a launch that failed shows at the next call that asks)
+    if (int rc = fetch_result(h, h->res_bytes, (hipStream_t)stream, false)) return rc;
+    return adopt_result(h, 0, u_out, u0_out, stats);
 }
 
 extern "C" int mppi_get_costs(mppi_handle *h, double *S) {
@@ -1180,13 +1176,10 @@ extern "C" int mppi_get_weights(mppi_handle *h, double *w) {
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
     if (!h->d_w) HIPCHECK(h, hipMalloc((void **)&h->d_w, sizeof(double) * h->cfg.K));
-    if (h->f64) {
-        KParams<double> P = make_params<double>(h, nullptr);
-        launch_weights<double>(P, h->h_res->rho, h->h_res->eta, h->d_w, nullptr);
-    } else {
-        KParams<float> P = make_params<float>(h, nullptr);
-        launch_weights<float>(P, h->h_res->rho, h->h_res->eta, h->d_w, nullptr);
-    }
+    with_real(h, [&](auto r) {
+        using R = decltype(r);
+        launch_weights<R>(make_params<R>(h, nullptr), h->h_res->rho, h->h_res->eta, h->d_w, nullptr);
+    });
     HIPCHECK(h, hipDeviceSynchronize());
     HIPCHECK(h, hipMemcpy(w, h->d_w, sizeof(double) * h->cfg.K, hipMemcpyDeviceToHost));
     return MPPI_OK;
@@ -1230,21 +1223,15 @@ extern "C" int mppi_rollout_viz(mppi_handle *h, float *optimal_traj, float *samp
     SINGLE_AGENT_ONLY(h, "mppi_rollout_viz");
     if (h->iter < 1) FAIL(h, MPPI_ERR_STATE, "mppi_rollout_viz before the first mppi_step");
     HIPCHECK(h, hipSetDevice(h->cfg.device));
-    const float *eps = h->last_philox ? nullptr : h->last_eps;
-    const int T = h->cfg.T;
-    if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) {  // (fp32 only, checked at create)
-        KParams<float> P = make_params<float>(h, eps);
-        const float *hist = (const float *)h->d_uhist;
-        launch_viz_mlp(P, h->mlp, h->sw, hist, hist + 2 * T, h->iter - 1, optimal_traj, sampled_traj, (hipStream_t)stream);
-    } else if (h->f64) {
-        KParams<double> P = make_params<double>(h, eps);
-        const double *hist = (const double *)h->d_uhist;
-        launch_viz<double>(P, hist, hist + 2 * T, h->iter - 1, optimal_traj, sampled_traj, (hipStream_t)stream);
-    } else {
-        KParams<float> P = make_params<float>(h, eps);
-        const float *hist = (const float *)h->d_uhist;
-        launch_viz<float>(P, hist, hist + 2 * T, h->iter - 1, optimal_traj, sampled_traj, (hipStream_t)stream);
-    }
+    with_real(h, [&](auto r) {
+        using R = decltype(r);
+        const KParams<R> P = make_params<R>(h, h->last_eps);
+        const R *hist = (const R *)h->d_uhist, *hist_after = hist + 2 * h->cfg.T;
+        if constexpr (sizeof(R) == 4)  // (the learned model: f32 handles only, checked at create)
+            if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP)
+                return launch_viz_mlp(P, h->mlp, h->sw, hist, hist_after, h->iter - 1, optimal_traj, sampled_traj, (hipStream_t)stream);
+        launch_viz<R>(P, hist, hist_after, h->iter - 1, optimal_traj, sampled_traj, (hipStream_t)stream);
+    });
     HIPCHECK(h, hipGetLastError());
     return MPPI_OK;
 }
@@ -1347,6 +1334,19 @@ extern "C" int mppi_comm_init(mppi_handle *h, const void *unique_id, int32_t ran
     return MPPI_OK;
 }
 
+// The device buffer of the closed loop's u0 trace, grown to n_iters rows.  *rows: where the finalize kernel, which indexes by
+// the absolute iteration, finds row h->iter.
+static int trace_rows(mppi_handle *h, int n_iters, double **rows) {
+    if (h->trace_cap < n_iters) {
+        if (h->d_trace) HIPCHECK(h, hipFree(h->d_trace));
+        h->d_trace = nullptr;
+        HIPCHECK(h, hipMalloc((void **)&h->d_trace, sizeof(double) * 2 * n_iters));
+        h->trace_cap = n_iters;
+    }
+    *rows = h->d_trace - 2 * h->iter;
+    return MPPI_OK;
+}
+
 // One iteration on the stream with the collective in the middle: rollout -> this rank's record -> ncclAllGather ->
 // finalize over the gathered records (identical on every rank, so u stays replicated without a broadcast).
 template <typename R>
@@ -1365,18 +1365,8 @@ static int rccl_iteration(mppi_handle *h, const KParams<R> &P, int plant, double
 // outputs of the last finished iteration -> host (copy + synchronise; the collective paces the stream anyway)
 static int rccl_fetch(mppi_handle *h, double *u_out, double *u0_out, mppi_stats *stats, hipStream_t s) {
     HIPCHECK(h, hipGetLastError());
-    HIPCHECK(h, hipMemcpyAsync(h->h_res, h->d_res, h->res_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    HIPCHECK(h, hipGetLastError());
-    h->idx = h->h_res->idx_after;
-    h->idx_valid = true;
-    fill_stats(h, stats);
-    if (h->h_res->status == STATUS_PATH_END) FAIL(h, MPPI_ERR_PATH_END, "[ERROR] Reached the end of the reference path.");
-    h->iter = h->h_res->iter;
-    const double *ru = reinterpret_cast<const double *>(h->h_res + 1);
-    if (u_out) memcpy(u_out, ru, sizeof(double) * 2 * h->cfg.T);
-    if (u0_out) { u0_out[0] = h->h_res->u0[0]; u0_out[1] = h->h_res->u0[1]; }
-    return MPPI_OK;
+    if (int rc = fetch_result(h, h->res_bytes, s)) return rc;
+    return adopt_result(h, 0, u_out, u0_out, stats);
 }
 
 template <typename R>
@@ -1386,9 +1376,8 @@ static int step_rccl(mppi_handle *h, const double *x0, const double *x0_dev, con
     if (x0) launch_set_state<R>(P, x0, s);
     else launch_set_state_dev<R>(P, x0_dev, h->nx, s);  // the observed state in device memory (mppi_step_device_x0)
     if (int rc = rccl_iteration<R>(h, P, 0, nullptr, s)) return rc;
-    h->dev_loop_primed = false;
-    h->last_eps = eps;
-    h->last_philox = eps == nullptr;
+    note_noise(h, eps, true);
+    // kept: this carrier leaves last_iter_us (mppi_stats::iter_us) as the last call of another path set it
     return rccl_fetch(h, u_out, u0_out, stats, s);
 }
 
@@ -1396,21 +1385,14 @@ template <typename R>
 static int closed_loop_rccl(mppi_handle *h, int n_iters, double *u0_trace, mppi_stats *stats, hipStream_t s) {
     const KParams<R> P = make_params<R>(h, nullptr);
     double *trace = nullptr;
-    if (u0_trace) {
-        if (h->trace_cap < n_iters) {
-            if (h->d_trace) HIPCHECK(h, hipFree(h->d_trace));
-            h->d_trace = nullptr;
-            HIPCHECK(h, hipMalloc((void **)&h->d_trace, sizeof(double) * 2 * n_iters));
-            h->trace_cap = n_iters;
-        }
-        trace = h->d_trace - 2 * h->iter;  // the kernel indexes by the absolute iteration
-    }
+    if (u0_trace)
+        if (int rc = trace_rows(h, n_iters, &trace)) return rc;
     if (!h->dev_loop_primed) launch_set_state<R>(P, nullptr, s);  // (see closed_loop_impl)
     h->dev_loop_primed = false;
     for (int i = 0; i < n_iters; ++i)
         if (int rc = rccl_iteration<R>(h, P, 1, trace, s)) return rc;
-    h->last_eps = nullptr;
-    h->last_philox = true;
+    note_noise(h, nullptr, false);
+    // kept: this carrier leaves last_iter_us, t_enqueue_s and t_loop_s (mppi_get_host_timing) alone
     if (int rc = rccl_fetch(h, nullptr, nullptr, stats, s)) return rc;
     if (u0_trace) HIPCHECK(h, hipMemcpy(u0_trace, h->d_trace, sizeof(double) * 2 * n_iters, hipMemcpyDeviceToHost));
     h->dev_loop_primed = true;  // the last finalize made the next iteration's x0 call
@@ -1547,12 +1529,6 @@ extern "C" int mppi_comm_probe(mppi_handle *h, void *stream) {
     return MPPI_OK;
 }
 
-// GRAPH_SLOTS closed-loop iterations (rollout -> finalize, the device-resident plant, next x0 call) as ONE instantiated HIP
-// graph, cached per handle and re-captured when a kernel argument changes.  Replayed, an iteration costs the host a
-// 64th of a graph launch instead of two kernel launches (2.8 us each against the GPU's 4.4 us per kernel: a slower or
-// shared host core paces the eager loop, 10-12 us per iteration on such boxes of the pool), and the GPU side runs the
-// chain at 8.6-8.7 us per iteration on every box (mppi_time_rollout_launch measures exactly this).  Only iterations that
-// cannot ask for another round: frozen waypoint index, or the sequential one resting at the end of the path.
 // GRAPH_SLOTS closed-loop iterations (rollout -> finalize, the device-resident plant, next x0 call) as an instantiated HIP
 // graph, cached per handle and re-captured when a kernel argument changes.  Replayed, an iteration costs the host a
 // 64th of a graph launch instead of two kernel launches (2.8 us each against the GPU's 4.4 us per kernel: a slower or
@@ -1566,6 +1542,23 @@ extern "C" int mppi_comm_probe(mppi_handle *h, void *stream) {
 // changes) it came out 0.1-0.4 us per iteration behind, so eager launches stay the default.  MPPI_GRAPH_SLOTS: iterations
 // per graph (experiments).
 #define GRAPH_SLOTS (h->sw.graph_slots)
+
+// The one graph capture: n closed-loop slots (launch_slot) captured from gs, thread-local mode, into *graph.  The launch
+// counters come back as they were: a captured launch has not run (replays are counted where they are launched).
+// Instantiation, caching and replay are the caller's.
+template <typename R>
+static hipError_t capture_slots(mppi_handle *h, const KParams<R> &P, const FinalizeParams &F, int n, hipStream_t gs, hipGraph_t *graph) {
+    const long long l0 = h->n_rollout_launches, f0 = h->n_finalize_launches;
+    hipError_t e = hipStreamBeginCapture(gs, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        for (int j = 0; j < n; ++j) launch_slot<R>(h, P, F, gs);
+        e = hipStreamEndCapture(gs, graph);
+    }
+    h->n_rollout_launches = l0;
+    h->n_finalize_launches = f0;
+    return e;
+}
+
 template <typename R>
 static bool ensure_graph(mppi_handle *h, const KParams<R> &P, const FinalizeParams &F) {
     // (the learned model's parameters too: its launches carry MlpParams -- weight pointers, shape, output bias -- by value)
@@ -1588,14 +1581,7 @@ static bool ensure_graph(mppi_handle *h, const KParams<R> &P, const FinalizePara
     for (int i = 0; i < 2 && e == hipSuccess; ++i)
         if (!h->graph_done[i]) e = hipEventCreateWithFlags(&h->graph_done[i], hipEventDisableTiming);
     hipGraph_t graph = nullptr;
-    const long long l0 = h->n_rollout_launches, f0 = h->n_finalize_launches;
-    if (e == hipSuccess) e = hipStreamBeginCapture(h->graph_stream, hipStreamCaptureModeThreadLocal);
-    if (e == hipSuccess) {
-        for (int j = 0; j < GRAPH_SLOTS; ++j) launch_slot<R>(h, P, F, h->graph_stream);
-        e = hipStreamEndCapture(h->graph_stream, &graph);
-    }
-    h->n_rollout_launches = l0;  // (counted per replay)
-    h->n_finalize_launches = f0;
+    if (e == hipSuccess) e = capture_slots<R>(h, P, F, GRAPH_SLOTS, h->graph_stream, &graph);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipGraphInstantiate(&h->graph_exec[i], graph, nullptr, nullptr, 0);
     if (graph) hipGraphDestroy(graph);
     if (e != hipSuccess) {  // no graphs on this runtime: the eager loop serves
@@ -1616,15 +1602,8 @@ static int closed_loop_impl(mppi_handle *h, int n_iters, double *u0_trace, mppi_
     if (h->rccl_comm && h->x_nranks <= 1) return closed_loop_rccl<R>(h, n_iters, u0_trace, stats, s);
     KParams<R> P = make_params<R>(h, nullptr);
     FinalizeParams F = make_finalize(h, h->d_partials, h->n_part, 1);
-    if (u0_trace) {
-        if (h->trace_cap < n_iters) {
-            if (h->d_trace) HIPCHECK(h, hipFree(h->d_trace));
-            h->d_trace = nullptr;
-            HIPCHECK(h, hipMalloc((void **)&h->d_trace, sizeof(double) * 2 * n_iters));
-            h->trace_cap = n_iters;
-        }
-        F.u0_trace = h->d_trace - 2 * h->iter;  // the kernel indexes by the absolute iteration
-    }
+    if (u0_trace)
+        if (int rc = trace_rows(h, n_iters, &F.u0_trace)) return rc;
     const long long target = h->iter + n_iters;
     // x0 call for the state already on the device -- unless the finalize kernel of the previous closed-loop iteration
     // has made it (a second call would search from the index the first one left: with the frozen index that is c, not
@@ -1684,10 +1663,8 @@ static int closed_loop_impl(mppi_handle *h, int n_iters, double *u0_trace, mppi_
         h->t_enqueue_s += now_s() - t_enq;
         if (poll) {
             if (int rc = wait_result(h, h->seq, s)) return rc;
-        } else {
-            HIPCHECK(h, hipMemcpyAsync(h->h_res, h->d_res, (size_t)h->B * h->res_bytes, hipMemcpyDeviceToHost, s));
-            HIPCHECK(h, hipStreamSynchronize(s));
-            HIPCHECK(h, hipGetLastError());
+        } else if (int rc = fetch_result(h, (size_t)h->B * h->res_bytes, s)) {
+            return rc;
         }
         for (int a = 1; a < h->B; ++a) {  // an agent at the end of its path stops the batch like the single agent does
             const StepResult *ra =
@@ -1709,17 +1686,11 @@ static int closed_loop_impl(mppi_handle *h, int n_iters, double *u0_trace, mppi_
     }
     h->t_loop_s += now_s() - t_call;
     h->last_iter_us = 1e6 * (now_s() - t_call) / (n_iters > 0 ? n_iters : 1);
-    h->last_eps = nullptr;
-    h->last_philox = true;
-    h->idx = h->h_res->idx_after;
-    fill_stats(h, stats);
-    if (h->h_res->status == STATUS_EXCHANGE_FAILED)
-        FAIL(h, MPPI_ERR_COMM, "peer-to-peer exchange: a rank did not arrive within the timeout");
-    if (h->h_res->status == STATUS_PATH_END)
-        FAIL(h, MPPI_ERR_PATH_END, "[ERROR] Reached the end of the reference path.");
+    note_noise(h, nullptr, false);
+    // kept: after an asynchronous split step this does not hand the index back to the host (idx_valid stays as it is)
+    if (int rc = adopt_result(h, KEEP_IDX_VALID, nullptr, nullptr, stats)) return rc;
     if (u0_trace)
         HIPCHECK(h, hipMemcpy(u0_trace, h->d_trace, sizeof(double) * 2 * n_iters, hipMemcpyDeviceToHost));
-    h->iter = h->h_res->iter;
     h->dev_loop_primed = true;  // the last finalize made the next iteration's x0 call
     return MPPI_OK;
 }
@@ -1730,8 +1701,7 @@ extern "C" int mppi_run_closed_loop(mppi_handle *h, int32_t n_iters, double *u0_
     if (rc) return rc;
     if (n_iters < 1) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_run_closed_loop: n_iters < 1");
     HIPCHECK(h, hipSetDevice(h->cfg.device));
-    return h->f64 ? closed_loop_impl<double>(h, n_iters, u0_trace, stats, (hipStream_t)stream)
-                  : closed_loop_impl<float>(h, n_iters, u0_trace, stats, (hipStream_t)stream);
+    return with_real(h, [&](auto r) { return closed_loop_impl<decltype(r)>(h, n_iters, u0_trace, stats, (hipStream_t)stream); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1768,18 +1738,13 @@ static int time_rollout_impl(mppi_handle *h, int n_slots, int extra, hipStream_t
     const hipStream_t gs = sc.gs;
     const hipEvent_t e0 = sc.e0, e1 = sc.e1;
     const int saved = h->rollout_repeats, reps = 4;
-    const long long l0 = h->n_rollout_launches, f0 = h->n_finalize_launches;
     double ms[2] = {0.0, 0.0};
     int rc = MPPI_OK;
     for (int v = 0; v < 2 && rc == MPPI_OK; ++v) {
         h->rollout_repeats = v == 0 ? 1 : 1 + extra;
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
-        hipError_t e = hipStreamBeginCapture(gs, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            for (int j = 0; j < n_slots; ++j) launch_slot<R>(h, P, F, gs);
-            e = hipStreamEndCapture(gs, &graph);
-        }
+        hipError_t e = capture_slots<R>(h, P, F, n_slots, gs, &graph);  // (a diagnostic: the caller's launch counters stay)
         if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         if (e == hipSuccess) e = hipGraphLaunch(exec, gs);  // warm
         if (e == hipSuccess) e = hipStreamSynchronize(gs);
@@ -1800,16 +1765,14 @@ static int time_rollout_impl(mppi_handle *h, int n_slots, int extra, hipStream_t
         }
     }
     h->rollout_repeats = saved;
-    h->n_rollout_launches = l0;  // (a diagnostic: the bookkeeping of the caller's runs stays as it was)
-    h->n_finalize_launches = f0;
     if (rc != MPPI_OK) return rc;
     // the replays advanced the closed loop like any other run: pick the state up where they left it
     HIPCHECK(h, hipMemcpy(h->h_res, h->d_res, h->res_bytes, hipMemcpyDeviceToHost));
-    h->iter = h->h_res->iter;
-    h->idx = h->h_res->idx_after;
+    // kept: a diagnostic -- whatever status the last replayed slot left (a path end with raise_at_path_end) is not an error
+    // here, and idx_valid stays as it is
+    (void)adopt_result(h, KEEP_IDX_VALID | KEEP_GOING, nullptr, nullptr, nullptr);
     h->dev_loop_primed = true;
-    h->last_eps = nullptr;
-    h->last_philox = true;
+    note_noise(h, nullptr, false);
     const double per = (double)reps * n_slots;
     us_out[0] = 1e3 * (ms[1] - ms[0]) / (per * extra);
     us_out[1] = 1e3 * ms[0] / per;
@@ -1824,8 +1787,7 @@ extern "C" int mppi_time_rollout_launch(mppi_handle *h, int32_t n_slots, int32_t
     if (h->x_nranks > 1 || h->rccl_comm)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_time_rollout_launch: not with an exchange between ranks (its sequence numbers cannot be replayed)");
     HIPCHECK(h, hipSetDevice(h->cfg.device));
-    return h->f64 ? time_rollout_impl<double>(h, n_slots, extra, (hipStream_t)stream, us_out2)
-                  : time_rollout_impl<float>(h, n_slots, extra, (hipStream_t)stream, us_out2);
+    return with_real(h, [&](auto r) { return time_rollout_impl<decltype(r)>(h, n_slots, extra, (hipStream_t)stream, us_out2); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1895,8 +1857,7 @@ static int eval_entry(mppi_handle *h, const char *who, int what, const double *x
     if ((what != EVAL_CLAMP && !x) || ((what == EVAL_TRANSITION || what == EVAL_CLAMP) && !v))
         FAIL(h, MPPI_ERR_BAD_ARG, "%s: null input", who);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
-    return h->f64 ? eval_impl<double>(h, what, x, v, n, prev_idx, update, out, idx_out)
-                  : eval_impl<float>(h, what, x, v, n, prev_idx, update, out, idx_out);
+    return with_real(h, [&](auto r) { return eval_impl<decltype(r)>(h, what, x, v, n, prev_idx, update, out, idx_out); });
 }
 
 extern "C" int mppi_eval_state_transition(mppi_handle *h, const double *x, const double *v, int32_t n, double *x_next) {
@@ -1927,8 +1888,10 @@ extern "C" int mppi_eval_moving_average(mppi_handle *h, const double *xx, double
     HIPCHECK(h, in.alloc(rsz(h) * 2 * T));
     HIPCHECK(h, o.alloc(rsz(h) * 2 * T));
     if (int rc = upload_real(h, in.p, xx, (size_t)2 * T)) return rc;
-    if (h->f64) launch_eval_filter<double>((const double *)in.p, (double *)o.p, T, h->cfg.filter_window, h->cfg.filter_mode, nullptr);
-    else launch_eval_filter<float>((const float *)in.p, (float *)o.p, T, h->cfg.filter_window, h->cfg.filter_mode, nullptr);
+    with_real(h, [&](auto r) {
+        using R = decltype(r);
+        launch_eval_filter<R>((const R *)in.p, (R *)o.p, T, h->cfg.filter_window, h->cfg.filter_mode, nullptr);
+    });
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipDeviceSynchronize());
     return download_real(h, out, o.p, (size_t)2 * T);
