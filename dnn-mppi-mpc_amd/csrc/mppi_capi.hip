@@ -67,10 +67,9 @@ struct mppi_handle {
     bool f64 = false;
     int nx = 3, n_ref = 0, n_obs = 0, n_blocks = 0, traj_per_block = 0;
     bool fused = false;       // rollout + softmin partial in one launch (T <= 128)
-    int n_part = 0;           // records the rollout/reduce stage leaves in d_partials
     int B = 1;                // agents (mppi_config.n_agents); per-agent buffers are B consecutive copies
-    int slots = 0;            // records per agent in d_partials / d_heads (n_part + zero padding)
-    void *d_partials2 = nullptr;    // second level for large K (records merged 64:1)
+    int slots = 0;            // records per agent in d_partials / d_heads (the most a launch leaves + zero padding)
+    void *d_partials2 = nullptr;    // what a merge launch in front of the reader leaves (merge_tree)
     void *d_heads = nullptr, *d_heads2 = nullptr;  // compact {rho, eta, eta2, 0} of d_partials / d_partials2
     float *d_mlp = nullptr;         // packed residual-model weights (config 5)
     unsigned short *d_mlp16 = nullptr;  // the same as f16 hi / lo planes (k_rollout_mlp_h3, k_rollout_mlp_w)
@@ -171,8 +170,22 @@ static double softmin_beta(const mppi_config &c) {
 // The sequential index only grows: once it sits on the last waypoint every search window holds one candidate and nothing
 // can move.  index_can_move: the handle runs the kernels that resolve the index in one launch, and it has not got there.
 static bool at_path_end(const mppi_handle *h, int idx) { return idx >= h->n_ref - 1; }
+// The sequential index in one launch (look-back, LB_CAND in mppi_kernels.h) serves this handle: horizons of one 64-step pass
+// in the one-sample-per-wave layout or the two-samples-per-wave layout with one pass per workgroup, the reference's 20- / 10-
+// candidate windows, `S[k] =`, one agent, at most 512 workgroups = records (K <= 16384: configs 2 and 3).  Anything else keeps
+// the speculation rounds alone (they also serve as this path's fallback).  MPPI_NO_HYP=1 switches it off for A/B runs.
+// The one place that decides it: KParams::hyp carries it (while the index can move) to the rollout planners, and what they
+// picked comes back as RolloutPlan::lookback.
+static bool lookback_serves(const mppi_handle *h, int records) {
+    const mppi_config &c = h->cfg;
+    const bool lb_layout = (h->layout & LAYOUT_KIND) == LAYOUT_FUSED || h->layout == LAYOUT_DUAL;  // (one pass per workgroup)
+    return h->fused && lb_layout && c.T <= 64 && c.model == MPPI_MODEL_DIFFDRIVE && c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL &&
+           !c.accumulate_stage_cost && (c.search_window == HYP_WINDOW || c.search_window == HYP_WINDOW_CUDA) && c.n_agents == 1 &&
+           records <= HYP_MAX_BLOCKS && !h->sw.no_hyp;
+}
 static bool index_can_move(const mppi_handle *h) { return h->hyp && !(h->idx_valid && h->n_ref > 0 && at_path_end(h, h->idx)); }
 template <typename R> static KParams<R> make_params(const mppi_handle *h, const float *eps);
+template <typename R> static RolloutPlan front_plan(const mppi_handle *h, const KParams<R> &P);
 
 // host double[] -> device array in the kernel precision
 static int upload_real(mppi_handle *h, void *dst, const double *src, size_t n) {
@@ -238,13 +251,13 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         if (c.n_agents > 4096) FAIL((mppi_handle *)nullptr, MPPI_ERR_SHAPE, "mppi_create: n_agents %d > 4096", c.n_agents);
         if (c.model == MPPI_MODEL_DIFFDRIVE_MLP) {
             // one learned model for every agent: k_rollout_mlp_h3_agents / k_rollout_mlp_w_agents, one 64-sample tile per
-            // workgroup and agent; at most 512 records per agent, which k_finalize merges itself (launch_merge is not agent-aware)
-            if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL || c.K_global != c.K || mlp_blocks(c.K, 64) > 512)
+            // workgroup and agent; at most the 512 records per agent k_finalize merges itself (k_merge is not agent-aware)
+            if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL || c.K_global != c.K || merge_tree(mlp_blocks(c.K, 64), true).group)
                 FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED,
                      "several agents per learned-dynamics handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, at most 512 rollout "
                      "workgroups of 64 samples per agent (K <= 32768) and no sharding (got K = %d, K_global = %d)", c.K, c.K_global);
         } else if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL || c.K_global != c.K || !fused_supported(c.T) ||
-                   fused_blocks(c.K, c.T, rollout_layout(sw, c.K, c.T, c.n_agents, kernel_model(c), c.precision == MPPI_PREC_F64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT)) > 512) {
+                   merge_tree(fused_blocks(c.K, c.T, rollout_layout(sw, c.K, c.T, c.n_agents, kernel_model(c), c.precision == MPPI_PREC_F64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT)), true).group) {
             FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED,
                  "several agents per handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, T <= 128, at most 512 rollout workgroups "
                  "(K <= 8192) and no sharding");
@@ -289,8 +302,9 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     const bool tri_ok = c.model == MPPI_MODEL_RACECAR && !h->f64 && c.n_agents == 1 && c.waypoint_mode == MPPI_WAYPOINT_FROZEN &&
                         c.accumulate_stage_cost;
     h->layout = rollout_layout(sw, c.K, c.T, c.n_agents, kernel_model(c), h->f64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT, tri_ok);
-    h->n_part = h->fused ? fused_blocks(c.K, c.T, h->layout) : h->n_blocks;
-    if (c.model == MPPI_MODEL_DIFFDRIVE_MLP) h->n_part = mlp_blocks(c.K, 64);  // (mppi_set_mlp sets it again for the kernel that serves the model)
+    h->B = c.n_agents;
+    // records per agent of this handle's own rollout launch: its plan's count (every learned-dynamics kernel leaves the same)
+    const int n_part = with_real(h, [&](auto r) { return front_plan<decltype(r)>(h, make_params<decltype(r)>(h, nullptr)).records; });
     h->res_bytes = sizeof(StepResult) + sizeof(double) * 2 * c.T;
     auto fail = [&](hipError_t e, const char *what) {
         g_create_error = std::string(what) + " failed: " + hipGetErrorString(e);
@@ -307,7 +321,6 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     hipError_t e;
     if ((e = hipSetDevice(c.device)) != hipSuccess) return fail(e, "hipSetDevice");
     const size_t r = rsz(h), B = (size_t)c.n_agents;
-    h->B = c.n_agents;
     if (int rc = zeroed(&h->d_u, B * r * 2 * c.T, "hipMalloc(u)")) return rc;  // u_prev = 0 (:82)
     if (int rc = zeroed(&h->d_uhist, B * r * 4 * c.T, "hipMalloc(u history)")) return rc;
     if (int rc = zeroed(&h->d_S, B * r * c.K, "hipMalloc(S)")) return rc;
@@ -315,21 +328,15 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     const size_t rec_bytes = sizeof(double) * (size_t)record_len(c.T, 8);  // enough for either precision
     // zero-filled and padded by 256 records: the merge kernels read 256 slots unconditionally
     // (a launch may leave more records than the handle's own count -- fused_max_records: room for the larger of the two)
-    const size_t n_rec_max = (size_t)std::max(h->n_part, fused_max_records(c.K, c.T, h->layout));
-    const size_t slots = n_rec_max + 256, n1 = B * slots, n2 = n_rec_max / 64 + 2 + 256;
+    const size_t n_rec_max = (size_t)std::max(n_part, fused_max_records(c.K, c.T, h->layout));
+    // (the second level: a merge launch leaves at most one window, and only more records than a window are ever merged)
+    const size_t slots = n_rec_max + 256, n1 = B * slots, n2 = (merge_tree((int)n_rec_max, false).group ? MERGE_MAX_RECORDS : 0) + 256;
     h->slots = (int)slots;
     if (int rc = zeroed(&h->d_partials, rec_bytes * n1, "hipMalloc(partials)")) return rc;
     if (int rc = zeroed(&h->d_partials2, rec_bytes * n2, "hipMalloc(partials2)")) return rc;
     if (int rc = zeroed(&h->d_heads, 32 * n1, "hipMalloc(heads)")) return rc;
     if (int rc = zeroed(&h->d_heads2, 32 * n2, "hipMalloc(heads2)")) return rc;
-    // The sequential index in one launch (look-back, LB_CAND in mppi_kernels.h): horizons of one 64-step pass in the
-    // one-sample-per-wave layout or the two-samples-per-wave layout with one pass per workgroup, the reference's 20- / 10-
-    // candidate windows, `S[k] =`, one agent, at most 512 workgroups (K <= 16384: configs 2 and 3).  Anything else keeps the
-    // speculation rounds alone (they also serve as this path's fallback).  MPPI_NO_HYP=1 switches it off for A/B runs.
-    const bool lb_layout = (h->layout & LAYOUT_KIND) == LAYOUT_FUSED || h->layout == LAYOUT_DUAL;  // (one pass per workgroup)
-    h->hyp = h->fused && lb_layout && c.T <= 64 && c.model == MPPI_MODEL_DIFFDRIVE &&
-             c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL && !c.accumulate_stage_cost && (c.search_window == HYP_WINDOW || c.search_window == HYP_WINDOW_CUDA) &&
-             c.n_agents == 1 && h->n_part <= HYP_MAX_BLOCKS && !sw.no_hyp;
+    h->hyp = lookback_serves(h, n_part);
     if (h->hyp)
         if (int rc = zeroed((void **)&h->d_hyp_slots, sizeof(unsigned) * (size_t)LB_COPIES * LB_COPY_STRIDE, "hipMalloc(look-back words)")) return rc;
     h->res_bytes = (h->res_bytes + 15) & ~(size_t)15;  // (the agents' results are stored back to back)
@@ -532,10 +539,8 @@ extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, co
     h->mlp.n_hidden = n_hidden;
     h->mlp.hidden = H;
     h->sw.mlp = sw.mlp;
-    // the rollout kernel that serves this model: the records it leaves, and its name before the first launch already
-    const RolloutPlan plan = plan_mlp(make_params<float>(h, nullptr), h->mlp, h->sw);
-    h->n_part = plan.records;
-    h->rollout_kernel = plan.name;
+    // the rollout kernel that serves this model: its name before the first launch already
+    h->rollout_kernel = plan_mlp(make_params<float>(h, nullptr), h->mlp, h->sw).k.name;
     h->mlp_set = true;
     return MPPI_OK;
 }
@@ -725,13 +730,21 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     return P;
 }
 
-static FinalizeParams make_finalize(const mppi_handle *h, const void *partials, int n_part, int plant) {
+// the softmin rate as the records carry it
+static double record_beta(const mppi_handle *h) {
+    const double beta = softmin_beta(h->cfg);
+    return h->f64 ? beta : (double)(float)beta;  // the block partials were scaled with the f32 rate
+}
+
+// abi_recs / n_recs: the caller's records in the ABI layout (the split step's, the gathered ones); null: the records, their
+// count and the look-back fields are the slot plan's (plan_slot)
+static FinalizeParams make_finalize(const mppi_handle *h, int plant, const void *abi_recs = nullptr, int n_recs = 0) {
     const mppi_config &c = h->cfg;
     FinalizeParams F;
     memset(&F, 0, sizeof(F));
     F.T = c.T;
     F.K = c.K;
-    F.n_part = n_part;
+    F.n_part = n_recs;
     F.filter_mode = c.filter_mode;
     F.filter_window = c.filter_window;
     F.clamp_u = c.clamp_u_after_update;
@@ -743,14 +756,13 @@ static FinalizeParams make_finalize(const mppi_handle *h, const void *partials, 
     F.window = c.search_window;
     F.is_f64 = h->f64;
     F.count_hits = c.obstacle_model != MPPI_OBSTACLE_NONE && h->n_obs > 0;
-    F.beta = softmin_beta(c);
-    if (!h->f64) F.beta = (double)(float)F.beta;  // the block partials were scaled with the f32 rate
+    F.beta = record_beta(h);
     F.dt = c.delta_t;
     F.wheel_base = c.wheel_base;
     F.umax0 = c.u_max[0];
     F.umax1 = c.u_max[1];
-    F.partials = partials;
-    F.heads = partials == h->d_partials2 ? h->d_heads2 : h->d_heads;
+    F.partials = abi_recs;
+    F.heads = h->d_heads;  // (unused for the ABI layout)
     F.u = h->d_u;
     F.u_out = h->d_u;
     F.u_before = h->d_uhist;
@@ -763,8 +775,6 @@ static FinalizeParams make_finalize(const mppi_handle *h, const void *partials, 
     F.n_agents = h->B;
     F.res_stride = h->res_bytes;
     F.u0_trace = nullptr;
-    F.hyp = partials == h->d_partials && index_can_move(h);
-    F.hyp_blocks = h->n_part;
     F.hyp_slots = h->d_hyp_slots;
     F.lb_seq = 0;
     F.pad_lb = 0;
@@ -789,10 +799,15 @@ static hipEvent_t next_event(mppi_handle *h) {
 
 static bool timing_on(const mppi_handle *h) { return h->timing && h->ev_used + EV_PER_SLOT <= EV_MAX; }
 
-// Softmin partial records of this handle's samples: rollout (+ reduce when not fused), and for large K a
-// 64:1 merge so that the finalize block never reads more than MAX_FINAL_PARTS records.
-constexpr int MAX_FINAL_PARTS = 256;   // = MERGE_MAX_RECORDS of the kernels (ABI records: one per rank)
-constexpr int MAX_DIRECT_PARTS = 512;  // block records k_finalize merges itself (two windows of 256)
+// the peer-to-peer exchange as mppi_comm_connect wired it (x_seq: drawn per launch)
+static void wire_exchange(const mppi_handle *h, FinalizeParams &F) {
+    if (h->x_nranks <= 1) return;
+    F.x_nranks = h->x_nranks;
+    F.x_rank = h->x_rank;
+    F.x_timeout = h->x_timeout;
+    F.x_peers = h->d_xpeers;
+    F.x_err = h->d_xerr;
+}
 
 // the rollout launch of this handle (the learned model: f32 handles only, mppi_create refuses the rest)
 template <typename R> static RolloutPlan front_plan(const mppi_handle *h, const KParams<R> &P) {
@@ -800,71 +815,93 @@ template <typename R> static RolloutPlan front_plan(const mppi_handle *h, const 
         if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) return plan_mlp(P, h->mlp, h->sw);
     return plan_rollout<R>(P, h->fused, h->sw);
 }
-template <typename R> static void launch_front_plan(mppi_handle *h, const RolloutPlan &plan, const KParams<R> &P, hipStream_t s) {
-    if constexpr (sizeof(R) == 4)
-        if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) return launch_mlp(plan, P, h->mlp, h->d_partials, nullptr, s);
-    launch_rollout<R>(plan, P, h->d_partials, s);
-}
 
+// One iteration slot, resolved once and executed many times: rollout (-> reduce) (-> merge) -> its reader.  The reader is
+// k_finalize -- local, or with the peer-to-peer exchange once mppi_comm_connect has wired it -- or, for the carriers that
+// exchange records outside the slot (split step, RCCL), the k_merge that writes this rank's ONE record {rho, eta, eta2,
+// W[T][2]} in f64; their finalize over the gathered records is plan_finalize(..., abi_recs) alone.  plan_slot is a pure
+// function of P, the handle's switches and wiring and the carrier; it aims F at the records the finalize reads.  Nothing in
+// it depends on what changes from slot to slot: the look-back tag, the exchange sequence number, use_args, res / seq.
+struct SlotPlan {
+    RolloutPlan front;      // front.lookback: the slot draws a tag and k_finalize<..., HYPK> reads the words
+    bool reduce = false;    // k_reduce follows the rollout (k_rollout)
+    int n_merges = 0;       // k_merge launches: the tree's (merge_tree), then the one that writes the rank's record
+    MergeStep merge[2];
+    double beta = 0.0;      // record_beta: the rate the merges scale with
+    KernelLaunch fin;       // (none with rank_record)
+};
 template <typename R>
-static void launch_front(mppi_handle *h, const KParams<R> &P, double beta, hipStream_t s, const void **recs,
-                         const void **heads, int *n_recs, bool tm) {
-    if (tm) hipEventRecord(next_event(h), s);
-    const RolloutPlan plan = front_plan<R>(h, P);
-    h->n_rollout_launches += h->rollout_repeats;
-    for (int rep = 0; rep < h->rollout_repeats; ++rep) launch_front_plan<R>(h, plan, P, s);
-    h->rollout_kernel = plan.name;
-    if (tm) hipEventRecord(next_event(h), s);
-    if (tm) hipEventRecord(next_event(h), s);
-    if (h->cfg.model != MPPI_MODEL_DIFFDRIVE_MLP && !h->fused) launch_reduce<R>(P, h->d_partials, plan.records, s);
-    const int n_part = plan.records;  // (per agent)
-    *recs = h->d_partials;
-    *heads = h->d_heads;
-    *n_recs = n_part;
-    if (n_part > MAX_DIRECT_PARTS) {
-        const int group = n_part > 64 * MAX_FINAL_PARTS ? MAX_FINAL_PARTS : 64;
-        launch_merge<R>(h->d_partials, h->d_heads, n_part, group, h->cfg.T, beta, h->d_partials2, h->d_heads2, false, s);
-        *recs = h->d_partials2;
-        *heads = h->d_heads2;
-        *n_recs = (n_part + group - 1) / group;
+static SlotPlan plan_slot(const mppi_handle *h, const KParams<R> &P, FinalizeParams *F, double *rank_record = nullptr) {
+    SlotPlan sp;
+    sp.front = front_plan<R>(h, P);
+    sp.reduce = h->cfg.model != MPPI_MODEL_DIFFDRIVE_MLP && !h->fused;
+    sp.beta = record_beta(h);
+    const void *recs = h->d_partials, *heads = h->d_heads;
+    const MergeTree tree = merge_tree(sp.front.records, rank_record == nullptr);
+    if (tree.group) {
+        sp.merge[sp.n_merges++] = plan_merge<R>(recs, heads, sp.front.records, tree.group, h->cfg.T, h->d_partials2, h->d_heads2);
+        recs = h->d_partials2;
+        heads = h->d_heads2;
     }
+    if (rank_record) {
+        sp.merge[sp.n_merges++] = plan_merge<R>(recs, heads, tree.n_out, tree.n_out, h->cfg.T, rank_record, nullptr);
+        return sp;
+    }
+    F->partials = recs;
+    F->heads = heads;
+    F->n_part = tree.n_out;
+    F->hyp = sp.front.lookback;
+    F->hyp_blocks = sp.front.records;
+    wire_exchange(h, *F);
+    sp.fin = plan_finalize<R>(*F, false, sp.front.lookback);
+    return sp;
+}
+
+// the plan's launches up to its reader: [rollout] [reduce / merge]
+template <typename R> static void launch_records(mppi_handle *h, const SlotPlan &sp, const KParams<R> &P, hipStream_t s, bool tm) {
+    if (tm) hipEventRecord(next_event(h), s);
+    h->n_rollout_launches += h->rollout_repeats;
+    for (int rep = 0; rep < h->rollout_repeats; ++rep) {
+        if constexpr (sizeof(R) == 4)
+            if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) {
+                launch_mlp(sp.front, P, h->mlp, h->d_partials, nullptr, s);
+                continue;
+            }
+        launch_rollout<R>(sp.front, P, h->d_partials, s);
+    }
+    h->rollout_kernel = sp.front.k.name;
+    if (tm) hipEventRecord(next_event(h), s);
+    if (tm) hipEventRecord(next_event(h), s);
+    if (sp.reduce) launch_reduce<R>(P, h->d_partials, sp.front.records, s);
+    for (int i = 0; i < sp.n_merges; ++i) launch_merge<R>(sp.merge[i], h->cfg.T, sp.beta, s);
     if (tm) hipEventRecord(next_event(h), s);
 }
 
-template <typename R>
-static void launch_back(mppi_handle *h, const FinalizeParams &F, bool abi_recs, hipStream_t s, bool tm) {
+// [finalize] [empty]
+static void launch_back(mppi_handle *h, const KernelLaunch &fin, const FinalizeParams &F, hipStream_t s, bool tm) {
     if (tm) hipEventRecord(next_event(h), s);
     ++h->n_finalize_launches;
-    launch_finalize<R>(F, abi_recs, s);
+    launch_finalize(fin, F, s);
     if (tm) hipEventRecord(next_event(h), s);
     if (tm) hipEventRecord(next_event(h), s);  // empty pair: the cost of the bracketing itself
     if (tm) hipEventRecord(next_event(h), s);
 }
 
-static void arm_exchange(mppi_handle *h, FinalizeParams &F) {
-    if (h->x_nranks <= 1) return;
-    F.x_nranks = h->x_nranks;
-    F.x_rank = h->x_rank;
-    F.x_seq = ++h->xseq;
-    F.x_timeout = h->x_timeout;
-    F.x_peers = h->d_xpeers;
-    F.x_err = h->d_xerr;
-}
-
-// rollout (-> reduce) -> finalize
+// One execution of a slot plan that ends in k_finalize.  Per slot: the exchange's sequence number, the look-back tag, the
+// optional events, the rollout_repeats loop, the launches and the counters.
 template <typename R>
-static void launch_slot(mppi_handle *h, const KParams<R> &P, FinalizeParams F, hipStream_t s) {
+static void launch_slot(mppi_handle *h, const SlotPlan &sp, const KParams<R> &P, FinalizeParams F, hipStream_t s) {
     const bool tm = timing_on(h);
-    arm_exchange(h, F);
-    if (P.hyp) {  // the look-back words of this launch pair carry its own tag (lb_tag)
+    if (F.x_nranks > 1) F.x_seq = ++h->xseq;
+    if (sp.front.lookback) {  // the look-back words of this launch pair carry its own tag (lb_tag)
         if ((++h->lb_seq & 0xffffffu) == 0u) ++h->lb_seq;
         KParams<R> Pl = P;
         Pl.lb_seq = F.lb_seq = h->lb_seq;
-        launch_front<R>(h, Pl, F.beta, s, &F.partials, &F.heads, &F.n_part, tm);
+        launch_records<R>(h, sp, Pl, s, tm);
     } else {
-        launch_front<R>(h, P, F.beta, s, &F.partials, &F.heads, &F.n_part, tm);
+        launch_records<R>(h, sp, P, s, tm);
     }
-    launch_back<R>(h, F, false, s, tm);
+    launch_back(h, sp.fin, F, s, tm);
 }
 
 static void collect_timing(mppi_handle *h) {
@@ -1019,7 +1056,7 @@ static int step_impl(mppi_handle *h, const double *x0, const double *x0_dev, con
     if (h->rccl_comm && h->x_nranks <= 1) return step_rccl<R>(h, x0, x0_dev, eps, u_out, u0_out, stats, s);
     const double t_call = now_s();
     KParams<R> P = make_params<R>(h, eps);
-    FinalizeParams F = make_finalize(h, h->d_partials, h->n_part, 0);
+    FinalizeParams F = make_finalize(h, 0);
     const bool by_args = x0 && h->idx_valid && !h->sw.no_args;
     if (!x0) {
         if (!h->idx_valid) FAIL(h, MPPI_ERR_STATE, "mppi_step_device_x0 after an asynchronous split step: call mppi_sync_result first");
@@ -1027,15 +1064,16 @@ static int step_impl(mppi_handle *h, const double *x0, const double *x0_dev, con
     } else if (by_args) {
         P.use_args = F.use_args = 1;
         P.c_arg = F.c_arg = host_x0_call(h, x0);
-        P.hyp = F.hyp = h->hyp && !at_path_end(h, P.c_arg);
+        P.hyp = h->hyp && !at_path_end(h, P.c_arg);
         for (int i = 0; i < 4; ++i) P.x0_arg[i] = F.x0_arg[i] = x0[i];
     } else {
         launch_set_state<R>(P, x0, s);
     }
     if (!h->sw.no_poll) F.res = h->res_mapped;
+    const SlotPlan sp = plan_slot<R>(h, P, &F);  // (the speculation rounds reuse it)
     for (int round = 0;; ++round) {
         F.seq = !h->sw.no_poll ? ++h->seq : 0;
-        launch_slot<R>(h, P, F, s);
+        launch_slot<R>(h, sp, P, F, s);
         HIPCHECK(h, hipGetLastError());  // a refused launch would otherwise show only as the poll's timeout
         int rc = wait_result(h, F.seq, s);
         if (rc) return rc;
@@ -1076,30 +1114,14 @@ extern "C" int mppi_partial_len(const mppi_handle *h, int32_t *n) {
     return MPPI_OK;
 }
 
-// rollout (-> reduce) -> merges down to this rank's ONE record {rho, eta, eta2, W[T][2]} in f64 at `partial` (device)
-template <typename R>
-static void launch_rank_record(mppi_handle *h, const KParams<R> &P, double beta, double *partial, hipStream_t s, bool tm) {
-    const void *recs, *heads;
-    int n_recs;
-    launch_front<R>(h, P, beta, s, &recs, &heads, &n_recs, tm);
-    if (n_recs > MAX_FINAL_PARTS) {  // (k_merge takes 256 records per workgroup)
-        launch_merge<R>(recs, heads, n_recs, 64, h->cfg.T, beta, h->d_partials2, h->d_heads2, false, s);
-        recs = h->d_partials2;
-        heads = h->d_heads2;
-        n_recs = (n_recs + 63) / 64;
-    }
-    launch_merge<R>(recs, heads, n_recs, n_recs, h->cfg.T, beta, partial, nullptr, true, s);
-}
-
 template <typename R>
 static int begin_impl(mppi_handle *h, const double *x0, const float *eps, double *partial, hipStream_t s) {
     KParams<R> P = make_params<R>(h, eps);
-    const FinalizeParams F = make_finalize(h, h->d_partials, h->n_part, 0);
     // closed loop on the device: the previous end_async already made the x0 call for the new state
     if (x0 || !h->dev_loop_primed) launch_set_state<R>(P, x0, s);
     h->dev_loop_primed = x0 == nullptr;
     h->slot_timed = timing_on(h);
-    launch_rank_record<R>(h, P, F.beta, partial, s, h->slot_timed);
+    launch_records<R>(h, plan_slot<R>(h, P, nullptr, partial), P, s, h->slot_timed);
     HIPCHECK(h, hipGetLastError());
     note_noise(h, eps, false);  // (dev_loop_primed: set above)
     h->begun = true;
@@ -1125,13 +1147,13 @@ extern "C" int mppi_step_end(mppi_handle *h, const double *partials, int32_t nra
     int rc = check_ready(h, "mppi_step_end");
     if (rc) return rc;
     SINGLE_AGENT_ONLY(h, "mppi_step_end");
-    if (!partials || nranks < 1 || nranks > MAX_FINAL_PARTS)
-        FAIL(h, MPPI_ERR_BAD_ARG, "mppi_step_end: bad partials/nranks (1..%d)", MAX_FINAL_PARTS);
+    if (!partials || nranks < 1 || nranks > MERGE_MAX_RECORDS)
+        FAIL(h, MPPI_ERR_BAD_ARG, "mppi_step_end: bad partials/nranks (1..%d)", MERGE_MAX_RECORDS);
     if (!h->begun) FAIL(h, MPPI_ERR_STATE, "mppi_step_end without mppi_step_begin");
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
-    FinalizeParams F = make_finalize(h, partials, nranks, 0);
-    with_real(h, [&](auto r) { launch_back<decltype(r)>(h, F, true, s, h->slot_timed); });
+    const FinalizeParams F = make_finalize(h, 0, partials, nranks);
+    with_real(h, [&](auto r) { launch_back(h, plan_finalize<decltype(r)>(F, true, false), F, s, h->slot_timed); });
     if ((rc = fetch_result(h, h->res_bytes, s))) return rc;
     h->begun = false;
     h->dev_loop_primed = false;  // no plant ran: the next device-state step makes its own x0 call
@@ -1143,12 +1165,12 @@ extern "C" int mppi_step_end_async(mppi_handle *h, const double *partials, int32
     int rc = check_ready(h, "mppi_step_end_async");
     if (rc) return rc;
     SINGLE_AGENT_ONLY(h, "mppi_step_end_async");
-    if (!partials || nranks < 1 || nranks > MAX_FINAL_PARTS)
-        FAIL(h, MPPI_ERR_BAD_ARG, "mppi_step_end_async: bad partials/nranks (1..%d)", MAX_FINAL_PARTS);
+    if (!partials || nranks < 1 || nranks > MERGE_MAX_RECORDS)
+        FAIL(h, MPPI_ERR_BAD_ARG, "mppi_step_end_async: bad partials/nranks (1..%d)", MERGE_MAX_RECORDS);
     if (!h->begun) FAIL(h, MPPI_ERR_STATE, "mppi_step_end_async without mppi_step_begin");
     HIPCHECK(h, hipSetDevice(h->cfg.device));
-    FinalizeParams F = make_finalize(h, partials, nranks, 1);  // plant on: the state advances on the device
-    with_real(h, [&](auto r) { launch_back<decltype(r)>(h, F, true, (hipStream_t)stream, h->slot_timed); });
+    const FinalizeParams F = make_finalize(h, 1, partials, nranks);  // plant on: the state advances on the device
+    with_real(h, [&](auto r) { launch_back(h, plan_finalize<decltype(r)>(F, true, false), F, (hipStream_t)stream, h->slot_timed); });
     HIPCHECK(h, hipGetLastError());
     h->begun = false;
     h->idx_valid = false;  // the waypoint index now advances on the device until mppi_sync_result
@@ -1315,8 +1337,8 @@ extern "C" int mppi_comm_unique_id(void *id_out) {
 extern "C" int mppi_comm_init(mppi_handle *h, const void *unique_id, int32_t rank, int32_t nranks) {
     if (!h || !unique_id) return MPPI_ERR_BAD_ARG;
     SINGLE_AGENT_ONLY(h, "mppi_comm_init");
-    if (nranks < 1 || nranks > MAX_FINAL_PARTS || rank < 0 || rank >= nranks)
-        FAIL(h, MPPI_ERR_BAD_ARG, "mppi_comm_init: rank %d of %d (1..%d ranks)", rank, nranks, MAX_FINAL_PARTS);
+    if (nranks < 1 || nranks > MERGE_MAX_RECORDS || rank < 0 || rank >= nranks)
+        FAIL(h, MPPI_ERR_BAD_ARG, "mppi_comm_init: rank %d of %d (1..%d ranks)", rank, nranks, MERGE_MAX_RECORDS);
     if (h->cfg.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "the exchange needs MPPI_WAYPOINT_FROZEN (no cross-sample waypoint state)");
     RcclApi &a = rccl_api();
@@ -1352,13 +1374,12 @@ static int trace_rows(mppi_handle *h, int n_iters, double **rows) {
 template <typename R>
 static int rccl_iteration(mppi_handle *h, const KParams<R> &P, int plant, double *u0_trace_dev, hipStream_t s) {
     const bool tm = timing_on(h);
-    const FinalizeParams F0 = make_finalize(h, h->d_partials, h->n_part, 0);
-    launch_rank_record<R>(h, P, F0.beta, h->d_rccl_part, s, tm);
+    launch_records<R>(h, plan_slot<R>(h, P, nullptr, h->d_rccl_part), P, s, tm);
     RCCLCHECK(h, rccl_api().AllGather(h->d_rccl_part, h->d_rccl_gath, (size_t)partial_len(h->cfg.T), 8 /* ncclFloat64 */,
                                       h->rccl_comm, s));
-    FinalizeParams F = make_finalize(h, h->d_rccl_gath, h->rccl_nranks, plant);
+    FinalizeParams F = make_finalize(h, plant, h->d_rccl_gath, h->rccl_nranks);
     F.u0_trace = u0_trace_dev;
-    launch_back<R>(h, F, true, s, tm);
+    launch_back(h, plan_finalize<R>(F, true, false), F, s, tm);
     return MPPI_OK;
 }
 
@@ -1516,8 +1537,9 @@ extern "C" int mppi_comm_probe(mppi_handle *h, void *stream) {
     if (!h) return MPPI_ERR_BAD_ARG;
     if (h->x_nranks <= 1) FAIL(h, MPPI_ERR_STATE, "mppi_comm_probe before mppi_comm_connect");
     HIPCHECK(h, hipSetDevice(h->cfg.device));
-    FinalizeParams F = make_finalize(h, nullptr, 0, 0);
-    arm_exchange(h, F);
+    FinalizeParams F = make_finalize(h, 0);
+    wire_exchange(h, F);
+    F.x_seq = ++h->xseq;
     launch_exchange_probe(F, h->d_xok, (hipStream_t)stream);
     int ok = 0;
     HIPCHECK(h, hipMemcpyAsync(&ok, h->d_xok, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -1543,15 +1565,16 @@ extern "C" int mppi_comm_probe(mppi_handle *h, void *stream) {
 // per graph (experiments).
 #define GRAPH_SLOTS (h->sw.graph_slots)
 
-// The one graph capture: n closed-loop slots (launch_slot) captured from gs, thread-local mode, into *graph.  The launch
+// The one graph capture: n executions of a slot plan (launch_slot) captured from gs, thread-local mode, into *graph.  The launch
 // counters come back as they were: a captured launch has not run (replays are counted where they are launched).
 // Instantiation, caching and replay are the caller's.
 template <typename R>
-static hipError_t capture_slots(mppi_handle *h, const KParams<R> &P, const FinalizeParams &F, int n, hipStream_t gs, hipGraph_t *graph) {
+static hipError_t capture_slots(mppi_handle *h, const SlotPlan &sp, const KParams<R> &P, const FinalizeParams &F, int n, hipStream_t gs,
+                                hipGraph_t *graph) {
     const long long l0 = h->n_rollout_launches, f0 = h->n_finalize_launches;
     hipError_t e = hipStreamBeginCapture(gs, hipStreamCaptureModeThreadLocal);
     if (e == hipSuccess) {
-        for (int j = 0; j < n; ++j) launch_slot<R>(h, P, F, gs);
+        for (int j = 0; j < n; ++j) launch_slot<R>(h, sp, P, F, gs);
         e = hipStreamEndCapture(gs, graph);
     }
     h->n_rollout_launches = l0;
@@ -1560,7 +1583,7 @@ static hipError_t capture_slots(mppi_handle *h, const KParams<R> &P, const Final
 }
 
 template <typename R>
-static bool ensure_graph(mppi_handle *h, const KParams<R> &P, const FinalizeParams &F) {
+static bool ensure_graph(mppi_handle *h, const SlotPlan &sp, const KParams<R> &P, const FinalizeParams &F) {
     // (the learned model's parameters too: its launches carry MlpParams -- weight pointers, shape, output bias -- by value)
     std::vector<char> key(sizeof(P) + sizeof(F) + 2 * sizeof(int) + sizeof(MlpParams));
     memcpy(key.data(), &P, sizeof(P));
@@ -1581,7 +1604,7 @@ static bool ensure_graph(mppi_handle *h, const KParams<R> &P, const FinalizePara
     for (int i = 0; i < 2 && e == hipSuccess; ++i)
         if (!h->graph_done[i]) e = hipEventCreateWithFlags(&h->graph_done[i], hipEventDisableTiming);
     hipGraph_t graph = nullptr;
-    if (e == hipSuccess) e = capture_slots<R>(h, P, F, GRAPH_SLOTS, h->graph_stream, &graph);
+    if (e == hipSuccess) e = capture_slots<R>(h, sp, P, F, GRAPH_SLOTS, h->graph_stream, &graph);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipGraphInstantiate(&h->graph_exec[i], graph, nullptr, nullptr, 0);
     if (graph) hipGraphDestroy(graph);
     if (e != hipSuccess) {  // no graphs on this runtime: the eager loop serves
@@ -1601,9 +1624,10 @@ template <typename R>
 static int closed_loop_impl(mppi_handle *h, int n_iters, double *u0_trace, mppi_stats *stats, hipStream_t s) {
     if (h->rccl_comm && h->x_nranks <= 1) return closed_loop_rccl<R>(h, n_iters, u0_trace, stats, s);
     KParams<R> P = make_params<R>(h, nullptr);
-    FinalizeParams F = make_finalize(h, h->d_partials, h->n_part, 1);
+    FinalizeParams F = make_finalize(h, 1);
     if (u0_trace)
         if (int rc = trace_rows(h, n_iters, &F.u0_trace)) return rc;
+    SlotPlan sp = plan_slot<R>(h, P, &F);  // for the whole call -- made again where the look-back is dropped at the path end
     const long long target = h->iter + n_iters;
     // x0 call for the state already on the device -- unless the finalize kernel of the previous closed-loop iteration
     // has made it (a second call would search from the index the first one left: with the frozen index that is c, not
@@ -1630,7 +1654,7 @@ static int closed_loop_impl(mppi_handle *h, int n_iters, double *u0_trace, mppi_
         hipStream_t ls = s;
         long long i = 0;
         if (h->graph_on && rests && !P.hyp && !u0_trace && h->x_nranks <= 1 && !timing_on(h) && todo > GRAPH_SLOTS &&
-            ensure_graph<R>(h, P, F)) {
+            ensure_graph<R>(h, sp, P, F)) {
             ls = h->graph_stream;
             HIPCHECK(h, hipEventRecord(h->graph_ev_in, s));
             HIPCHECK(h, hipStreamWaitEvent(ls, h->graph_ev_in, 0));
@@ -1650,9 +1674,9 @@ static int closed_loop_impl(mppi_handle *h, int n_iters, double *u0_trace, mppi_
                 FinalizeParams Fl = F;
                 Fl.res = h->res_mapped;
                 Fl.seq = ++h->seq;
-                launch_slot<R>(h, P, Fl, ls);
+                launch_slot<R>(h, sp, P, Fl, ls);
             } else {
-                launch_slot<R>(h, P, F, ls);
+                launch_slot<R>(h, sp, P, F, ls);
             }
         }
         if (ls != s) {
@@ -1676,7 +1700,8 @@ static int closed_loop_impl(mppi_handle *h, int n_iters, double *u0_trace, mppi_
         idx_now = h->h_res->idx_after;
         if (P.hyp) {
             if (h->B == 1 && at_path_end(h, h->h_res->idx_after)) {
-                P.hyp = F.hyp = 0;
+                P.hyp = 0;
+                sp = plan_slot<R>(h, P, &F);
                 batch = 1LL << 62;
             } else {
                 batch *= 2;
@@ -1714,7 +1739,8 @@ extern "C" int mppi_run_closed_loop(mppi_handle *h, int32_t n_iters, double *u0_
 template <typename R>
 static int time_rollout_impl(mppi_handle *h, int n_slots, int extra, hipStream_t s, double *us_out) {
     KParams<R> P = make_params<R>(h, nullptr);
-    FinalizeParams F = make_finalize(h, h->d_partials, h->n_part, 1);
+    FinalizeParams F = make_finalize(h, 1);
+    const SlotPlan sp = plan_slot<R>(h, P, &F);
     if (P.hyp || (h->cfg.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL && !at_path_end(h, h->idx)))
         FAIL(h, MPPI_ERR_STATE, "mppi_time_rollout_launch: the sequential waypoint index can still move (speculation rounds "
                                 "cannot be replayed from a graph); call it once the index rests at the end of the path");
@@ -1744,7 +1770,7 @@ static int time_rollout_impl(mppi_handle *h, int n_slots, int extra, hipStream_t
         h->rollout_repeats = v == 0 ? 1 : 1 + extra;
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
-        hipError_t e = capture_slots<R>(h, P, F, n_slots, gs, &graph);  // (a diagnostic: the caller's launch counters stay)
+        hipError_t e = capture_slots<R>(h, sp, P, F, n_slots, gs, &graph);  // (a diagnostic: the caller's launch counters stay)
         if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         if (e == hipSuccess) e = hipGraphLaunch(exec, gs);  // warm
         if (e == hipSuccess) e = hipStreamSynchronize(gs);

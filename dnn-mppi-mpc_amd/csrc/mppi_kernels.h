@@ -85,11 +85,27 @@ __host__ __device__ inline int record_len(int T, int elem_bytes) {
 // filter's padded layout [2 (T + W + 1)], the updated controls [2T], 64 record scales per wave and window, block
 // reductions, per-group partial sums.  Every region starts on a 16-byte boundary.
 constexpr int MERGE_THREADS = 256;
-constexpr int MERGE_MAX_RECORDS = 256;  // per window
+constexpr int MERGE_MAX_RECORDS = 256;  // per window: what one k_merge workgroup takes, and the ABI records (one per rank) of a finalize
 constexpr int MERGE_MAX_WINDOWS = 2;    // k_finalize takes up to 512 records itself (K = 16384 in the dual layout)
 __host__ __device__ inline size_t merge_lds_elems(int T, int W, size_t elem, int nt = MERGE_THREADS) {
     const size_t r4 = 3, nw = (2 * (size_t)(T + W + 1) + r4) & ~r4, nu = (2 * (size_t)T + r4) & ~r4;
     return nw + nu + (size_t)MERGE_MAX_WINDOWS * nt + 64 + (size_t)(nt / 32) * 32 * (16 / elem);
+}
+// The merge tree between the n records a rollout launch leaves (per agent) and their reader, the one place that knows its
+// shape.  k_finalize reads up to MERGE_MAX_WINDOWS windows, the k_merge that writes a rank's one record (split step) one;
+// more records than that go through ONE k_merge launch first, `group` records per workgroup: 64, or a whole window where
+// 64:1 would leave more than a window.  What it leaves fits a window (n <= 256 * 256: K <= 2^20 samples, >= 16 per record).
+// group: records per workgroup of the merge launch in front of the reader, 0: none; n_out: records the reader takes, in
+// `windows` windows of MERGE_MAX_RECORDS
+struct MergeTree { int group, n_out, windows; };
+inline MergeTree merge_tree(int n, bool finalize_reads) {
+    MergeTree t = {0, n, 1};
+    if (n > (finalize_reads ? MERGE_MAX_WINDOWS : 1) * MERGE_MAX_RECORDS) {
+        t.group = n > 64 * MERGE_MAX_RECORDS ? MERGE_MAX_RECORDS : 64;
+        t.n_out = (n + t.group - 1) / t.group;
+    }
+    t.windows = (t.n_out + MERGE_MAX_RECORDS - 1) / MERGE_MAX_RECORDS;
+    return t;
 }
 
 template <typename R> struct KParams {
@@ -126,7 +142,8 @@ template <typename R> struct KParams {
     // all samples' calls) and starts from the x0 call's index at every sample: samples stay independent
     int per_rollout, pad_pr;
     // one-launch resolution of the sequential index (see LB_CAND)
-    int hyp;                // the handle qualifies (one pass per workgroup, T <= 64, window 20 / 10, `S[k] =`, one agent, <= 512 workgroups)
+    int hyp;                // the look-back serves the handle (lookback_serves, mppi_capi.hip) and the index can still move:
+                            // what the rollout planners read; RolloutPlan::lookback says whether the launch they picked publishes words
     unsigned lb_seq;        // this launch pair's tag (see lb_tag)
     unsigned *hyp_slots;    // [HYP_MAX_BLOCKS] one word per workgroup
 };
@@ -137,7 +154,7 @@ struct FinalizeParams {
     int model, sequential, plant, n_ref;
     int window, is_f64, count_hits, pad1;  // count_hits: the block records' heads carry collision counts (a handle with obstacles)
     double beta, dt, wheel_base, umax0, umax1;
-    const void *partials;    // [n_part][partial_len], n_part <= 256; element type: see launch_finalize
+    const void *partials;    // [n_part] records: the slot plan's, or the caller's ABI records [n_part][partial_len], n_part <= 256
     const void *heads;       // compact heads of `partials` (KParams::heads); unused for the ABI layout
     void *u;                 // [T][2] in the kernel precision: the controls the finished rollouts used
     void *u_out;             // where the updated, shifted controls go (== u: in place)
@@ -162,7 +179,8 @@ struct FinalizeParams {
     // several agents per launch (blockIdx.y), see KParams
     int slots, n_agents;
     size_t res_stride;       // bytes between two agents' StepResult (+ returned u)
-    // one-launch resolution of the sequential index (see LB_CAND / KParams)
+    // one-launch resolution of the sequential index (see LB_CAND / KParams): filled from the slot plan -- hyp its `lookback`
+    // (plan_finalize picks the HYPK kernel from that flag), hyp_blocks the rollout plan's record count
     int hyp, hyp_blocks;
     const unsigned *hyp_slots;
     unsigned lb_seq, pad_lb;
@@ -227,17 +245,30 @@ struct Switches {
     long long exchange_timeout_ms = 0;   // MPPI_EXCHANGE_TIMEOUT_MS (> 0: set)
 };
 
-// One rollout launch, resolved once: which instantiation, how it is launched, what it is called and what it leaves.  Made by
-// plan_rollout (mppi_kernels.hip) / plan_mlp (mppi_mlp.hip) -- pure functions of the kernel parameters and the switches,
-// a handful of branches -- and executed by launch_plan.  A new kernel variant is one more entry in its family's planner.
-struct RolloutPlan {
+// One kernel launch, resolved once: which instantiation and how it is launched.  Made by the planners -- plan_rollout, plan_merge,
+// plan_finalize (mppi_kernels.hip), plan_mlp (mppi_mlp.hip): pure functions of the kernel parameters and the switches, a
+// handful of branches -- and executed by launch_plan.  A new kernel variant is one more entry in its family's planner.
+struct KernelLaunch {
     const void *fn = nullptr;    // the __global__ instantiation
     const char *name = "";       // as rocprofv3 spells it ("k_rollout_dual<float, 1, 1, false, 2, true, false>"); static storage
     dim3 grid, block;
     size_t lds = 0;              // dynamic LDS bytes
-    int records = 0;             // softmin records per agent the launch leaves (k_rollout: what launch_reduce leaves behind it)
-    int passes = 0;              // k_rollout_stream's batches per workgroup, else 0
     bool *lds_raised = nullptr;  // per device: hipFuncAttributeMaxDynamicSharedMemorySize was raised to `lds` (null: not needed)
+};
+// A rollout launch and what it leaves
+struct RolloutPlan {
+    KernelLaunch k;
+    int records = 0;        // softmin records per agent the launch leaves (k_rollout: what launch_reduce leaves behind it)
+    int passes = 0;         // k_rollout_stream's batches per workgroup, else 0
+    bool lookback = false;  // the instantiation publishes look-back words (LB_CAND): only then does k_finalize<..., HYPK> follow
+};
+// A k_merge launch: groups of `group` <= 256 records (handle precision) of recs[n] -> out[ceil(n / group)], internal layout
+// with compact heads, or -- out_heads null -- the ABI layout in doubles
+struct MergeStep {
+    KernelLaunch k;
+    const void *recs = nullptr, *heads = nullptr;
+    int n = 0, group = 0;
+    void *out = nullptr, *out_heads = nullptr;
 };
 constexpr int PLAN_MAX_DEVICES = 64;
 // What is static about one instantiation, kept as a function-local static of its *_entry template beside the function
@@ -253,8 +284,8 @@ struct KernelEntry {
     }
     static const char *of(bool b) { return b ? "true" : "false"; }
 };
-inline RolloutPlan plan_entry(const void *fn, KernelEntry &e, int threads, size_t lds = 0) {
-    RolloutPlan p;
+inline KernelLaunch plan_entry(const void *fn, KernelEntry &e, int threads, size_t lds = 0) {
+    KernelLaunch p;
     p.fn = fn;
     p.name = e.name;
     p.block = dim3(threads);
@@ -264,7 +295,7 @@ inline RolloutPlan plan_entry(const void *fn, KernelEntry &e, int threads, size_
 }
 // `args`: the kernel's arguments in order (a kernel with a shorter list takes the first ones).  Every kernel is launched
 // from the file that defines it: this is inline so that each of the two files carries its own copy.
-inline void launch_plan(const RolloutPlan &p, void **args, hipStream_t s) {
+inline void launch_plan(const KernelLaunch &p, void **args, hipStream_t s) {
     if (p.lds_raised) {  // (the attribute belongs to the device's copy of the code object: one process may drive several GPUs)
         int dev = 0;
         (void)hipGetDevice(&dev);
@@ -291,14 +322,12 @@ int fused_max_records(int K, int T, int layout);
 // else k_rollout_fused / _dual / _tri by P.layout, or k_rollout_stream where it serves (T <= 128)
 template <typename R> RolloutPlan plan_rollout(const KParams<R> &P, bool fused, const Switches &sw);
 template <typename R> void launch_rollout(const RolloutPlan &plan, const KParams<R> &P, void *partials, hipStream_t s);
-// merges groups of `group` <= 256 records (precision R) of `recs[n]` into out[ceil(n/group)]
-// (`heads` / `out_heads`: the compact head arrays of the input / internal-layout output records)
-template <typename R>
-void launch_merge(const void *recs, const void *heads, int n, int group, int T, double beta, void *out, void *out_heads,
-                  bool out_f64, hipStream_t s);
-// F.partials holds n_part <= 256 records of precision R (recs_f64 false) or double
-// (with F.x_nranks > 1 and recs_f64 false: the peer-to-peer exchange variant)
-template <typename R> void launch_finalize(const FinalizeParams &F, bool recs_f64, hipStream_t s);
+template <typename R> MergeStep plan_merge(const void *recs, const void *heads, int n, int group, int T, void *out, void *out_heads);
+template <typename R> void launch_merge(const MergeStep &m, int T, double beta, hipStream_t s);
+// k_finalize over F.partials: F.n_part <= 512 records of precision R -- with F.x_nranks > 1 the peer-to-peer exchange variant --
+// or (abi_recs) <= 256 ABI records in doubles.  lookback: RolloutPlan::lookback of the rollout in front of it
+template <typename R> KernelLaunch plan_finalize(const FinalizeParams &F, bool abi_recs, bool lookback);
+void launch_finalize(const KernelLaunch &k, const FinalizeParams &F, hipStream_t s);
 // exchange self-test: one flag round over the peers, no records
 void launch_exchange_probe(const FinalizeParams &F, int *ok_out, hipStream_t s);
 // batched stage methods (mppi_eval_*): `what` of launch_eval

@@ -2652,25 +2652,25 @@ __global__ __launch_bounds__(64) void k_set_state_dev(const R *ref, int n_ref, i
 // Plan entries: the one place per kernel family where template arguments turn into the function to launch and its name as
 // rocprofv3 prints it (bench.py looks its counters up by this name) -- both from the same arguments, the name formatted once.
 template <typename R> static const char *type_name() { return sizeof(R) == 8 ? "double" : "float"; }
-template <typename R, int MODEL> static RolloutPlan rollout_entry() {
+template <typename R, int MODEL> static KernelLaunch rollout_entry() {
     static KernelEntry e("k_rollout<%s, %d>", type_name<R>(), MODEL);
     return plan_entry(reinterpret_cast<const void *>(k_rollout<R, MODEL>), e, 256);
 }
-template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK> static RolloutPlan fused_entry() {
+template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK> static KernelLaunch fused_entry() {
     static KernelEntry e("k_rollout_fused<%s, %d, %d, %s, %d, %s>", type_name<R>(), MODEL, NCH, KernelEntry::of(MULTI), SPEC,
                                  KernelEntry::of(HYPK));
     return plan_entry(reinterpret_cast<const void *>(k_rollout_fused<R, MODEL, NCH, MULTI, SPEC, HYPK>), e, 64 * FUSED_WAVES);
 }
-template <typename R, int MODEL, int SPW, bool MULTI, int SEQ, bool PLAIN, bool LB = false> static RolloutPlan dual_entry() {
+template <typename R, int MODEL, int SPW, bool MULTI, int SEQ, bool PLAIN, bool LB = false> static KernelLaunch dual_entry() {
     static KernelEntry e("k_rollout_dual<%s, %d, %d, %s, %d, %s, %s>", type_name<R>(), MODEL, SPW, KernelEntry::of(MULTI), SEQ,
                                  KernelEntry::of(PLAIN), KernelEntry::of(LB));
     return plan_entry(reinterpret_cast<const void *>(k_rollout_dual<R, MODEL, SPW, MULTI, SEQ, PLAIN, LB>), e, 64 * DUAL_WAVES);
 }
-template <bool PLAIN, bool SHARE> static RolloutPlan tri_entry() {
+template <bool PLAIN, bool SHARE> static KernelLaunch tri_entry() {
     static KernelEntry e("k_rollout_tri<%s, %s>", KernelEntry::of(PLAIN), KernelEntry::of(SHARE));
     return plan_entry(reinterpret_cast<const void *>(k_rollout_tri<PLAIN, SHARE>), e, 64 * DUAL_WAVES);
 }
-template <typename R, bool MULTI, bool OBS, bool PHILOX> static RolloutPlan stream_entry() {
+template <typename R, bool MULTI, bool OBS, bool PHILOX> static KernelLaunch stream_entry() {
     static KernelEntry e("k_rollout_stream<%s, %s, %s, %s>", type_name<R>(), KernelEntry::of(MULTI), KernelEntry::of(OBS),
                                  KernelEntry::of(PHILOX));
     return plan_entry(reinterpret_cast<const void *>(k_rollout_stream<R, MULTI, OBS, PHILOX>), e, 64 * DUAL_WAVES);
@@ -2755,9 +2755,9 @@ int fused_max_records(int K, int T, int layout) {  // (one pass per workgroup is
 // k_rollout_dual<R, MODEL, SPW, MULTI, ...>: the LB form resolves the sequential index in the launch (diff-drive, one agent,
 // two samples per wave, one pass); PLAIN: every single-agent form, and for batched agents the one the default layout takes
 // -- two samples per wave, one pass
-template <typename R, int MODEL, bool MULTI, int SPW> static RolloutPlan dual_plan(bool twice, bool plain, bool lb) {
+template <typename R, int MODEL, bool MULTI, int SPW> static KernelLaunch dual_plan(bool twice, bool plain, bool lb) {
     if constexpr (!MULTI && MODEL == MODEL_DIFF && SPW == 2)
-        if (lb && !twice) return plain ? dual_entry<R, MODEL_DIFF, 2, false, 1, true, true>() : dual_entry<R, MODEL_DIFF, 2, false, 1, false, true>();
+        if (lb) return plain ? dual_entry<R, MODEL_DIFF, 2, false, 1, true, true>() : dual_entry<R, MODEL_DIFF, 2, false, 1, false, true>();
     if constexpr (!MULTI)
         if (plain) return twice ? dual_entry<R, MODEL, SPW, false, 2, true>() : dual_entry<R, MODEL, SPW, false, 1, true>();
     if constexpr (MULTI && SPW == 2)
@@ -2765,7 +2765,7 @@ template <typename R, int MODEL, bool MULTI, int SPW> static RolloutPlan dual_pl
     return twice ? dual_entry<R, MODEL, SPW, MULTI, 2, false>() : dual_entry<R, MODEL, SPW, MULTI, 1, false>();
 }
 // k_rollout_fused<R, MODEL, NCH, MULTI, SPEC, HYPK>: SPEC 2 the plain form, 1 no obstacles, 0 everything
-template <typename R, int MODEL, int NCH, bool MULTI, bool HYPK> static RolloutPlan fused_plan(int spec) {
+template <typename R, int MODEL, int NCH, bool MULTI, bool HYPK> static KernelLaunch fused_plan(int spec) {
     return spec == 2   ? fused_entry<R, MODEL, NCH, MULTI, 2, HYPK>()
            : spec == 1 ? fused_entry<R, MODEL, NCH, MULTI, 1, HYPK>()
                        : fused_entry<R, MODEL, NCH, MULTI, 0, HYPK>();
@@ -2774,11 +2774,11 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
     RolloutPlan p;
     if (const int np = stream_passes(P, sw)) {
         const bool obs = P.obstacle_model != OBS_NONE;
-        p = P.use_philox ? (obs ? stream_entry<R, MULTI, true, true>() : stream_entry<R, MULTI, false, true>())
-                         : (obs ? stream_entry<R, MULTI, true, false>() : stream_entry<R, MULTI, false, false>());
+        p.k = P.use_philox ? (obs ? stream_entry<R, MULTI, true, true>() : stream_entry<R, MULTI, false, true>())
+                           : (obs ? stream_entry<R, MULTI, true, false>() : stream_entry<R, MULTI, false, false>());
         p.passes = np;
         p.records = (stream_batches(P.K) + np - 1) / np;
-        p.grid = dim3(p.records, MULTI ? P.n_agents : 1);
+        p.k.grid = dim3(p.records, MULTI ? P.n_agents : 1);
         return p;
     }
     const int blocks = fused_blocks(P.K, P.T, P.layout);
@@ -2786,13 +2786,16 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
     const bool race = MODEL == MODEL_RACE;
     const bool plain_ok = P.use_philox && P.clamp_rollout && (bool)P.wrap_stage == race && (bool)P.wrap_term == race;
     switch (P.layout & LAYOUT_KIND) {
-    case LAYOUT_DUAL: p = dual_plan<R, MODEL, MULTI, 2>(twice, plain_ok, P.hyp != 0); break;
-    case LAYOUT_PAIR: p = dual_plan<R, MODEL, MULTI, 1>(twice, plain_ok, false); break;
+    case LAYOUT_DUAL:
+        p.lookback = !MULTI && MODEL == MODEL_DIFF && P.hyp && !twice;  // (the LB form: one agent, diff-drive, one pass)
+        p.k = dual_plan<R, MODEL, MULTI, 2>(twice, plain_ok, p.lookback);
+        break;
+    case LAYOUT_PAIR: p.k = dual_plan<R, MODEL, MULTI, 1>(twice, plain_ok, false); break;
     case LAYOUT_TRI:
         if constexpr (sizeof(R) == 4 && MODEL == MODEL_RACE && !MULTI) {
             const bool share = blocks > 256;  // (more than one workgroup per CU)
-            p = plain_ok ? (share ? tri_entry<true, true>() : tri_entry<true, false>())
-                         : (share ? tri_entry<false, true>() : tri_entry<false, false>());
+            p.k = plain_ok ? (share ? tri_entry<true, true>() : tri_entry<true, false>())
+                           : (share ? tri_entry<false, true>() : tri_entry<false, false>());
         }
         break;
     default:
@@ -2800,14 +2803,14 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
             const bool plain = P.obstacle_model == OBS_NONE && P.use_philox && P.clamp_rollout && !P.wrap_stage && !P.wrap_term &&
                                !P.per_rollout;
             const int spec = plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
-            // (HYPK: the sequential index resolved in the launch)
-            p = P.hyp && P.T <= 64 && !MULTI && MODEL == MODEL_DIFF ? fused_plan<R, MODEL_DIFF, 1, false, true>(spec)
-                : P.T <= 64                                         ? fused_plan<R, MODEL, 1, MULTI, false>(spec)
-                                                                    : fused_plan<R, MODEL, 2, MULTI, false>(spec);
+            p.lookback = !MULTI && MODEL == MODEL_DIFF && P.hyp && P.T <= 64;  // (the HYPK form: one agent, diff-drive, one chunk)
+            p.k = p.lookback  ? fused_plan<R, MODEL_DIFF, 1, false, true>(spec)
+                  : P.T <= 64 ? fused_plan<R, MODEL, 1, MULTI, false>(spec)
+                              : fused_plan<R, MODEL, 2, MULTI, false>(spec);
         }
     }
     p.records = blocks;
-    p.grid = dim3(blocks, MULTI ? P.n_agents : 1);
+    p.k.grid = dim3(blocks, MULTI ? P.n_agents : 1);
     return p;
 }
 
@@ -2817,8 +2820,9 @@ template <typename R> RolloutPlan plan_rollout(const KParams<R> &P, bool fused, 
         if (P.n_agents > 1) return diff ? plan_fused<R, MODEL_DIFF, true>(P, sw) : plan_fused<R, MODEL_RACE, true>(P, sw);
         return diff ? plan_fused<R, MODEL_DIFF, false>(P, sw) : plan_fused<R, MODEL_RACE, false>(P, sw);
     }
-    RolloutPlan p = diff ? rollout_entry<R, MODEL_DIFF>() : rollout_entry<R, MODEL_RACE>();
-    p.grid = dim3((P.K + 3) / 4);  // four waves per workgroup, a sample each
+    RolloutPlan p;
+    p.k = diff ? rollout_entry<R, MODEL_DIFF>() : rollout_entry<R, MODEL_RACE>();
+    p.k.grid = dim3((P.K + 3) / 4);  // four waves per workgroup, a sample each
     p.records = reduce_blocks(P.K, P.traj_per_block);
     return p;
 }
@@ -2826,7 +2830,7 @@ template <typename R> void launch_rollout(const RolloutPlan &plan, const KParams
     const DevState *st = P.st;
     int n_pass = plan.passes;
     void *args[] = {&st, const_cast<KParams<R> *>(&P), &partials, &n_pass};  // (k_rollout: the first two; n_pass: k_rollout_stream)
-    launch_plan(plan, args, s);
+    launch_plan(plan.k, args, s);
 }
 
 template <typename R> void launch_reduce(const KParams<R> &P, void *partials, int n_blocks, hipStream_t s) {
@@ -2836,48 +2840,55 @@ template <typename R> void launch_reduce(const KParams<R> &P, void *partials, in
 
 static size_t merge_lds(int T, int W, size_t elem) { return elem * merge_lds_elems(T, W, elem); }
 
-template <typename R>
-void launch_merge(const void *recs, const void *heads, int n, int group, int T, double beta, void *out, void *out_heads,
-                  bool out_abi, hipStream_t s) {
-    const int blocks = (n + group - 1) / group;
-    if (out_abi)
-        hipLaunchKernelGGL((k_merge<R, true>), dim3(blocks), dim3(MERGE_THREADS), merge_lds(T, 0, sizeof(R)), s,
-                           (const R *)recs, (const R *)heads, n, group, T, (R)beta, out, (R *)nullptr);
-    else
-        hipLaunchKernelGGL((k_merge<R, false>), dim3(blocks), dim3(MERGE_THREADS), merge_lds(T, 0, sizeof(R)), s,
-                           (const R *)recs, (const R *)heads, n, group, T, (R)beta, out, (R *)out_heads);
+template <typename R, bool ABI_OUT> static KernelLaunch merge_entry() {
+    static KernelEntry e("k_merge<%s, %s>", type_name<R>(), KernelEntry::of(ABI_OUT));
+    return plan_entry(reinterpret_cast<const void *>(k_merge<R, ABI_OUT>), e, MERGE_THREADS);
+}
+template <typename R> MergeStep plan_merge(const void *recs, const void *heads, int n, int group, int T, void *out, void *out_heads) {
+    MergeStep m;
+    m.k = out_heads ? merge_entry<R, false>() : merge_entry<R, true>();
+    m.k.grid = dim3((n + group - 1) / group);
+    m.k.lds = merge_lds(T, 0, sizeof(R));
+    m.recs = recs, m.heads = heads, m.n = n, m.group = group, m.out = out, m.out_heads = out_heads;
+    return m;
+}
+template <typename R> void launch_merge(const MergeStep &m, int T, double beta, hipStream_t s) {
+    R b = (R)beta;
+    void *args[] = {const_cast<const void **>(&m.recs), const_cast<const void **>(&m.heads), const_cast<int *>(&m.n),
+                    const_cast<int *>(&m.group), &T, &b, const_cast<void **>(&m.out), const_cast<void **>(&m.out_heads)};
+    launch_plan(m.k, args, s);
 }
 
-template <typename R> void launch_finalize(const FinalizeParams &F, bool abi_recs, hipStream_t s) {
+template <typename R, int MODE, int NWIN, bool MULTI, bool PLAIN = false, bool HYPK = false> static KernelLaunch finalize_entry() {
+    static KernelEntry e("k_finalize<%s, %d, %d, %s, %s, %s>", type_name<R>(), MODE, NWIN, KernelEntry::of(MULTI), KernelEntry::of(PLAIN),
+                         KernelEntry::of(HYPK));
+    return plan_entry(reinterpret_cast<const void *>(k_finalize<R, MODE, NWIN, MULTI, PLAIN, HYPK>), e, MERGE_THREADS);
+}
+// k_finalize<R, MODE, NWIN, MULTI, PLAIN, HYPK>: MODE 1 the caller's ABI records, 2 the peer-to-peer exchange, 0 neither; NWIN
+// windows of records; MULTI one workgroup per agent; HYPK reads the look-back words of the rollout in front of it; PLAIN (one
+// window, one agent) the closed loop of the reference's diff-drive file with nothing optional switched on
+template <typename R> KernelLaunch plan_finalize(const FinalizeParams &F, bool abi_recs, bool lookback) {
+    const bool two = merge_tree(F.n_part, true).windows > 1;
+    const bool multi = !abi_recs && F.x_nranks <= 1 && F.n_agents > 1;
+    const bool plain = F.sequential && F.plant && !F.use_args && !F.raise_at_path_end && !F.clamp_u && F.model == MODEL_DIFF &&
+                       !F.u0_trace && F.filter_mode == FILTER_DIFF;
+    KernelLaunch k = abi_recs         ? finalize_entry<R, 1, 1, false>()
+                     : F.x_nranks > 1 ? (two ? finalize_entry<R, 2, 2, false>() : finalize_entry<R, 2, 1, false>())
+                     : multi          ? (two ? finalize_entry<R, 0, 2, true>() : finalize_entry<R, 0, 1, true>())
+                     : two            ? (lookback ? finalize_entry<R, 0, 2, false, false, true>() : finalize_entry<R, 0, 2, false>())
+                     : lookback       ? (plain ? finalize_entry<R, 0, 1, false, true, true>() : finalize_entry<R, 0, 1, false, false, true>())
+                                      : (plain ? finalize_entry<R, 0, 1, false, true, false>() : finalize_entry<R, 0, 1, false>());
+    k.grid = dim3(1, multi ? F.n_agents : 1);
     // (+ the staging area of the peer-to-peer exchange; merge_lds_elems is a multiple of 4 elements: 16-byte aligned)
-    const size_t lds = merge_lds(F.T, F.filter_window, sizeof(R)) +
-                       (F.x_nranks > 1 ? sizeof(double) * XCHG_LDS_RANKS * xchg_rec_len(F.T) : 0) +
-                       (F.hyp ? (size_t)HYP_MAX_BLOCKS + 16 : 0);
+    k.lds = merge_lds(F.T, F.filter_window, sizeof(R)) + (F.x_nranks > 1 ? sizeof(double) * XCHG_LDS_RANKS * xchg_rec_len(F.T) : 0) +
+            (lookback ? (size_t)HYP_MAX_BLOCKS + 16 : 0);
+    return k;
+}
+void launch_finalize(const KernelLaunch &k, const FinalizeParams &F, hipStream_t s) {
     const DevState *st = F.st;
-    const bool two = F.n_part > MERGE_MAX_RECORDS;  // (at most MERGE_MAX_WINDOWS * 256: the caller merges above that)
-    const bool multi = !abi_recs && F.x_nranks <= 1 && F.n_agents > 1;  // one workgroup per agent
-    const dim3 grid(1, multi ? F.n_agents : 1);
-#define MPPI_FIN(MODE, NWIN, MULTI)                                                                                    \
-    hipLaunchKernelGGL((k_finalize<R, MODE, NWIN, MULTI>), grid, dim3(MERGE_THREADS), lds, s, F.partials, F.heads, st,  \
-                       (const void *)F.u, F.T, F)
-    if (abi_recs) MPPI_FIN(1, 1, false);
-    else if (F.x_nranks > 1) { if (two) MPPI_FIN(2, 2, false); else MPPI_FIN(2, 1, false); }
-    else if (multi) { if (two) MPPI_FIN(0, 2, true); else MPPI_FIN(0, 1, true); }
-    else if (two) {
-        if (F.hyp) hipLaunchKernelGGL((k_finalize<R, 0, 2, false, false, true>), grid, dim3(MERGE_THREADS), lds, s, F.partials, F.heads, st,
-                                      (const void *)F.u, F.T, F);
-        else MPPI_FIN(0, 2, false);
-    } else {
-        const bool plain = F.sequential && F.plant && !F.use_args && !F.raise_at_path_end && !F.clamp_u && F.model == MODEL_DIFF &&
-                           !F.u0_trace && F.filter_mode == FILTER_DIFF;
-#define MPPI_FIN_SINGLE(PLAIN_, HYPK_)                                                                                  \
-    hipLaunchKernelGGL((k_finalize<R, 0, 1, false, PLAIN_, HYPK_>), grid, dim3(MERGE_THREADS), lds, s, F.partials, F.heads, \
-                       st, (const void *)F.u, F.T, F)
-        if (F.hyp) { if (plain) MPPI_FIN_SINGLE(true, true); else MPPI_FIN_SINGLE(false, true); }
-        else { if (plain) MPPI_FIN_SINGLE(true, false); else MPPI_FIN_SINGLE(false, false); }
-#undef MPPI_FIN_SINGLE
-    }
-#undef MPPI_FIN
+    void *args[] = {const_cast<const void **>(&F.partials), const_cast<const void **>(&F.heads), &st, const_cast<void **>(&F.u),
+                    const_cast<int *>(&F.T), const_cast<FinalizeParams *>(&F)};
+    launch_plan(k, args, s);
 }
 
 void launch_exchange_probe(const FinalizeParams &F, int *ok_out, hipStream_t s) {
@@ -2940,8 +2951,9 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
     template RolloutPlan plan_rollout<R>(const KParams<R> &, bool, const Switches &);                     \
     template void launch_rollout<R>(const RolloutPlan &, const KParams<R> &, void *, hipStream_t);        \
     template void launch_reduce<R>(const KParams<R> &, void *, int, hipStream_t);                         \
-    template void launch_merge<R>(const void *, const void *, int, int, int, double, void *, void *, bool, hipStream_t);        \
-    template void launch_finalize<R>(const FinalizeParams &, bool, hipStream_t);                          \
+    template MergeStep plan_merge<R>(const void *, const void *, int, int, int, void *, void *);             \
+    template void launch_merge<R>(const MergeStep &, int, double, hipStream_t);                           \
+    template KernelLaunch plan_finalize<R>(const FinalizeParams &, bool, bool);                           \
     template void launch_weights<R>(const KParams<R> &, double, double, double *, hipStream_t);           \
     template void launch_eval_index<R>(const KParams<R> &, const R *, int, int, int, int, int *, int *, hipStream_t); \
     template void launch_eval<R>(const KParams<R> &, int, const R *, const R *, const int *, int, R *, hipStream_t);   \

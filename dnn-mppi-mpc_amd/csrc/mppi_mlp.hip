@@ -791,29 +791,29 @@ static bool mlp_is_w(const MlpParams &Q) { return !mlp_shape_is_h3(Q.hidden, Q.n
 // Plan entries: the one place per kernel where template arguments turn into the function to launch, its name as rocprofv3
 // prints it, its workgroup and its dynamic LDS (beyond 64 KB: launch_plan raises the attribute before the first launch on
 // a device).
-static RolloutPlan f32_entry() {
+static KernelLaunch f32_entry() {
     static KernelEntry e("k_rollout_mlp(");  // (up to the parenthesis: the other kernels' names begin with this one's)
     const size_t ref_lds = sizeof(float) * 4 * MLP_REF_LDS_MAX;  // the path (mlp_stage_path)
     return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp), e, 64 * MLP_WAVES,
                       sizeof(float) * (MLP_M * MLP_PITCH + MLP_M * 8 + MLP_WAVES * MLP_M * 4) + ref_lds);
 }
-template <bool VIZ, int NW, int RT, int TERMS = 3> static RolloutPlan h3_entry() {
+template <bool VIZ, int NW, int RT, int TERMS = 3> static KernelLaunch h3_entry() {
     static KernelEntry e("k_rollout_mlp_h3<%s, %d, %d, %d>", KernelEntry::of(VIZ), NW, RT, TERMS);
     return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_h3<VIZ, NW, RT, TERMS>), e, 64 * NW, h3_shmem(NW, RT));
 }
-template <int NW, int RT, int TERMS> static RolloutPlan h3_agents_entry() {
+template <int NW, int RT, int TERMS> static KernelLaunch h3_agents_entry() {
     static KernelEntry e("k_rollout_mlp_h3_agents<%d, %d, %d>", NW, RT, TERMS);
     return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_h3_agents<NW, RT, TERMS>), e, 64 * NW, h3_shmem(NW, RT));
 }
-template <int H, bool VIZ> static RolloutPlan w_entry() {
+template <int H, bool VIZ> static KernelLaunch w_entry() {
     static KernelEntry e("k_rollout_mlp_w<%d, %s>", H, KernelEntry::of(VIZ));
     return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w<H, VIZ>), e, H, w_shmem(H));
 }
-template <int H> static RolloutPlan w_agents_entry() {
+template <int H> static KernelLaunch w_agents_entry() {
     static KernelEntry e("k_rollout_mlp_w_agents<%d>", H);
     return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w_agents<H>), e, H, w_shmem(H));
 }
-template <int H> static RolloutPlan w_plan(bool viz, bool agents) {
+template <int H> static KernelLaunch w_plan(bool viz, bool agents) {
     return viz ? w_entry<H, true>() : agents ? w_agents_entry<H>() : w_entry<H, false>();
 }
 
@@ -823,32 +823,32 @@ RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches
     RolloutPlan p;
     if (mlp_is_w(Q)) {  // (MPPI_MLP_FORM / MPPI_MLP_TERMS / MPPI_MLP_F32 concern the 512 x 3 and 512 x 2 shapes only)
         switch (Q.hidden) {  // (mppi_set_mlp admits only these)
-        case 64: p = w_plan<64>(viz, agents > 1); break;
-        case 128: p = w_plan<128>(viz, agents > 1); break;
-        case 256: p = w_plan<256>(viz, agents > 1); break;
-        case 512: p = w_plan<512>(viz, agents > 1); break;
+        case 64: p.k = w_plan<64>(viz, agents > 1); break;
+        case 128: p.k = w_plan<128>(viz, agents > 1); break;
+        case 256: p.k = w_plan<256>(viz, agents > 1); break;
+        case 512: p.k = w_plan<512>(viz, agents > 1); break;
         }
     } else if (viz) {  // (the f16-split kernel, whichever rollout kernel MPPI_MLP_F32 selects: both weight sets are packed)
-        p = form == H3_FORM_8x64 ? h3_entry<true, 8, 2>() : h3_entry<true, 4, 2>();
+        p.k = form == H3_FORM_8x64 ? h3_entry<true, 8, 2>() : h3_entry<true, 4, 2>();
     } else if (agents > 1) {  // several agents: the default form always (mppi_set_mlp refuses the f32-input kernel)
-        p = h3_agents_entry<8, 2, 3>();
+        p.k = h3_agents_entry<8, 2, 3>();
     } else if (!Q.use_h3) {
-        p = f32_entry();
+        p.k = f32_entry();
     } else if (form == H3_FORM_8x64) {
-        p = sw.mlp.terms == 2 ? h3_entry<false, 8, 2, 2>() : h3_entry<false, 8, 2>();
+        p.k = sw.mlp.terms == 2 ? h3_entry<false, 8, 2, 2>() : h3_entry<false, 8, 2>();
     } else {
-        p = h3_entry<false, 4, 2>();
+        p.k = h3_entry<false, 4, 2>();
     }
     p.records = mlp_blocks(P.K, MLP_M);  // every kernel: one 64-sample tile, one softmin record, per workgroup
     // viz: the samples' workgroups (when their trajectories are wanted) and one for the nominal sequence (likewise)
-    if (viz) p.grid = dim3(viz->ex ? mlp_blocks(viz->en, MLP_M) : (viz->smp ? p.records : 0) + (viz->opt ? 1 : 0));
-    else p.grid = dim3(p.records, agents);
+    if (viz) p.k.grid = dim3(viz->ex ? mlp_blocks(viz->en, MLP_M) : (viz->smp ? p.records : 0) + (viz->opt ? 1 : 0));
+    else p.k.grid = dim3(p.records, agents);
     return p;
 }
 void launch_mlp(const RolloutPlan &plan, const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz *viz, hipStream_t s) {
     const MlpViz none{};
     void *args[] = {const_cast<KParams<float> *>(&P), const_cast<MlpParams *>(&Q), &partials, const_cast<MlpViz *>(viz ? viz : &none)};
-    launch_plan(plan, args, s);  // (k_rollout_mlp and the _agents kernels take no MlpViz)
+    launch_plan(plan.k, args, s);  // (k_rollout_mlp and the _agents kernels take no MlpViz)
 }
 
 void launch_viz_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const float *u_before, const float *u_upd,
