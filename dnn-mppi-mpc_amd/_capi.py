@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 PKG = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 4  # MPPI_ABI_VERSION of include/mppi_hip.h this mirror was written against
+ABI_VERSION = 5  # MPPI_ABI_VERSION of include/mppi_hip.h this mirror was written against
 MIN_AB_ABI_VERSION = 3  # oldest library an MPPI_LIB override may point at: same mppi_config layout as now (an ABI-3 library
                         # fills the first fields of mppi_stats only: the struct grew at its end in version 4)
 LIB_PATH = os.environ.get("MPPI_LIB") or os.path.join(PKG, "lib", "libmppi_hip.so")  # MPPI_LIB: A/B a diagnostic build
@@ -66,6 +66,9 @@ PROTOTYPES = {
     "mppi_destroy": (C.c_int, [_H]),
     "mppi_set_ref_path": (C.c_int, [_H, _D, C.c_int32, C.c_int32]),
     "mppi_set_obstacles": (C.c_int, [_H, _D, C.c_int32]),
+    "mppi_set_agent_ref_path": (C.c_int, [_H, C.c_int32, _D, C.c_int32, C.c_int32]),
+    "mppi_set_agent_obstacles": (C.c_int, [_H, C.c_int32, _D, C.c_int32]),
+    "mppi_get_agent_status": (C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mppi_set_mlp": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                               C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float)),
                               C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -87,6 +87,17 @@ struct mppi_handle {
     MlpParams mlp;
     bool mlp_set = false;
     void *d_ref = nullptr, *d_obs = nullptr, *d_u = nullptr, *d_uhist = nullptr, *d_S = nullptr;
+    // Several agents: d_ref / n_ref / d_obs / n_obs above are the scene every agent shares (mppi_set_ref_path /
+    // mppi_set_obstacles); own[a] holds what mppi_set_agent_ref_path / mppi_set_agent_obstacles gave agent a instead (buffers
+    // it owns), and d_scenes is the table the batched kernels read: every agent's view, rewritten by every setter (scene_of,
+    // upload_scenes).  A single-agent handle has neither.
+    struct OwnScene {
+        void *d_ref = nullptr, *d_obs = nullptr;
+        int n_ref = 0, n_obs = 0;
+        bool has_obs = false;  // (an own set of m = 0 circles has no buffer)
+    };
+    std::vector<OwnScene> own;
+    AgentScene *d_scenes = nullptr;
     int *d_pout = nullptr;
     void *d_partials = nullptr;     // block records in the handle's precision
     double *d_w = nullptr, *d_trace = nullptr;
@@ -169,7 +180,24 @@ static double softmin_beta(const mppi_config &c) {
 }
 // The sequential index only grows: once it sits on the last waypoint every search window holds one candidate and nothing
 // can move.  index_can_move: the handle runs the kernels that resolve the index in one launch, and it has not got there.
-static bool at_path_end(const mppi_handle *h, int idx) { return idx >= h->n_ref - 1; }
+static bool at_path_end(const mppi_handle *h, int idx) { return idx >= h->n_ref - 1; }  // (sequential index: one agent)
+// Agent a's scene: what it was given for itself, else the shared one.  n_obs counts only where the handle tests collisions.
+static AgentScene scene_of(const mppi_handle *h, int a) {
+    AgentScene sc = {h->d_ref, h->d_obs, h->n_ref, h->n_obs, {0, 0}};
+    if (a < (int)h->own.size()) {
+        const mppi_handle::OwnScene &o = h->own[a];
+        if (o.d_ref) sc.ref = o.d_ref, sc.n_ref = o.n_ref;
+        if (o.has_obs) sc.obs = o.d_obs, sc.n_obs = o.n_obs;
+    }
+    if (h->cfg.obstacle_model == MPPI_OBSTACLE_NONE) sc.n_obs = 0;
+    return sc;
+}
+// some agent has obstacles: the obstacle instantiations serve and the records carry collision counts
+static bool any_obstacles(const mppi_handle *h) {
+    for (int a = 0; a < h->B; ++a)
+        if (scene_of(h, a).n_obs > 0) return true;
+    return false;
+}
 // The sequential index in one launch (look-back, LB_CAND in mppi_kernels.h) serves this handle: horizons of one 64-step pass
 // in the one-sample-per-wave layout or the two-samples-per-wave layout with one pass per workgroup, the reference's 20- / 10-
 // candidate windows, `S[k] =`, one agent, at most 512 workgroups = records (K <= 16384: configs 2 and 3).  Anything else keeps
@@ -346,6 +374,10 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         return fail(e, "hipHostMalloc(result)");
     if ((e = hipHostGetDevicePointer((void **)&h->res_mapped, h->h_res, 0)) != hipSuccess)
         return fail(e, "hipHostGetDevicePointer(result)");
+    if (B > 1) {
+        h->own.resize(B);
+        if (int rc = zeroed((void **)&h->d_scenes, B * sizeof(AgentScene), "hipMalloc(agent scenes)")) return rc;
+    }
     DevState st0;
     memset(&st0, 0, sizeof(st0));  // prev_way_point_idx = 0 (:85)
     st0.first_k = NO_TRIGGER;
@@ -368,6 +400,11 @@ extern "C" int mppi_destroy(mppi_handle *h) {
                     h->d_w,   h->d_trace, h->d_st, h->d_res, h->d_heads, h->d_heads2, h->d_hyp_slots, h->d_mlp16};
     for (void *b : bufs)
         if (b) hipFree(b);
+    for (const mppi_handle::OwnScene &o : h->own) {
+        if (o.d_ref) hipFree(o.d_ref);
+        if (o.d_obs) hipFree(o.d_obs);
+    }
+    if (h->d_scenes) hipFree(h->d_scenes);
     if (h->h_res) hipHostFree(h->h_res);
     for (int i = 0; i < 2; ++i) {
         if (h->graph_exec[i]) hipGraphExecDestroy(h->graph_exec[i]);
@@ -383,8 +420,22 @@ extern "C" int mppi_destroy(mppi_handle *h) {
     return MPPI_OK;
 }
 
-extern "C" int mppi_set_ref_path(mppi_handle *h, const double *path, int32_t n, int32_t ncols) {
-    if (!h || !path) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_ref_path: null argument");
+// The batched kernels' table (AgentScene[n_agents]), rewritten from the host's view of every agent (the caller has synchronised
+// the device).  The table is read at run time, so a cached graph (ensure_graph) replays the new scenes; what a launch carries
+// by value -- agent 0's scene and the "any agent has obstacles" decisions in KParams / FinalizeParams -- is part of the graph's key.
+static int upload_scenes(mppi_handle *h) {
+    if (!h->d_scenes) return MPPI_OK;
+    std::vector<AgentScene> tab(h->B);
+    for (int a = 0; a < h->B; ++a) tab[a] = scene_of(h, a);
+    HIPCHECK(h, hipMemcpy(h->d_scenes, tab.data(), sizeof(AgentScene) * tab.size(), hipMemcpyHostToDevice));
+    return MPPI_OK;
+}
+
+// `self.ref_path` into *d_ref / *n_ref (the shared scene's or one agent's): validated, packed to [n][4], the device idle before
+// the old buffer goes; host_copy (nullable): the packed path as the kernels see it
+static int set_path(mppi_handle *h, const char *who, const double *path, int32_t n, int32_t ncols, void **d_ref, int *n_ref,
+                    std::vector<double> *host_copy) {
+    if (!path) FAIL(h, MPPI_ERR_BAD_ARG, "%s: null argument", who);
     const int need = h->cfg.model == MPPI_MODEL_RACECAR ? 4 : 3;
     if (n < 1 || ncols < need || ncols > 4)
         FAIL(h, MPPI_ERR_SHAPE, "ref_path must be [n>=1, %d] (got [%d, %d])", need, n, ncols);
@@ -393,25 +444,29 @@ extern "C" int mppi_set_ref_path(mppi_handle *h, const double *path, int32_t n, 
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < ncols; ++j) packed[(size_t)i * 4 + j] = path[(size_t)i * ncols + j];
     HIPCHECK(h, hipDeviceSynchronize());
-    if (h->d_ref) HIPCHECK(h, hipFree(h->d_ref));
-    h->d_ref = nullptr;
-    HIPCHECK(h, hipMalloc(&h->d_ref, rsz(h) * 4 * n));
-    h->n_ref = n;
+    if (*d_ref) HIPCHECK(h, hipFree(*d_ref));
+    *d_ref = nullptr;
+    *n_ref = 0;
+    HIPCHECK(h, hipMalloc(d_ref, rsz(h) * 4 * n));
+    *n_ref = n;
     h->dev_loop_primed = false;
-    h->ref_host = packed;
-    if (!h->f64)
-        for (double &v : h->ref_host) v = (double)(float)v;
-    return upload_real(h, h->d_ref, packed.data(), packed.size());
+    if (host_copy) {
+        *host_copy = packed;
+        if (!h->f64)
+            for (double &v : *host_copy) v = (double)(float)v;
+    }
+    return upload_real(h, *d_ref, packed.data(), packed.size());
 }
 
-extern "C" int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m) {
-    if (!h || (m > 0 && !xyr)) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_obstacles: null argument");
-    if (m < 0) FAIL(h, MPPI_ERR_SHAPE, "mppi_set_obstacles: m < 0");
+// `self.obstacle_circles` into *d_obs / *n_obs, likewise
+static int set_circles(mppi_handle *h, const char *who, const double *xyr, int32_t m, void **d_obs, int *n_obs) {
+    if (m > 0 && !xyr) FAIL(h, MPPI_ERR_BAD_ARG, "%s: null argument", who);
+    if (m < 0) FAIL(h, MPPI_ERR_SHAPE, "%s: m < 0", who);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
-    if (h->d_obs) HIPCHECK(h, hipFree(h->d_obs));
-    h->d_obs = nullptr;
-    h->n_obs = m;
+    if (*d_obs) HIPCHECK(h, hipFree(*d_obs));
+    *d_obs = nullptr;
+    *n_obs = m;
     if (m == 0) return MPPI_OK;
     std::vector<double> packed((size_t)m * 4, 0.0);
     for (int i = 0; i < m; ++i) {
@@ -422,8 +477,68 @@ extern "C" int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m) 
         packed[4 * i + 1] = xyr[3 * i + 1];
         packed[4 * i + 2] = thr * thr;
     }
-    HIPCHECK(h, hipMalloc(&h->d_obs, rsz(h) * 4 * m));
-    return upload_real(h, h->d_obs, packed.data(), packed.size());
+    HIPCHECK(h, hipMalloc(d_obs, rsz(h) * 4 * m));
+    return upload_real(h, *d_obs, packed.data(), packed.size());
+}
+
+extern "C" int mppi_set_ref_path(mppi_handle *h, const double *path, int32_t n, int32_t ncols) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (int rc = set_path(h, "mppi_set_ref_path", path, n, ncols, &h->d_ref, &h->n_ref, &h->ref_host)) return rc;
+    for (mppi_handle::OwnScene &o : h->own) {  // several agents: every agent follows this path again
+        if (o.d_ref) HIPCHECK(h, hipFree(o.d_ref));
+        o.d_ref = nullptr;
+        o.n_ref = 0;
+    }
+    return upload_scenes(h);
+}
+
+extern "C" int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (int rc = set_circles(h, "mppi_set_obstacles", xyr, m, &h->d_obs, &h->n_obs)) return rc;
+    for (mppi_handle::OwnScene &o : h->own) {
+        if (o.d_obs) HIPCHECK(h, hipFree(o.d_obs));
+        o.d_obs = nullptr;
+        o.n_obs = 0;
+        o.has_obs = false;
+    }
+    return upload_scenes(h);
+}
+
+extern "C" int mppi_set_agent_ref_path(mppi_handle *h, int32_t agent, const double *path, int32_t n, int32_t ncols) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_agent_ref_path: agent %d not in [0, %d)", agent, h->B);
+    if (h->B == 1) return mppi_set_ref_path(h, path, n, ncols);
+    mppi_handle::OwnScene &o = h->own[agent];
+    if (int rc = set_path(h, "mppi_set_agent_ref_path", path, n, ncols, &o.d_ref, &o.n_ref, nullptr)) {
+        (void)upload_scenes(h);  // (a failed allocation left the agent on the shared path)
+        return rc;
+    }
+    return upload_scenes(h);
+}
+
+extern "C" int mppi_set_agent_obstacles(mppi_handle *h, int32_t agent, const double *xyr, int32_t m) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_agent_obstacles: agent %d not in [0, %d)", agent, h->B);
+    if (h->B == 1) return mppi_set_obstacles(h, xyr, m);
+    mppi_handle::OwnScene &o = h->own[agent];
+    h->dev_loop_primed = false;
+    const int rc = set_circles(h, "mppi_set_agent_obstacles", xyr, m, &o.d_obs, &o.n_obs);
+    if (rc == MPPI_OK || rc == MPPI_ERR_HIP) o.has_obs = rc == MPPI_OK;  // (refused arguments change nothing)
+    if (int rc2 = upload_scenes(h)) return rc ? rc : rc2;
+    return rc;
+}
+
+extern "C" int mppi_get_agent_status(mppi_handle *h, int32_t *idx_out, int32_t *path_end_out) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    std::vector<DevState> st(h->B);
+    HIPCHECK(h, hipMemcpy(st.data(), h->d_st, sizeof(DevState) * st.size(), hipMemcpyDeviceToHost));
+    for (int a = 0; a < h->B; ++a) {
+        if (idx_out) idx_out[a] = st[a].p;
+        if (path_end_out) path_end_out[a] = st[a].path_end;
+    }
+    return MPPI_OK;
 }
 
 // (the caller has synchronised the device: no instance is running)
@@ -595,7 +710,10 @@ extern "C" int mppi_get_u_prev(mppi_handle *h, double *u) {
 
 extern "C" int mppi_set_waypoint_idx(mppi_handle *h, int32_t idx) {
     if (!h) return MPPI_ERR_BAD_ARG;
-    if (idx < 0 || (h->n_ref > 0 && idx >= h->n_ref)) FAIL(h, MPPI_ERR_BAD_ARG, "waypoint index %d out of range", idx);
+    for (int a = 0; a < h->B; ++a) {  // (every agent's path, where it has one yet)
+        const int n = scene_of(h, a).n_ref;
+        if (idx < 0 || (n > 0 && idx >= n)) FAIL(h, MPPI_ERR_BAD_ARG, "waypoint index %d out of range", idx);
+    }
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
     for (int a = 0; a < h->B; ++a)  // (every agent of a batched handle)
@@ -665,14 +783,16 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     if (ne < 0) ne = 0;
     if (ne > c.K_global) ne = c.K_global;
     P.n_exploit = (int)ne;
-    P.n_ref = h->n_ref;
-    P.n_obs = c.obstacle_model == MPPI_OBSTACLE_NONE ? 0 : h->n_obs;
+    // (several agents: agent 0's scene here, every agent's in the table -- see KParams::scenes)
+    const AgentScene sc0 = scene_of(h, 0);
+    P.n_ref = sc0.n_ref;
+    P.n_obs = sc0.n_obs;
     P.window = c.search_window;
     P.model = kernel_model(c);
     P.accumulate = c.accumulate_stage_cost;
     P.sequential = c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL;
     P.per_rollout = c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT;
-    P.obstacle_model = P.n_obs > 0 ? c.obstacle_model : OBS_NONE;
+    P.obstacle_model = any_obstacles(h) ? c.obstacle_model : OBS_NONE;
     P.clamp_rollout = c.clamp_rollout;
     P.wrap_stage = c.wrap_yaw_stage;
     P.wrap_term = c.wrap_yaw_terminal;
@@ -710,8 +830,9 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.chol[0] = (float)l00;
     P.chol[1] = (float)l10;
     P.chol[2] = (float)l11;
-    P.ref = (const R *)h->d_ref;
-    P.obs = (const R *)h->d_obs;
+    P.ref = (const R *)sc0.ref;
+    P.obs = (const R *)sc0.obs;
+    P.scenes = h->d_scenes;
     P.u = (const R *)h->d_u;
     P.eps = noise;
     P.S = (R *)h->d_S;
@@ -752,10 +873,11 @@ static FinalizeParams make_finalize(const mppi_handle *h, int plant, const void 
     F.model = kernel_model(c);
     F.sequential = c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL;
     F.plant = plant;
-    F.n_ref = h->n_ref;
+    const AgentScene sc0 = scene_of(h, 0);
+    F.n_ref = sc0.n_ref;
     F.window = c.search_window;
     F.is_f64 = h->f64;
-    F.count_hits = c.obstacle_model != MPPI_OBSTACLE_NONE && h->n_obs > 0;
+    F.count_hits = any_obstacles(h);
     F.beta = record_beta(h);
     F.dt = c.delta_t;
     F.wheel_base = c.wheel_base;
@@ -766,7 +888,8 @@ static FinalizeParams make_finalize(const mppi_handle *h, int plant, const void 
     F.u = h->d_u;
     F.u_out = h->d_u;
     F.u_before = h->d_uhist;
-    F.ref = h->d_ref;
+    F.ref = sc0.ref;
+    F.scenes = h->d_scenes;
     F.pout = h->d_pout;
     F.st = h->d_st;
     F.st_out = h->d_st;
@@ -923,9 +1046,14 @@ static void collect_timing(mppi_handle *h) {
 
 static int check_ready(mppi_handle *h, const char *who) {
     if (!h) return MPPI_ERR_BAD_ARG;
-    if (!h->d_ref || h->n_ref < 1) FAIL(h, MPPI_ERR_STATE, "%s: ref_path has not been set", who);
-    if (h->cfg.obstacle_model != MPPI_OBSTACLE_NONE && h->n_obs > 0 && !h->d_obs)
-        FAIL(h, MPPI_ERR_STATE, "%s: obstacles not uploaded", who);
+    for (int a = 0; a < h->B; ++a) {
+        const AgentScene sc = scene_of(h, a);
+        if (!sc.ref || sc.n_ref < 1) {
+            if (h->B > 1) FAIL(h, MPPI_ERR_STATE, "%s: ref_path of agent %d has not been set", who, a);
+            FAIL(h, MPPI_ERR_STATE, "%s: ref_path has not been set", who);
+        }
+        if (sc.n_obs > 0 && !sc.obs) FAIL(h, MPPI_ERR_STATE, "%s: obstacles not uploaded", who);
+    }
     if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP && !h->mlp_set)
         FAIL(h, MPPI_ERR_STATE, "%s: mppi_set_mlp has not been called", who);
     return MPPI_OK;
@@ -1850,7 +1978,7 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
     }
     if (need_idx) {
         if (!prev_idx) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval: prev_idx is null");
-        if (*prev_idx < 0 || *prev_idx >= h->n_ref) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval: waypoint index %d out of range", *prev_idx);
+        if (*prev_idx < 0 || *prev_idx >= P.n_ref) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval: waypoint index %d out of range", *prev_idx);
         HIPCHECK(h, di.alloc(sizeof(int) * (size_t)n));
         HIPCHECK(h, dp.alloc(sizeof(int)));
         launch_eval_index<R>(P, (const R *)dx.p, nx, n, *prev_idx, update ? 1 : 0, (int *)di.p, (int *)dp.p, nullptr);

@@ -253,6 +253,17 @@ template <typename R> __device__ __forceinline__ DevState load_state(const KPara
     return sv;
 }
 
+// Several agents per launch: agent a's view of the handle's parameters -- its own path and obstacle table (AgentScene) in
+// place of ref / obs / n_ref / n_obs, resolved once at the top of the kernel (a is wave-uniform: scalar loads) in the kernel's
+// own copy of its argument, so that Rollout, stage_window, load_obstacles and the searches read P as they always did.  The
+// single-agent instantiations do not call it and compile to the code they had.
+template <typename R> __device__ __forceinline__ void agent_scene(KParams<R> &A, const AgentScene *__restrict__ scenes, int a) {
+    const AgentScene sc = scenes[a];
+    A.ref = reinterpret_cast<const R *>(sc.ref);
+    A.obs = reinterpret_cast<const R *>(sc.obs);
+    A.n_ref = sc.n_ref;
+    A.n_obs = sc.n_obs;
+}
 __device__ __forceinline__ bool round_unresolved(const DevState *st, int K) {
     const int fk = st->first_k;
     return fk != NO_TRIGGER && fk + 1 < K;

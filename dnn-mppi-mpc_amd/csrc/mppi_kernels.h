@@ -108,6 +108,18 @@ inline MergeTree merge_tree(int n, bool finalize_reads) {
     return t;
 }
 
+// One agent's scene (several agents per handle, mppi_config.n_agents > 1): its reference path and obstacle table in the
+// handle's precision and their lengths.  The handle keeps AgentScene[n_agents] in device memory and rewrites it on every
+// setter; agents that share a scene carry the same pointers.  The batched kernels read entry blockIdx.y (scalar loads) and
+// see the handle's parameters with these four fields in place of ref / obs / n_ref / n_obs (agent_scene, mppi_device.h); the
+// single-agent kernels never read the table.
+struct alignas(32) AgentScene {
+    const void *ref, *obs;  // [n_ref][4], [n_obs][4] as KParams::ref / obs
+    int n_ref, n_obs;       // (n_obs: 0 for a handle without an obstacle model)
+    int pad[2];
+};
+static_assert(sizeof(AgentScene) == 32, "AgentScene layout");
+
 template <typename R> struct KParams {
     int K, T, k_offset, noise_stream;  // noise_stream: fourth Philox counter word (of agent 0) -- kept in the first
                                        // kernel-argument fetch: the draw is the first thing a wave does
@@ -146,6 +158,12 @@ template <typename R> struct KParams {
                             // what the rollout planners read; RolloutPlan::lookback says whether the launch they picked publishes words
     unsigned lb_seq;        // this launch pair's tag (see lb_tag)
     unsigned *hyp_slots;    // [HYP_MAX_BLOCKS] one word per workgroup
+    // several agents per launch: every agent's scene (null for a single agent).  ref / obs / n_ref / n_obs above are agent
+    // 0's then -- what anything that does not read the table sees -- and obstacle_model says whether ANY agent has obstacles.
+    // Last, so that the first kernel-argument fetch keeps its layout; padded to 32 bytes, so that the arguments behind the
+    // struct keep their alignment and the compiler merges their loads as it did (the single-agent kernels' code is unchanged).
+    const AgentScene *scenes;
+    long long pad_scenes[3];
 };
 
 struct FinalizeParams {
@@ -184,6 +202,8 @@ struct FinalizeParams {
     int hyp, hyp_blocks;
     const unsigned *hyp_slots;
     unsigned lb_seq, pad_lb;
+    const AgentScene *scenes;  // see KParams: ref / n_ref above are agent 0's, count_hits says whether any agent has obstacles
+    long long pad_scenes[3];
 };
 
 // learned residual dynamics (mppi_mlp.hip): device pointers to fragment-packed weights.  Hidden width H in {64, 128, 256, 512}

@@ -70,9 +70,14 @@ __device__ __forceinline__ void x0_call(DevState *st, const R *ref, int n_ref, i
 
 template <typename R>
 __global__ __launch_bounds__(64) void k_set_state(const R *ref, int n_ref, int window, int sequential, DevState *st,
-                                                  double x0, double x1, double x2, double x3, int have_x) {
+                                                  double x0, double x1, double x2, double x3, int have_x,
+                                                  const AgentScene *scenes) {
     const int lane = threadIdx.x;
     st += blockIdx.x;  // one workgroup per agent (have_x: single agent only)
+    if (scenes) {      // several agents: each searches its own path
+        ref = reinterpret_cast<const R *>(scenes[blockIdx.x].ref);
+        n_ref = scenes[blockIdx.x].n_ref;
+    }
     if (have_x) {
         if (lane == 0) { st->x0[0] = x0; st->x0[1] = x1; st->x0[2] = x2; st->x0[3] = x3; }
     } else {
@@ -665,10 +670,11 @@ __device__ __forceinline__ void per_rollout_thread(const KParams<R> &P, int c, c
 // picked by the host while the waypoint index can still move (KParams::hyp): carrying that code costs the lean kernel
 // 0.17 us per launch in registers and LDS (A/B on one box), and at the end of the path nothing moves any more.
 template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK = false>
-__global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevState *st_pre, const KParams<R> P,
+__global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevState *st_pre, KParams<R> P,
                                                                     R *__restrict__ partials) {
     constexpr bool OBS = SPEC == 0, PLAIN = SPEC == 2;
     const int agent = MULTI ? (int)blockIdx.y : 0;
+    if constexpr (MULTI) agent_scene(P, P.scenes, agent);  // (the agent's view of P: its own path and obstacles, see AgentScene)
     __shared__ R sh_S[FUSED_WAVES];
     __shared__ R sh_e[FUSED_WAVES];
     __shared__ R sh_acc[FUSED_WAVES][128 * NCH];
@@ -819,9 +825,10 @@ constexpr int DUAL_WAVES = 16, DUAL_SAMPLES = 2 * DUAL_WAVES;
 // two samples per wave and two steps per lane: KParams::hyp; one pass, one agent) -- picked by the host while the index
 // can still move, like k_rollout_fused's HYPK.
 template <typename R, int MODEL, int SPW, bool MULTI, int SEQ, bool PLAIN, bool LB = false>
-__global__ __launch_bounds__(64 * DUAL_WAVES, (sizeof(R) == 4 && MODEL == MODEL_DIFF && SPW == 2 && (MULTI || SEQ == 1)) ? 8 : 1) void k_rollout_dual(const DevState *st_pre, const KParams<R> P,
+__global__ __launch_bounds__(64 * DUAL_WAVES, (sizeof(R) == 4 && MODEL == MODEL_DIFF && SPW == 2 && (MULTI || SEQ == 1)) ? 8 : 1) void k_rollout_dual(const DevState *st_pre, KParams<R> P,
                                                                   R *__restrict__ partials) {
     const int agent = MULTI ? (int)blockIdx.y : 0;  // several agents per launch (see k_rollout_fused)
+    if constexpr (MULTI) agent_scene(P, P.scenes, agent);
     const bool use_philox = PLAIN || P.use_philox, clamp_rollout = PLAIN || P.clamp_rollout;
     const bool wrap_stage = PLAIN ? MODEL == MODEL_RACE : (bool)P.wrap_stage, wrap_term = PLAIN ? MODEL == MODEL_RACE : (bool)P.wrap_term;
     const R *__restrict__ u_ = P.u + (size_t)agent * 2 * P.T;
@@ -1502,10 +1509,11 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, SHARE ? 8 : 1) void k_rollout_tri(
 // k_rollout_dual) -- the frozen-index `S[k] =` form then also pays one search per sample instead of one per lane and step,
 // no workgroup barrier per 32 samples and one record per workgroup: 32 batched config-2 agents 63 -> ~35 us per launch.
 template <typename R, bool MULTI, bool OBS, bool PHILOX>
-__global__ __launch_bounds__(64 * DUAL_WAVES, sizeof(R) == 4 ? 8 : 1) void k_rollout_stream(const DevState *st_pre, const KParams<R> P,
+__global__ __launch_bounds__(64 * DUAL_WAVES, sizeof(R) == 4 ? 8 : 1) void k_rollout_stream(const DevState *st_pre, KParams<R> P,
                                                                                             R *__restrict__ partials, int n_pass) {
     constexpr int ROWS = DUAL_SAMPLES;  // half-waves of the workgroup = samples in flight
     const int agent = MULTI ? (int)blockIdx.y : 0;
+    if constexpr (MULTI) agent_scene(P, P.scenes, agent);
     const R *__restrict__ u_ = P.u + (size_t)agent * 2 * P.T;
     R *__restrict__ S_ = P.S + (size_t)agent * P.K;
     __shared__ R sh_rho[ROWS];
@@ -2438,11 +2446,17 @@ __global__ __launch_bounds__(MERGE_THREADS) void k_finalize(const void *partials
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (MULTI) {  // several agents per launch: workgroup row blockIdx.y finishes agent blockIdx.y
         const int a = blockIdx.y;
+        // the agent's view of F: its own path for the next x0 call and path_end; no collision count without obstacles of its own
+        const AgentScene sc = F.scenes[a];
+        FinalizeParams Fa = F;
+        Fa.ref = sc.ref;
+        Fa.n_ref = sc.n_ref;
+        Fa.count_hits = F.count_hits && sc.n_obs > 0;
         const size_t rec = (size_t)a * F.slots * record_len(T_pre, (int)sizeof(A));
         finalize_body<A, MODE, MERGE_THREADS, NWIN>(reinterpret_cast<const A *>(partials_pre) + rec,
                                                     reinterpret_cast<const A *>(heads_pre) + (size_t)a * F.slots * 4,
                                                     st_pre + a, reinterpret_cast<const A *>(u_pre) + (size_t)a * 2 * T_pre,
-                                                    T_pre, F, smem, a);
+                                                    T_pre, Fa, smem, a);
     } else {
         finalize_body<A, MODE, MERGE_THREADS, NWIN, PLAIN, HYPK>(partials_pre, heads_pre, st_pre, u_pre, T_pre, F, smem, 0);
     }
@@ -2683,7 +2697,7 @@ template <typename R> void launch_set_state(const KParams<R> &P, const double *x
     const double z[4] = {0, 0, 0, 0};
     const double *v = x ? x : z;
     hipLaunchKernelGGL(k_set_state<R>, dim3(agents), dim3(64), 0, s, P.ref, P.n_ref, P.window, P.sequential, P.st, v[0],
-                       v[1], v[2], v[3], x ? 1 : 0);
+                       v[1], v[2], v[3], x ? 1 : 0, agents > 1 ? P.scenes : (const AgentScene *)nullptr);
 }
 
 bool fused_supported(int T) { return T <= 128; }

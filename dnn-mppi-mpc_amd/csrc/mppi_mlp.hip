@@ -704,7 +704,8 @@ constexpr int h3_ref_cap(int rt, int h) { return rt == 1 ? H3_REF_LDS_32 : h == 
 // Several agents per launch (mppi_config.n_agents > 1): workgroup row a = blockIdx.y runs agent a, which sees
 // the handle's parameters with its own nominal controls u + 2 T a, costs and waypoint outputs S / pout + K a, controller
 // state st + a (x0, x0 index, iteration), noise (Philox stream noise_stream + a, or its tensor of the caller's ring) and
-// record heads + 4 slots a -- the layout of k_rollout_fused<..., MULTI>, which k_finalize's batched path reads.  The
+// record heads + 4 slots a, its reference path and obstacle table (AgentScene) -- the layout of k_rollout_fused<..., MULTI>,
+// which k_finalize's batched path reads.  The
 // records themselves: mlp_agent_records.  The single-agent kernels never call these, so their code stays what it was.
 __device__ __forceinline__ KParams<float> mlp_agent(const KParams<float> &P, int a) {
     KParams<float> A = P;
@@ -715,6 +716,7 @@ __device__ __forceinline__ KParams<float> mlp_agent(const KParams<float> &P, int
     A.noise_stream += a;
     if (P.eps) A.eps += (size_t)a * P.K * P.T * 2;  // eps_tensor(A, iter, 0) == eps_tensor(P, iter, a)
     A.heads += (size_t)a * P.slots * 4;
+    agent_scene(A, P.scenes, a);  // its path and obstacles: mlp_stage_path's "fits in LDS" falls out per agent
     return A;
 }
 __device__ __forceinline__ float *mlp_agent_records(const KParams<float> &P, float *partials, int a) {

@@ -71,15 +71,31 @@ class Engine:
         capi.check(self.lib, self._h, rc)
 
     # -- configuration / state ----------------------------------------------------------------
-    def set_ref_path(self, path):
+    def set_ref_path(self, path, agent=None):
+        """``agent``: None sets every agent of the handle (the shared scene), an index in [0, n_agents) that agent's own path."""
         p = np.ascontiguousarray(path, dtype=np.float64)
         if p.ndim != 2:
             raise ValueError("ref_path must be 2-D")
-        self._ck(self.lib.mppi_set_ref_path(self._h, _dp(p), p.shape[0], p.shape[1]))
+        if agent is None:
+            self._ck(self.lib.mppi_set_ref_path(self._h, _dp(p), p.shape[0], p.shape[1]))
+        else:
+            self._ck(self.lib.mppi_set_agent_ref_path(self._h, int(agent), _dp(p), p.shape[0], p.shape[1]))
 
-    def set_obstacles(self, circles):
+    def set_obstacles(self, circles, agent=None):
+        """``agent``: as in `set_ref_path`; an agent given no circles collides with nothing."""
         c = np.ascontiguousarray(circles, dtype=np.float64).reshape(-1, 3)
-        self._ck(self.lib.mppi_set_obstacles(self._h, _dp(c), c.shape[0]))
+        if agent is None:
+            self._ck(self.lib.mppi_set_obstacles(self._h, _dp(c), c.shape[0]))
+        else:
+            self._ck(self.lib.mppi_set_agent_obstacles(self._h, int(agent), _dp(c), c.shape[0]))
+
+    def agent_status(self):
+        """(idx[n_agents], path_end[n_agents]): every agent's waypoint index and whether its last x0 call found the end of
+        its own path -- which agent stopped a `run_closed_loop` that raised MPPI_ERR_PATH_END."""
+        idx, end = np.zeros(self.n_agents, dtype=np.int32), np.zeros(self.n_agents, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._ck(self.lib.mppi_get_agent_status(self._h, idx.ctypes.data_as(ip), end.ctypes.data_as(ip)))
+        return idx, end.astype(bool)
 
     # the residual-model shapes the kernels serve: hidden width H x hidden layers n (512 x 3 and 512 x 2 on
     # k_rollout_mlp_h3, every other one on k_rollout_mlp_w<H, ...>)

@@ -43,12 +43,33 @@ int main(void) {
         EXPECT(mppi_set_ref_path(h, path, 2, 3) == MPPI_OK);
         EXPECT(mppi_set_ref_path(h, path, 0, 3) == MPPI_ERR_SHAPE);
         EXPECT(mppi_set_waypoint_idx(h, 5) == MPPI_ERR_BAD_ARG);
+        /* the per-agent setters on a single-agent handle: agent 0 is the plain setter, any other agent is refused */
+        double circle[3] = {0.5, 0.5, 0.1};
+        int32_t idx = -1, end = -1;
+        EXPECT(mppi_set_agent_ref_path(h, 0, path, 2, 3) == MPPI_OK);
+        EXPECT(mppi_set_agent_ref_path(h, 0, path, 2, 2) == MPPI_ERR_SHAPE);
+        EXPECT(mppi_set_agent_ref_path(h, 0, NULL, 2, 3) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_agent_ref_path(h, -1, path, 2, 3) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_agent_ref_path(h, 1, path, 2, 3) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_agent_obstacles(h, 0, circle, 1) == MPPI_OK);
+        EXPECT(mppi_set_agent_obstacles(h, 0, NULL, 0) == MPPI_OK);
+        EXPECT(mppi_set_agent_obstacles(h, 0, NULL, 1) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_agent_obstacles(h, 0, circle, -1) == MPPI_ERR_SHAPE);
+        EXPECT(mppi_set_agent_obstacles(h, 1, circle, 1) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_get_agent_status(h, &idx, NULL) == MPPI_OK && idx == 0);
+        EXPECT(mppi_get_agent_status(h, NULL, &end) == MPPI_OK);
         EXPECT(mppi_destroy(h) == MPPI_OK);
     } else {
         EXPECT(rc == MPPI_ERR_NO_DEVICE);
         EXPECT(strstr(mppi_last_error(NULL), "HIP device") != NULL || strstr(mppi_last_error(NULL), "gfx950") != NULL);
     }
     EXPECT(mppi_destroy(NULL) == MPPI_OK);
+    {
+        double path[6] = {0, 0, 0, 1, 1, 0};
+        EXPECT(mppi_set_agent_ref_path(NULL, 0, path, 2, 3) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_agent_obstacles(NULL, 0, path, 2) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_get_agent_status(NULL, NULL, NULL) == MPPI_ERR_BAD_ARG);
+    }
     EXPECT(mppi_comm_unique_id(NULL) == MPPI_ERR_BAD_ARG);
     EXPECT(mppi_get_rollout_kernel(NULL, NULL, 0) == MPPI_ERR_BAD_ARG);
     mppi_cb_config cb;

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MPPI_ABI_VERSION 4
+#define MPPI_ABI_VERSION 5
 
 typedef enum {
     MPPI_OK = 0,
@@ -120,14 +120,17 @@ typedef struct {
     double collision_penalty;    /* 1.0e10 */
     uint64_t seed;               /* Philox key for the on-device sampler */
     /* Several independent MPPI problems ("agents") in one handle and one launch per stage:
-     * same parameters, reference path and obstacles, separate state, nominal controls, waypoint index and noise.
+     * same parameters; separate state, nominal controls, waypoint index and noise; one scene -- reference path and obstacle
+     * set -- for all of them (mppi_set_ref_path / mppi_set_obstacles) or one per agent (mppi_set_agent_ref_path /
+     * mppi_set_agent_obstacles: a fleet, or one planner weighing several routes).
      * 0/1 = one agent (every entry point).  > 1: needs MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT and no sharding; the analytic
      * models T <= 128 and K <= 8192; MPPI_MODEL_DIFFDRIVE_MLP K <= 32768 (one mppi_set_mlp serves every agent, on the
      * f16-split kernels only: MPPI_MLP_F32 and weights beyond the f16 range are MPPI_ERR_UNSUPPORTED there);
      * mppi_set_state / mppi_get_state / mppi_set_u_prev / mppi_get_u_prev / mppi_get_costs then take [n_agents][...]
      * arrays and mppi_run_closed_loop advances all agents (stats: agent 0; an agent that reaches the end of its path
-     * stops the call with MPPI_ERR_PATH_END); mppi_set_waypoint_idx / mppi_set_iteration apply to every agent; the
-     * host-in-the-loop and split steps, the visualisation rollouts and the exchange are single-agent. */
+     * stops the call with MPPI_ERR_PATH_END: mppi_get_agent_status says which); mppi_set_waypoint_idx /
+     * mppi_set_iteration apply to every agent; the host-in-the-loop and split steps, the visualisation rollouts and the
+     * exchange are single-agent; the mppi_eval_* stage methods see agent 0's scene. */
     int32_t n_agents;
     /* fourth word of the sampler's Philox counter (agent a of a batched handle draws with noise_stream + a, so a
      * single-agent handle with noise_stream = a reproduces its noise) */
@@ -171,6 +174,18 @@ int mppi_destroy(mppi_handle *h);
 int mppi_set_ref_path(mppi_handle *h, const double *path, int32_t n, int32_t ncols);
 /* `self.obstacle_circles` (host, [m,3] = x,y,r) */
 int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m);
+/* The same for ONE agent of a batched handle (mppi_config.n_agents > 1): agent `agent` in [0, n_agents) -- else
+ * MPPI_ERR_BAD_ARG -- follows its own `self.ref_path` (mppi_race_car.py:267) / sees its own `self.obstacle_circles`
+ * (mppi_differential_drive_obs.py:301-313, mppi_race_car_obstacle.py:255-274); validation and packing are those of the two
+ * calls above.  On a batched handle the two calls above set EVERY agent, so a later one returns the batch to a shared scene;
+ * an agent with m = 0 beside agents with obstacles collides with nothing.  Every agent needs a path before a run
+ * (MPPI_ERR_STATE).  On a single-agent handle agent = 0 is the plain setter. */
+int mppi_set_agent_ref_path(mppi_handle *h, int32_t agent, const double *path, int32_t n, int32_t ncols);
+int mppi_set_agent_obstacles(mppi_handle *h, int32_t agent, const double *xyr, int32_t m);
+/* Per agent: `prev_way_point_idx` / `prev_waypoints_idx` (mppi_differential_drive.py:85) and whether its last x0 call found
+ * the last waypoint of ITS path (:97-99, mppi_race_car.py:62-65) -- with paths of different lengths, which agent stopped a
+ * call that returned MPPI_ERR_PATH_END.  Host int32_t[n_agents] each, either may be NULL. */
+int mppi_get_agent_status(mppi_handle *h, int32_t *idx_out, int32_t *path_end_out);
 /*
  * Weights of the residual model `MultiLayerPerceptron` (train/train_diff_mlp.py:13-36), host float arrays in the
  * checkpoint's own layout (saved_models/mlp_diff_300x100_3l.pth): input_layer.weight [H,5], .bias [H];
@@ -201,7 +216,7 @@ int mppi_set_mlp_scaled(mppi_handle *h, int32_t hidden, int32_t n_hidden, const 
  * (mppi_differential_drive.py:82,:85); host pointers */
 int mppi_set_u_prev(mppi_handle *h, const double *u);
 int mppi_get_u_prev(mppi_handle *h, double *u);
-int mppi_set_waypoint_idx(mppi_handle *h, int32_t idx);
+int mppi_set_waypoint_idx(mppi_handle *h, int32_t idx); /* every agent: idx must lie on every agent's path */
 int mppi_get_waypoint_idx(mppi_handle *h, int32_t *idx);
 
 /*
