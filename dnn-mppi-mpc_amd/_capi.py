@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 PKG = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 5  # MPPI_ABI_VERSION of include/mppi_hip.h this mirror was written against
+ABI_VERSION = 6  # MPPI_ABI_VERSION of include/mppi_hip.h this mirror was written against
 MIN_AB_ABI_VERSION = 3  # oldest library an MPPI_LIB override may point at: same mppi_config layout as now (an ABI-3 library
                         # fills the first fields of mppi_stats only: the struct grew at its end in version 4)
 LIB_PATH = os.environ.get("MPPI_LIB") or os.path.join(PKG, "lib", "libmppi_hip.so")  # MPPI_LIB: A/B a diagnostic build
@@ -76,6 +76,13 @@ PROTOTYPES = {
                                      C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float)),
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "mppi_set_agent_mlp": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float)),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mppi_set_agent_mlp_scaled": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float)),
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mppi_set_u_prev": (C.c_int, [_H, _D]),
     "mppi_get_u_prev": (C.c_int, [_H, _D]),
     "mppi_set_waypoint_idx": (C.c_int, [_H, C.c_int32]),

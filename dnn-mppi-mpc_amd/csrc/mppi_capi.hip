@@ -63,7 +63,7 @@ struct RcclUniqueId { char internal[128]; };  // ncclUniqueId (rccl.h: NCCL_UNIQ
 
 struct mppi_handle {
     mppi_config cfg;
-    Switches sw;              // the environment as mppi_create found it (sw.mlp: as the last mppi_set_mlp did)
+    Switches sw;              // the environment as mppi_create found it (sw.mlp: as the last model setter did)
     bool f64 = false;
     int nx = 3, n_ref = 0, n_obs = 0, n_blocks = 0, traj_per_block = 0;
     bool fused = false;       // rollout + softmin partial in one launch (T <= 128)
@@ -71,7 +71,7 @@ struct mppi_handle {
     int slots = 0;            // records per agent in d_partials / d_heads (the most a launch leaves + zero padding)
     void *d_partials2 = nullptr;    // what a merge launch in front of the reader leaves (merge_tree)
     void *d_heads = nullptr, *d_heads2 = nullptr;  // compact {rho, eta, eta2, 0} of d_partials / d_partials2
-    float *d_mlp = nullptr;         // packed residual-model weights (config 5)
+    float *d_mlp = nullptr;         // packed residual-model weights (config 5): the model every agent shares (mppi_set_mlp)
     unsigned short *d_mlp16 = nullptr;  // the same as f16 hi / lo planes (k_rollout_mlp_h3, k_rollout_mlp_w)
     size_t mlp_cap = 0, mlp16_cap = 0;  // their sizes in elements
     // one-launch resolution of the sequential waypoint index (LB_CAND in mppi_kernels.h)
@@ -84,8 +84,22 @@ struct mppi_handle {
     bool idx_valid = true;
     int layout = 0;  // rollout_layout(K, T): which fused rollout kernel serves this handle
     const char *rollout_kernel = "";  // RolloutPlan::name of the last rollout launch, or of the model mppi_set_mlp loaded (mppi_get_rollout_kernel)
-    MlpParams mlp;
-    bool mlp_set = false;
+    // The learned model.  mlp_shared / shared_set: the kernels' view of d_mlp / d_mlp16, what mppi_set_mlp loaded for every
+    // agent.  Several agents: own_mlp[a] holds what mppi_set_agent_mlp gave agent a instead (a buffer pair it owns, reused
+    // while large enough), and d_models is the table the batched kernels read: every agent's view, rewritten by every model
+    // setter (model_of, upload_models).  A single-agent handle has neither.  `mlp` -- what a launch carries by value and the
+    // planners read -- is agent 0's view; hidden, n_hidden and use_h3 in it are the batch's (one shape per handle).
+    MlpParams mlp = {}, mlp_shared = {};
+    bool shared_set = false;
+    struct OwnModel {
+        float *d_mlp = nullptr;
+        unsigned short *d_mlp16 = nullptr;
+        size_t cap = 0, cap16 = 0;
+        MlpParams q = {};
+        bool set = false;
+    };
+    std::vector<OwnModel> own_mlp;
+    MlpParams *d_models = nullptr;
     void *d_ref = nullptr, *d_obs = nullptr, *d_u = nullptr, *d_uhist = nullptr, *d_S = nullptr;
     // Several agents: d_ref / n_ref / d_obs / n_obs above are the scene every agent shares (mppi_set_ref_path /
     // mppi_set_obstacles); own[a] holds what mppi_set_agent_ref_path / mppi_set_agent_obstacles gave agent a instead (buffers
@@ -377,6 +391,10 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     if (B > 1) {
         h->own.resize(B);
         if (int rc = zeroed((void **)&h->d_scenes, B * sizeof(AgentScene), "hipMalloc(agent scenes)")) return rc;
+        if (c.model == MPPI_MODEL_DIFFDRIVE_MLP) {
+            h->own_mlp.resize(B);
+            if (int rc = zeroed((void **)&h->d_models, B * sizeof(MlpParams), "hipMalloc(agent models)")) return rc;
+        }
     }
     DevState st0;
     memset(&st0, 0, sizeof(st0));  // prev_way_point_idx = 0 (:85)
@@ -405,6 +423,11 @@ extern "C" int mppi_destroy(mppi_handle *h) {
         if (o.d_obs) hipFree(o.d_obs);
     }
     if (h->d_scenes) hipFree(h->d_scenes);
+    for (const mppi_handle::OwnModel &o : h->own_mlp) {
+        if (o.d_mlp) hipFree(o.d_mlp);
+        if (o.d_mlp16) hipFree(o.d_mlp16);
+    }
+    if (h->d_models) hipFree(h->d_models);
     if (h->h_res) hipHostFree(h->h_res);
     for (int i = 0; i < 2; ++i) {
         if (h->graph_exec[i]) hipGraphExecDestroy(h->graph_exec[i]);
@@ -552,17 +575,46 @@ static void drop_graph(mppi_handle *h) {
 
 #define MLP_SUPPORTED_SET "hidden H in {64, 128, 256, 512} x n_hidden in {1, 2, 3, 4}"
 
-extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, const float *w_in, const float *b_in,
-                            const float *const *w_hidden, const float *const *b_hidden, const float *w_out,
-                            const float *b_out) {
-    if (!h || !w_in || !b_in || !w_hidden || !b_hidden || !w_out || !b_out)
-        FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_mlp: null argument");
-    if (h->cfg.model != MPPI_MODEL_DIFFDRIVE_MLP) FAIL(h, MPPI_ERR_STATE, "mppi_set_mlp needs MPPI_MODEL_DIFFDRIVE_MLP");
+// Agent a's model: what it was given for itself, else the shared one
+static bool has_model(const mppi_handle *h, int a) { return (a < (int)h->own_mlp.size() && h->own_mlp[a].set) || h->shared_set; }
+static const MlpParams &model_of(const mppi_handle *h, int a) {
+    return a < (int)h->own_mlp.size() && h->own_mlp[a].set ? h->own_mlp[a].q : h->mlp_shared;
+}
+// The batched kernels' table (MlpParams[n_agents]) and the by-value copy of agent 0's entry, rewritten from the host's view of
+// every agent (the caller has synchronised the device, as for upload_scenes).  The table is read at run time, so a cached graph
+// (ensure_graph) replays the new models; its address and agent 0's entry are part of the graph's key.
+static int upload_models(mppi_handle *h) {
+    if (has_model(h, 0)) h->mlp = model_of(h, 0);
+    if (!h->d_models) return MPPI_OK;
+    std::vector<MlpParams> tab(h->B);
+    for (int a = 0; a < h->B; ++a) tab[a] = has_model(h, a) ? model_of(h, a) : MlpParams{};
+    HIPCHECK(h, hipMemcpy(h->d_models, tab.data(), sizeof(MlpParams) * tab.size(), hipMemcpyHostToDevice));
+    return MPPI_OK;
+}
+
+// A model as the setters hold it before the handle is touched: both packings on the host and MlpParams with offsets into
+// them where the device pointers go (place_mlp)
+struct HostMlp {
+    std::vector<float> f32;            // f32 fragment order (k_rollout_mlp, 512 only) + the biases and the output layer every kernel reads
+    std::vector<unsigned short> f16;   // the same weights as f16 (hi, lo) planes for the split kernels
+    size_t o_win = 0, o_bin = 0, o_wh[MLP_MAX_HIDDEN], o_bh[MLP_MAX_HIDDEN], o_wo = 0, n_in16 = 0, n_h16 = 0;
+    MlpParams q = {};                  // b_out, use_h3, in_gain / in_bias, shape
+    double wmax = 0.0;
+    bool f16_range = true;
+    Switches sw;
+};
+
+// Validation and packing of one model for `who` (any model setter): nothing in the handle changes (but its error text).
+// read_switches is consulted here and nowhere else in the model setters.
+static int pack_mlp(mppi_handle *h, const char *who, int32_t hidden, int32_t n_hidden, const float *w_in, const float *b_in,
+                    const float *const *w_hidden, const float *const *b_hidden, const float *w_out, const float *b_out, HostMlp *m) {
+    if (!h || !w_in || !b_in || !w_hidden || !b_hidden || !w_out || !b_out) FAIL(h, MPPI_ERR_BAD_ARG, "%s: null argument", who);
+    if (h->cfg.model != MPPI_MODEL_DIFFDRIVE_MLP) FAIL(h, MPPI_ERR_STATE, "%s needs MPPI_MODEL_DIFFDRIVE_MLP", who);
     if (!mlp_shape_supported(hidden, n_hidden))
-        FAIL(h, MPPI_ERR_SHAPE, "mppi_set_mlp: Linear(5,H) -> n x [Linear(H,H), tanh] -> Linear(H,3) is built for " MLP_SUPPORTED_SET
-                                " (got hidden = %d, n = %d)", hidden, n_hidden);
+        FAIL(h, MPPI_ERR_SHAPE, "%s: Linear(5,H) -> n x [Linear(H,H), tanh] -> Linear(H,3) is built for " MLP_SUPPORTED_SET
+                                " (got hidden = %d, n = %d)", who, hidden, n_hidden);
     for (int l = 0; l < n_hidden; ++l)
-        if (!w_hidden[l] || !b_hidden[l]) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_mlp: null hidden layer %d", l);
+        if (!w_hidden[l] || !b_hidden[l]) FAIL(h, MPPI_ERR_BAD_ARG, "%s: null hidden layer %d", who, l);
     const int H = hidden;
     const bool h3_shape = mlp_shape_is_h3(H, n_hidden);  // 512 x 3, 512 x 2: k_rollout_mlp_h3 / k_rollout_mlp; else k_rollout_mlp_w
     // The split kernels carry every WEIGHT as two f16 numbers: one beyond the f16 range (65504; e.g. W_in / in_scale with a
@@ -575,71 +627,47 @@ extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, co
     for (int l = 0; l < n_hidden; ++l)
         for (size_t i = 0; i < (size_t)H * H; ++i) wmax = fmax(wmax, fabs((double)w_hidden[l][i]));
     const bool f16_range = wmax <= 65504.0;  // (false for NaN too)
-    const Switches sw = read_switches();     // (MPPI_MLP_F32 / _TERMS / _FORM hold for this model until the next mppi_set_mlp)
+    m->wmax = wmax;
+    m->f16_range = f16_range;
+    m->sw = read_switches();  // (MPPI_MLP_F32 / _TERMS / _FORM hold for this model until the next model setter)
+    const Switches &sw = m->sw;
     if (!h3_shape && !f16_range)
-        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: max |weight| = %.4g exceeds the f16 range, and only the 512 x 3 and 512 x 2 "
-                                      "models have an f32-input kernel to serve that (got hidden = %d, n = %d)", wmax, H, n_hidden);
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: max |weight| = %.4g exceeds the f16 range, and only the 512 x 3 and 512 x 2 "
+                                      "models have an f32-input kernel to serve that (got hidden = %d, n = %d)", who, wmax, H, n_hidden);
     if (!h3_shape && sw.mlp.f32)
-        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: MPPI_MLP_F32 is set, and the f32-input kernel serves only the 512 x 3 and "
-                                      "512 x 2 models (got hidden = %d, n = %d)", H, n_hidden);
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: MPPI_MLP_F32 is set, and the f32-input kernel serves only the 512 x 3 and "
+                                      "512 x 2 models (got hidden = %d, n = %d)", who, H, n_hidden);
     // several agents per handle run the split kernels only (k_rollout_mlp_h3_agents, k_rollout_mlp_w_agents)
     if (h->B > 1 && !f16_range)
-        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: max |weight| = %.4g exceeds the f16 range, and the f32-input kernel that "
-                                      "serves such a model runs one agent per handle (n_agents = %d)", wmax, h->B);
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: max |weight| = %.4g exceeds the f16 range, and the f32-input kernel that "
+                                      "serves such a model runs one agent per handle (n_agents = %d)", who, wmax, h->B);
     if (h->B > 1 && sw.mlp.f32)
-        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_mlp: MPPI_MLP_F32 is set, and the f32-input kernel runs one agent per handle "
-                                      "(n_agents = %d)", h->B);
-    HIPCHECK(h, hipSetDevice(h->cfg.device));
-    HIPCHECK(h, hipDeviceSynchronize());
-    // A cached closed-loop graph (ensure_graph) holds the previous model's MlpParams -- device pointers into the buffers
-    // below, which may now move or be repacked for another shape: it is dropped here, before anything changes.
-    drop_graph(h);
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: MPPI_MLP_F32 is set, and the f32-input kernel runs one agent per handle "
+                                      "(n_agents = %d)", who, h->B);
     const int CT = H / 32;  // column tiles of 32 outputs
-    // f32 fragment order (k_rollout_mlp, 512 only) plus the biases and the output layer that every kernel reads
     const size_t n_in = (size_t)CT * 1 * 64 * 4, n_h = (size_t)CT * (H / 8) * 64 * 4;
     const size_t total = n_in + H + MLP_MAX_HIDDEN * (n_h + H) + 3 * (size_t)H;
-    std::vector<float> host(total);
+    std::vector<float> &host = m->f32;
+    host.assign(total, 0.f);
     size_t o = 0;
-    const size_t o_win = o; pack_linear(w_in, 5, host.data() + o, H); o += n_in;
-    const size_t o_bin = o; memcpy(host.data() + o, b_in, H * sizeof(float)); o += H;
-    size_t o_wh[MLP_MAX_HIDDEN], o_bh[MLP_MAX_HIDDEN];
+    m->o_win = o; pack_linear(w_in, 5, host.data() + o, H); o += n_in;
+    m->o_bin = o; memcpy(host.data() + o, b_in, H * sizeof(float)); o += H;
     for (int l = 0; l < MLP_MAX_HIDDEN; ++l) {  // (a shallower model leaves the last slots unused)
-        o_wh[l] = o; o_bh[l] = o + n_h;
+        m->o_wh[l] = o; m->o_bh[l] = o + n_h;
         if (l < n_hidden) {
             pack_linear(w_hidden[l], H, host.data() + o, H);
             memcpy(host.data() + o + n_h, b_hidden[l], H * sizeof(float));
         }
         o += n_h + H;
     }
-    const size_t o_wo = o; memcpy(host.data() + o, w_out, 3 * (size_t)H * sizeof(float)); o += 3 * (size_t)H;
-    // (a later call may load a larger model: the buffers grow to it)
-    if (h->d_mlp && h->mlp_cap < total) { HIPCHECK(h, hipFree(h->d_mlp)); h->d_mlp = nullptr; }
-    if (!h->d_mlp) { HIPCHECK(h, hipMalloc((void **)&h->d_mlp, total * sizeof(float))); h->mlp_cap = total; }
-    HIPCHECK(h, hipMemcpy(h->d_mlp, host.data(), total * sizeof(float), hipMemcpyHostToDevice));
-    h->mlp.w_in = h->d_mlp + o_win;
-    h->mlp.b_in = h->d_mlp + o_bin;
-    for (int l = 0; l < MLP_MAX_HIDDEN; ++l) { h->mlp.w_h[l] = h->d_mlp + o_wh[l]; h->mlp.b_h[l] = h->d_mlp + o_bh[l]; }
-    h->mlp.w_out = h->d_mlp + o_wo;
-    for (int i = 0; i < 3; ++i) h->mlp.b_out[i] = b_out[i];
-    {   // the same weights as f16 (hi, lo) planes for the split kernels
-        const size_t n_in16 = (size_t)2 * CT * 1 * 64 * 8, n_h16 = (size_t)2 * CT * (H / 16) * 64 * 8;
-        const size_t tot16 = n_in16 + MLP_MAX_HIDDEN * n_h16;
-        std::vector<unsigned short> h16(tot16);
-        pack_linear_h3(w_in, 5, h16.data(), H);
-        for (int l = 0; l < n_hidden; ++l) pack_linear_h3(w_hidden[l], H, h16.data() + n_in16 + (size_t)l * n_h16, H);
-        if (h->d_mlp16 && h->mlp16_cap < tot16) { HIPCHECK(h, hipFree(h->d_mlp16)); h->d_mlp16 = nullptr; }
-        if (!h->d_mlp16) { HIPCHECK(h, hipMalloc((void **)&h->d_mlp16, tot16 * sizeof(unsigned short))); h->mlp16_cap = tot16; }
-        HIPCHECK(h, hipMemcpy(h->d_mlp16, h16.data(), tot16 * sizeof(unsigned short), hipMemcpyHostToDevice));
-        h->mlp.h3_w_in = h->d_mlp16;
-        for (int l = 0; l < MLP_MAX_HIDDEN; ++l) h->mlp.h3_w_h[l] = h->d_mlp16 + n_in16 + (size_t)l * n_h16;
-        h->mlp.use_h3 = sw.mlp.f32 ? 0 : 1;
-        if (!f16_range) {  // (512 x 3 / 512 x 2 only: refused above otherwise)
-            h->mlp.use_h3 = 0;
-            char b[256];
-            snprintf(b, sizeof(b), "mppi_set_mlp: max |weight| = %.4g exceeds the f16 range: the f32-input MFMA kernel serves this model", wmax);
-            h->err = b;
-        }
-    }
+    m->o_wo = o; memcpy(host.data() + o, w_out, 3 * (size_t)H * sizeof(float)); o += 3 * (size_t)H;
+    m->n_in16 = (size_t)2 * CT * 1 * 64 * 8;
+    m->n_h16 = (size_t)2 * CT * (H / 16) * 64 * 8;
+    m->f16.assign(m->n_in16 + MLP_MAX_HIDDEN * m->n_h16, 0);
+    pack_linear_h3(w_in, 5, m->f16.data(), H);
+    for (int l = 0; l < n_hidden; ++l) pack_linear_h3(w_hidden[l], H, m->f16.data() + m->n_in16 + (size_t)l * m->n_h16, H);
+    for (int i = 0; i < 3; ++i) m->q.b_out[i] = b_out[i];
+    m->q.use_h3 = sw.mlp.f32 || !f16_range ? 0 : 1;  // (!f16_range: 512 x 3 / 512 x 2 on one agent only, refused above otherwise)
     {   // bounds the split kernel scales the first layer's output with: |W_in z + b_in|_inf <= in_gain |z|_inf + in_bias
         double gain = 0.0, bias = 0.0;
         for (int n = 0; n < H; ++n) {
@@ -648,22 +676,113 @@ extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, co
             gain = fmax(gain, row);
             bias = fmax(bias, fabs((double)b_in[n]));
         }
-        h->mlp.in_gain = (float)(gain * (1.0 + 1e-6));
-        h->mlp.in_bias = (float)(bias * (1.0 + 1e-6));
+        m->q.in_gain = (float)(gain * (1.0 + 1e-6));
+        m->q.in_bias = (float)(bias * (1.0 + 1e-6));
     }
-    h->mlp.n_hidden = n_hidden;
-    h->mlp.hidden = H;
-    h->sw.mlp = sw.mlp;
-    // the rollout kernel that serves this model: its name before the first launch already
-    h->rollout_kernel = plan_mlp(make_params<float>(h, nullptr), h->mlp, h->sw).k.name;
-    h->mlp_set = true;
+    m->q.n_hidden = n_hidden;
+    m->q.hidden = H;
     return MPPI_OK;
 }
 
-extern "C" int mppi_set_mlp_scaled(mppi_handle *h, int32_t hidden, int32_t n_hidden, const float *w_in, const float *b_in,
-                                   const float *const *w_hidden, const float *const *b_hidden, const float *w_out,
-                                   const float *b_out, const double *in_mean, const double *in_scale, const double *out_mean,
-                                   const double *out_scale) {
+// A packed model into a buffer pair (the shared one or an agent's own; grown when too small -- the new buffers are
+// allocated before the old ones go, so a failed allocation leaves the pair and *q as they were) and its view into *q.
+// The caller has synchronised the device.
+static int place_mlp(mppi_handle *h, const HostMlp &m, float **d, size_t *cap, unsigned short **d16, size_t *cap16, MlpParams *q) {
+    float *nd = nullptr;
+    unsigned short *nd16 = nullptr;
+    if (!*d || *cap < m.f32.size()) HIPCHECK(h, hipMalloc((void **)&nd, m.f32.size() * sizeof(float)));
+    if (!*d16 || *cap16 < m.f16.size()) {
+        const hipError_t e = hipMalloc((void **)&nd16, m.f16.size() * sizeof(unsigned short));
+        if (e != hipSuccess) {
+            if (nd) (void)hipFree(nd);
+            FAIL(h, MPPI_ERR_HIP, "hipMalloc(model) failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (nd) {
+        if (*d) (void)hipFree(*d);
+        *d = nd;
+        *cap = m.f32.size();
+    }
+    if (nd16) {
+        if (*d16) (void)hipFree(*d16);
+        *d16 = nd16;
+        *cap16 = m.f16.size();
+    }
+    HIPCHECK(h, hipMemcpy(*d, m.f32.data(), m.f32.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHECK(h, hipMemcpy(*d16, m.f16.data(), m.f16.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+    *q = m.q;
+    q->w_in = *d + m.o_win;
+    q->b_in = *d + m.o_bin;
+    for (int l = 0; l < MLP_MAX_HIDDEN; ++l) { q->w_h[l] = *d + m.o_wh[l]; q->b_h[l] = *d + m.o_bh[l]; }
+    q->w_out = *d + m.o_wo;
+    q->h3_w_in = *d16;
+    for (int l = 0; l < MLP_MAX_HIDDEN; ++l) q->h3_w_h[l] = *d16 + m.n_in16 + (size_t)l * m.n_h16;
+    return MPPI_OK;
+}
+
+// Every model setter behind its argument checks.  agent < 0: the model of every agent (mppi_set_mlp) -- the agents' own
+// copies are released; else agent's own model on a batched handle.
+static int set_model(mppi_handle *h, const char *who, int agent, const HostMlp &m) {
+    if (agent >= 0)  // one launch is one instantiation: one shape per batch
+        for (int a = 0; a < h->B; ++a)
+            if (a != agent && has_model(h, a) && (model_of(h, a).hidden != m.q.hidden || model_of(h, a).n_hidden != m.q.n_hidden))
+                FAIL(h, MPPI_ERR_SHAPE, "%s: a %d x %d model for agent %d beside the %d x %d model of agent %d: the agents of a handle "
+                                        "share one shape (mppi_set_mlp changes it for all of them)", who, m.q.hidden, m.q.n_hidden,
+                     agent, model_of(h, a).hidden, model_of(h, a).n_hidden, a);
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    if (agent < 0) {
+        // A cached closed-loop graph (ensure_graph) holds the previous model's MlpParams -- device pointers into the buffers
+        // below, which may now move or be repacked for another shape: it is dropped here, before anything changes.
+        drop_graph(h);
+        if (int rc = place_mlp(h, m, &h->d_mlp, &h->mlp_cap, &h->d_mlp16, &h->mlp16_cap, &h->mlp_shared)) return rc;
+        h->shared_set = true;
+        for (mppi_handle::OwnModel &o : h->own_mlp) {  // several agents: every agent runs this model again
+            if (o.d_mlp) (void)hipFree(o.d_mlp);
+            if (o.d_mlp16) (void)hipFree(o.d_mlp16);
+            o = mppi_handle::OwnModel{};
+        }
+    } else {
+        mppi_handle::OwnModel &o = h->own_mlp[agent];
+        if (int rc = place_mlp(h, m, &o.d_mlp, &o.cap, &o.d_mlp16, &o.cap16, &o.q)) return rc;
+        o.set = true;
+    }
+    h->sw.mlp = m.sw.mlp;
+    if (int rc = upload_models(h)) return rc;
+    if (!m.f16_range) {  // (512 x 3 / 512 x 2 on a single-agent handle only: refused by pack_mlp otherwise)
+        char b[256];
+        snprintf(b, sizeof(b), "%s: max |weight| = %.4g exceeds the f16 range: the f32-input MFMA kernel serves this model", who, m.wmax);
+        h->err = b;
+    }
+    // the rollout kernel that serves this model: its name before the first launch already
+    h->rollout_kernel = plan_mlp(make_params<float>(h, nullptr), has_model(h, 0) ? h->mlp : m.q, h->sw).k.name;
+    return MPPI_OK;
+}
+
+extern "C" int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, const float *w_in, const float *b_in,
+                            const float *const *w_hidden, const float *const *b_hidden, const float *w_out,
+                            const float *b_out) {
+    HostMlp m;
+    if (int rc = pack_mlp(h, "mppi_set_mlp", hidden, n_hidden, w_in, b_in, w_hidden, b_hidden, w_out, b_out, &m)) return rc;
+    return set_model(h, "mppi_set_mlp", -1, m);
+}
+
+extern "C" int mppi_set_agent_mlp(mppi_handle *h, int32_t agent, int32_t hidden, int32_t n_hidden, const float *w_in,
+                                  const float *b_in, const float *const *w_hidden, const float *const *b_hidden,
+                                  const float *w_out, const float *b_out) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_agent_mlp: agent %d not in [0, %d)", agent, h->B);
+    if (h->B == 1) return mppi_set_mlp(h, hidden, n_hidden, w_in, b_in, w_hidden, b_hidden, w_out, b_out);
+    HostMlp m;
+    if (int rc = pack_mlp(h, "mppi_set_agent_mlp", hidden, n_hidden, w_in, b_in, w_hidden, b_hidden, w_out, b_out, &m)) return rc;
+    return set_model(h, "mppi_set_agent_mlp", agent, m);
+}
+
+// The StandardScaler statistics folded into the first and the last Linear (include/mppi_hip.h), then the plain setter:
+// agent < 0 mppi_set_mlp, else mppi_set_agent_mlp
+static int set_mlp_scaled(mppi_handle *h, int agent, int32_t hidden, int32_t n_hidden, const float *w_in, const float *b_in,
+                          const float *const *w_hidden, const float *const *b_hidden, const float *w_out, const float *b_out,
+                          const double *in_mean, const double *in_scale, const double *out_mean, const double *out_scale) {
     if (!h || !w_in || !b_in || !w_out || !b_out) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_mlp_scaled: null argument");
     if ((in_mean == nullptr) != (in_scale == nullptr) || (out_mean == nullptr) != (out_scale == nullptr))
         FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_mlp_scaled: a mean without its scale (or the reverse)");
@@ -691,7 +810,24 @@ extern "C" int mppi_set_mlp_scaled(mppi_handle *h, int32_t hidden, int32_t n_hid
             bo[j] = (float)((double)b_out[j] * out_scale[j] + out_mean[j]);
         }
     }
+    if (agent >= 0) return mppi_set_agent_mlp(h, agent, hidden, n_hidden, wi.data(), bi.data(), w_hidden, b_hidden, wo.data(), bo.data());
     return mppi_set_mlp(h, hidden, n_hidden, wi.data(), bi.data(), w_hidden, b_hidden, wo.data(), bo.data());
+}
+
+extern "C" int mppi_set_mlp_scaled(mppi_handle *h, int32_t hidden, int32_t n_hidden, const float *w_in, const float *b_in,
+                                   const float *const *w_hidden, const float *const *b_hidden, const float *w_out,
+                                   const float *b_out, const double *in_mean, const double *in_scale, const double *out_mean,
+                                   const double *out_scale) {
+    return set_mlp_scaled(h, -1, hidden, n_hidden, w_in, b_in, w_hidden, b_hidden, w_out, b_out, in_mean, in_scale, out_mean, out_scale);
+}
+
+extern "C" int mppi_set_agent_mlp_scaled(mppi_handle *h, int32_t agent, int32_t hidden, int32_t n_hidden, const float *w_in,
+                                         const float *b_in, const float *const *w_hidden, const float *const *b_hidden,
+                                         const float *w_out, const float *b_out, const double *in_mean, const double *in_scale,
+                                         const double *out_mean, const double *out_scale) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_agent_mlp_scaled: agent %d not in [0, %d)", agent, h->B);
+    return set_mlp_scaled(h, agent, hidden, n_hidden, w_in, b_in, w_hidden, b_hidden, w_out, b_out, in_mean, in_scale, out_mean, out_scale);
 }
 
 extern "C" int mppi_set_u_prev(mppi_handle *h, const double *u) {
@@ -987,7 +1123,7 @@ template <typename R> static void launch_records(mppi_handle *h, const SlotPlan 
     for (int rep = 0; rep < h->rollout_repeats; ++rep) {
         if constexpr (sizeof(R) == 4)
             if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) {
-                launch_mlp(sp.front, P, h->mlp, h->d_partials, nullptr, s);
+                launch_mlp(sp.front, P, h->mlp, h->d_models, h->d_partials, nullptr, s);
                 continue;
             }
         launch_rollout<R>(sp.front, P, h->d_partials, s);
@@ -1054,8 +1190,12 @@ static int check_ready(mppi_handle *h, const char *who) {
         }
         if (sc.n_obs > 0 && !sc.obs) FAIL(h, MPPI_ERR_STATE, "%s: obstacles not uploaded", who);
     }
-    if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP && !h->mlp_set)
-        FAIL(h, MPPI_ERR_STATE, "%s: mppi_set_mlp has not been called", who);
+    if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP)
+        for (int a = 0; a < h->B; ++a)
+            if (!has_model(h, a)) {
+                if (h->B > 1) FAIL(h, MPPI_ERR_STATE, "%s: agent %d has no model (mppi_set_mlp / mppi_set_agent_mlp)", who, a);
+                FAIL(h, MPPI_ERR_STATE, "%s: mppi_set_mlp has not been called", who);
+            }
     return MPPI_OK;
 }
 
@@ -1712,13 +1852,15 @@ static hipError_t capture_slots(mppi_handle *h, const SlotPlan &sp, const KParam
 
 template <typename R>
 static bool ensure_graph(mppi_handle *h, const SlotPlan &sp, const KParams<R> &P, const FinalizeParams &F) {
-    // (the learned model's parameters too: its launches carry MlpParams -- weight pointers, shape, output bias -- by value)
-    std::vector<char> key(sizeof(P) + sizeof(F) + 2 * sizeof(int) + sizeof(MlpParams));
+    // (the learned model's parameters too: its launches carry MlpParams -- weight pointers, shape, output bias -- by value,
+    // agent 0's; a batched launch carries the address of the agents' table instead, whose entries a replay reads afresh)
+    std::vector<char> key(sizeof(P) + sizeof(F) + 2 * sizeof(int) + sizeof(MlpParams) + sizeof(h->d_models));
     memcpy(key.data(), &P, sizeof(P));
     memcpy(key.data() + sizeof(P), &F, sizeof(F));
     const int tail[2] = {h->rollout_repeats, (int)sizeof(R)};
     memcpy(key.data() + sizeof(P) + sizeof(F), tail, sizeof(tail));
     memcpy(key.data() + sizeof(P) + sizeof(F) + sizeof(tail), &h->mlp, sizeof(MlpParams));
+    memcpy(key.data() + sizeof(P) + sizeof(F) + sizeof(tail) + sizeof(MlpParams), &h->d_models, sizeof(h->d_models));
     if (h->graph_exec[0] && key == h->graph_key) return true;
     if (h->sw.graph_verbose) fprintf(stderr, "[mppi] capturing a graph of %d iterations\n", GRAPH_SLOTS);
     for (int i = 0; i < 2; ++i) {

@@ -371,7 +371,8 @@ int reduce_blocks(int K, int traj_per_block);
 // that launch: the rollout (viz null; `records` per agent), the visualisation rollouts and the batched transition
 struct MlpViz;
 RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const MlpViz *viz = nullptr);
-void launch_mlp(const RolloutPlan &plan, const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz *viz, hipStream_t s);
+void launch_mlp(const RolloutPlan &plan, const KParams<float> &P, const MlpParams &Q, const MlpParams *models, void *partials,
+                const MlpViz *viz, hipStream_t s);
 // the visualisation rollouts (mppi_differential_drive.py:144-159) with the learned model: opt [T][3], smp [K][T][3] (either
 // may be null); u_before / u_upd: the nominal controls before the update and the updated, unshifted ones
 void launch_viz_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const float *u_before, const float *u_upd,

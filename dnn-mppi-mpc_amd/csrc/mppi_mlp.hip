@@ -719,6 +719,15 @@ __device__ __forceinline__ KParams<float> mlp_agent(const KParams<float> &P, int
     agent_scene(A, P.scenes, a);  // its path and obstacles: mlp_stage_path's "fits in LDS" falls out per agent
     return A;
 }
+// Agent a's entry of the handle's model table (MlpParams[n_agents], mppi_set_agent_mlp), seen as CONSTANT memory: the host
+// rewrites the table only between launches, the index is uniform over the workgroup, so every field arrives by a scalar load
+// exactly as a field of the by-value kernel argument does (the kernel-argument segment is the same address space) -- and the
+// weight pointers read from it are known to be global addresses, as kernel-argument pointers are (read through a generic
+// pointer to the table they would be generic themselves and the weight stream would turn into flat loads, which wait on
+// the LDS counter too).  A reference, not a copy: the layers index w_h / b_h by a run-time l, and a private copy of the
+// struct would live in scratch.
+using MlpParamsConst = const __attribute__((address_space(4))) MlpParams;
+__device__ __forceinline__ MlpParamsConst &mlp_agent_model(const MlpParams *models, int a) { return ((MlpParamsConst *)models)[a]; }
 __device__ __forceinline__ float *mlp_agent_records(const KParams<float> &P, float *partials, int a) {
     return partials + (size_t)a * P.slots * record_len(P.T, 4);
 }
@@ -728,12 +737,16 @@ __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3(con
                                                                float *__restrict__ partials, const MlpViz V) {
 #include "mppi_mlp_h3_body.h"
 }
-// several agents per launch, agent = blockIdx.y (grid (mlp_blocks(K, 64), n_agents)); no visualisation form
+// several agents per launch, agent = blockIdx.y (grid (mlp_blocks(K, 64), n_agents)); no visualisation form.  `models`: every
+// agent's MlpParams (its own weight buffers or the shared ones; one shape for all, mppi_set_agent_mlp): `Q` is this
+// agent's entry (mlp_agent_model) where the single-agent kernel has its by-value argument
 template <int NW, int RT, int TERMS>
-__global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3_agents(const KParams<float> P_all, const MlpParams Q,
+__global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3_agents(const KParams<float> P_all,
+                                                                      const MlpParams *__restrict__ models,
                                                                       float *__restrict__ partials_all) {
     constexpr bool VIZ = false;
     const KParams<float> P = mlp_agent(P_all, (int)blockIdx.y);
+    MlpParamsConst &Q = mlp_agent_model(models, (int)blockIdx.y);
     float *__restrict__ partials = mlp_agent_records(P_all, partials_all, (int)blockIdx.y);
     const MlpViz V{};
 #include "mppi_mlp_h3_body.h"
@@ -754,10 +767,12 @@ __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w(const KPa
 }
 // several agents per launch (see k_rollout_mlp_h3_agents)
 template <int H>
-__global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_agents(const KParams<float> P_all, const MlpParams Q,
+__global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_agents(const KParams<float> P_all,
+                                                                            const MlpParams *__restrict__ models,
                                                                             float *__restrict__ partials_all) {
     constexpr bool VIZ = false;
     const KParams<float> P = mlp_agent(P_all, (int)blockIdx.y);
+    MlpParamsConst &Q = mlp_agent_model(models, (int)blockIdx.y);
     float *__restrict__ partials = mlp_agent_records(P_all, partials_all, (int)blockIdx.y);
     const MlpViz V{};
 #include "mppi_mlp_w_body.h"
@@ -847,9 +862,14 @@ RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches
     else p.k.grid = dim3(p.records, agents);
     return p;
 }
-void launch_mlp(const RolloutPlan &plan, const KParams<float> &P, const MlpParams &Q, void *partials, const MlpViz *viz, hipStream_t s) {
+// `models`: the handle's device table MlpParams[n_agents] -- what the `agents` branch of plan_mlp (grid.y = the agents) takes
+// in place of Q; every other kernel carries Q by value
+void launch_mlp(const RolloutPlan &plan, const KParams<float> &P, const MlpParams &Q, const MlpParams *models, void *partials,
+                const MlpViz *viz, hipStream_t s) {
     const MlpViz none{};
-    void *args[] = {const_cast<KParams<float> *>(&P), const_cast<MlpParams *>(&Q), &partials, const_cast<MlpViz *>(viz ? viz : &none)};
+    const bool agents = plan.k.grid.y > 1;
+    void *args[] = {const_cast<KParams<float> *>(&P), agents ? (void *)&models : (void *)const_cast<MlpParams *>(&Q), &partials,
+                    const_cast<MlpViz *>(viz ? viz : &none)};
     launch_plan(plan.k, args, s);  // (k_rollout_mlp and the _agents kernels take no MlpViz)
 }
 
@@ -857,13 +877,13 @@ void launch_viz_mlp(const KParams<float> &P, const MlpParams &Q, const Switches 
                     long long iter, float *opt, float *smp, hipStream_t s) {
     if (!opt && !smp) return;
     const MlpViz v{u_before, u_upd, opt, smp, (unsigned)iter, smp ? 0 : mlp_blocks(P.K, MLP_M), nullptr, nullptr, nullptr, 0};
-    launch_mlp(plan_mlp(P, Q, sw, &v), P, Q, nullptr, &v, s);
+    launch_mlp(plan_mlp(P, Q, sw, &v), P, Q, nullptr, nullptr, &v, s);
 }
 
 void launch_eval_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const float *x, const float *v, int n,
                      float *out, hipStream_t s) {
     const MlpViz e{nullptr, nullptr, nullptr, nullptr, 0u, 0, x, v, out, n};
-    launch_mlp(plan_mlp(P, Q, sw, &e), P, Q, nullptr, &e, s);
+    launch_mlp(plan_mlp(P, Q, sw, &e), P, Q, nullptr, nullptr, &e, s);
 }
 
 // Host-side packing of a torch Linear weight [n_out][n_in] (n_out a multiple of 32) into fragment order:

@@ -101,7 +101,7 @@ class Engine:
     # k_rollout_mlp_h3, every other one on k_rollout_mlp_w<H, ...>)
     SUPPORTED_MLP = {"hidden": (64, 128, 256, 512), "n_hidden": (1, 2, 3, 4)}
 
-    def set_mlp(self, weights, scalers=None):
+    def set_mlp(self, weights, scalers=None, agent=None):
         """Residual-model weights in the checkpoint's key layout (``state_dict`` of the reference's
         ``MultiLayerPerceptron``, train/train_diff_mlp.py:13-36); tensors or arrays.  Linear(5, H) -> n x [Linear(H, H),
         tanh] -> Linear(H, 3) with H in {64, 128, 256, 512} and n in {1, 2, 3, 4} (`SUPPORTED_MLP`); any other shape is a
@@ -112,10 +112,17 @@ class Engine:
         (3).  The affine maps are folded into the first and last Linear on the host (`mppi_set_mlp_scaled`), so the kernel
         is unchanged: MLP((z - m_in) / s_in) * s_out + m_out.
 
-        A handle of ``n_agents`` > 1 (frozen or per-rollout index, K <= 32768) runs every agent with this one model in one
-        launch per stage (k_rollout_mlp_h3_agents / k_rollout_mlp_w_agents); there a model only the f32-input kernel can
-        serve (512 x 2 / 512 x 3 with weights beyond the f16 range, or MPPI_MLP_F32=1) is refused (``MppiError``,
-        MPPI_ERR_UNSUPPORTED)."""
+        A handle of ``n_agents`` > 1 (frozen or per-rollout index, K <= 32768) runs all agents in one launch per stage
+        (k_rollout_mlp_h3_agents / k_rollout_mlp_w_agents).  ``agent``: None gives every agent this one model (the shared
+        model; a later such call returns the batch to it and releases the agents' own copies), an index in [0, n_agents)
+        gives that agent its own model (`mppi_set_agent_mlp[_scaled]`), as in `set_ref_path`; on a single-agent handle
+        ``agent=0`` is the plain setter.  A launch is one kernel instantiation, so all agents of a handle hold one shape
+        (H, n): a per-agent model whose shape differs from the one any other agent holds is refused (``MppiError``,
+        MPPI_ERR_SHAPE; the message names both shapes) -- ``set_mlp(weights)`` changes the shape of the whole batch.  Every
+        agent needs a model before a run (MPPI_ERR_STATE names the first one without).  Also refused: an ``agent`` outside
+        the handle (MPPI_ERR_BAD_ARG), a handle of another dynamics model (MPPI_ERR_STATE), and on a batched handle a
+        model only the f32-input kernel can serve -- weights beyond the f16 range, or MPPI_MLP_F32=1 -- (MPPI_ERR_UNSUPPORTED).
+        A refused call leaves the agent on the model it had."""
         def arr(k):
             v = weights[k]
             if hasattr(v, "detach"):
@@ -134,16 +141,21 @@ class Engine:
             raise ValueError(f"MLP of hidden width {hidden} with {n_hidden} hidden layers: the supported set is hidden H in "
                              "{64, 128, 256, 512} x n_hidden in {1, 2, 3, 4}")
         PP = C.POINTER(C.c_float) * max(1, n_hidden)
+        model = (hidden, n_hidden, fp(w_in), fp(b_in), PP(*[fp(w) for w in wh]), PP(*[fp(b) for b in bh]), fp(w_out), fp(b_out))
         if scalers is None:
-            self._ck(self.lib.mppi_set_mlp(self._h, hidden, n_hidden, fp(w_in), fp(b_in), PP(*[fp(w) for w in wh]),
-                                           PP(*[fp(b) for b in bh]), fp(w_out), fp(b_out)))
+            if agent is None:
+                self._ck(self.lib.mppi_set_mlp(self._h, *model))
+            else:
+                self._ck(self.lib.mppi_set_agent_mlp(self._h, int(agent), *model))
             return
         st = {k: np.ascontiguousarray(scalers[k], dtype=np.float64) for k in ("in_mean", "in_scale", "out_mean", "out_scale")}
         if st["in_mean"].shape != (5,) or st["in_scale"].shape != (5,) or st["out_mean"].shape != (3,) or st["out_scale"].shape != (3,):
             raise ValueError("scalers: in_mean / in_scale have 5 entries (state, control), out_mean / out_scale 3")
-        self._ck(self.lib.mppi_set_mlp_scaled(self._h, hidden, n_hidden, fp(w_in), fp(b_in), PP(*[fp(w) for w in wh]),
-                                              PP(*[fp(b) for b in bh]), fp(w_out), fp(b_out), _dp(st["in_mean"]),
-                                              _dp(st["in_scale"]), _dp(st["out_mean"]), _dp(st["out_scale"])))
+        stats = (_dp(st["in_mean"]), _dp(st["in_scale"]), _dp(st["out_mean"]), _dp(st["out_scale"]))
+        if agent is None:
+            self._ck(self.lib.mppi_set_mlp_scaled(self._h, *model, *stats))
+        else:
+            self._ck(self.lib.mppi_set_agent_mlp_scaled(self._h, int(agent), *model, *stats))
 
     def set_u_prev(self, u):
         u = np.ascontiguousarray(u, dtype=np.float64)

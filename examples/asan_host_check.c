@@ -70,6 +70,15 @@ int main(void) {
         EXPECT(mppi_set_agent_obstacles(NULL, 0, path, 2) == MPPI_ERR_BAD_ARG);
         EXPECT(mppi_get_agent_status(NULL, NULL, NULL) == MPPI_ERR_BAD_ARG);
     }
+    {   /* the per-agent model setters: a NULL handle is refused before anything is read */
+        static float w_in[64 * 5], b_in[64], w_h[64 * 64], b_h[64], w_out[3 * 64], b_out[3];
+        const float *wh[1] = {w_h}, *bh[1] = {b_h};
+        const double m5[5] = {0, 0, 0, 0, 0}, s5[5] = {1, 1, 1, 1, 1};
+        EXPECT(mppi_set_agent_mlp(NULL, 0, 64, 1, w_in, b_in, wh, bh, w_out, b_out) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_agent_mlp_scaled(NULL, 0, 64, 1, w_in, b_in, wh, bh, w_out, b_out, m5, s5, m5, s5) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_mlp(NULL, 64, 1, w_in, b_in, wh, bh, w_out, b_out) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_mlp_scaled(NULL, 64, 1, w_in, b_in, wh, bh, w_out, b_out, NULL, NULL, NULL, NULL) == MPPI_ERR_BAD_ARG);
+    }
     EXPECT(mppi_comm_unique_id(NULL) == MPPI_ERR_BAD_ARG);
     EXPECT(mppi_get_rollout_kernel(NULL, NULL, 0) == MPPI_ERR_BAD_ARG);
     mppi_cb_config cb;

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MPPI_ABI_VERSION 5
+#define MPPI_ABI_VERSION 6
 
 typedef enum {
     MPPI_OK = 0,
@@ -124,13 +124,15 @@ typedef struct {
      * set -- for all of them (mppi_set_ref_path / mppi_set_obstacles) or one per agent (mppi_set_agent_ref_path /
      * mppi_set_agent_obstacles: a fleet, or one planner weighing several routes).
      * 0/1 = one agent (every entry point).  > 1: needs MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT and no sharding; the analytic
-     * models T <= 128 and K <= 8192; MPPI_MODEL_DIFFDRIVE_MLP K <= 32768 (one mppi_set_mlp serves every agent, on the
-     * f16-split kernels only: MPPI_MLP_F32 and weights beyond the f16 range are MPPI_ERR_UNSUPPORTED there);
+     * models T <= 128 and K <= 8192; MPPI_MODEL_DIFFDRIVE_MLP K <= 32768, with one mppi_set_mlp serving every agent or one
+     * model per agent (mppi_set_agent_mlp: a fleet whose robots carry their own fine-tuned residuals, an ensemble of
+     * checkpoints planning side by side; all of one shape), on the f16-split kernels only: MPPI_MLP_F32 and weights beyond
+     * the f16 range are MPPI_ERR_UNSUPPORTED there;
      * mppi_set_state / mppi_get_state / mppi_set_u_prev / mppi_get_u_prev / mppi_get_costs then take [n_agents][...]
      * arrays and mppi_run_closed_loop advances all agents (stats: agent 0; an agent that reaches the end of its path
      * stops the call with MPPI_ERR_PATH_END: mppi_get_agent_status says which); mppi_set_waypoint_idx /
      * mppi_set_iteration apply to every agent; the host-in-the-loop and split steps, the visualisation rollouts and the
-     * exchange are single-agent; the mppi_eval_* stage methods see agent 0's scene. */
+     * exchange are single-agent; the mppi_eval_* stage methods see agent 0's scene and agent 0's model. */
     int32_t n_agents;
     /* fourth word of the sampler's Philox counter (agent a of a batched handle draws with noise_stream + a, so a
      * single-agent handle with noise_stream = a reproduces its noise) */
@@ -212,6 +214,29 @@ int mppi_set_mlp(mppi_handle *h, int32_t hidden, int32_t n_hidden, const float *
 int mppi_set_mlp_scaled(mppi_handle *h, int32_t hidden, int32_t n_hidden, const float *w_in, const float *b_in,
                         const float *const *w_hidden, const float *const *b_hidden, const float *w_out, const float *b_out,
                         const double *in_mean, const double *in_scale, const double *out_mean, const double *out_scale);
+/*
+ * The same two calls for ONE agent of a batched handle (mppi_config.n_agents > 1), with the semantics of the per-agent scene
+ * setters: agent `agent` in [0, n_agents) -- else MPPI_ERR_BAD_ARG -- plans with its own residual model, held in buffers the
+ * handle owns for it; validation, packing and (mppi_set_agent_mlp_scaled) folding are those of the calls above.  On a
+ * batched handle the two calls above set EVERY agent, so a later one returns the batch to one shared model and releases the
+ * agents' own copies.  On a single-agent handle agent = 0 is the plain setter.
+ * One shape per batch: a launch is one kernel instantiation, so a per-agent model whose (hidden, n_hidden) differs from the
+ * shape held by any OTHER agent that has a model is MPPI_ERR_SHAPE (mppi_last_error names both shapes); on a handle where
+ * no agent has a model yet the first call fixes the shape; mppi_set_mlp changes the shape of the whole batch.
+ * Also refused: a handle of another dynamics model (MPPI_ERR_STATE); a shape outside the supported set (MPPI_ERR_SHAPE);
+ * weights beyond the f16 range or MPPI_MLP_F32=1 (MPPI_ERR_UNSUPPORTED: batched handles run the f16-split kernels only).  A
+ * call that fails leaves the agent on the model it had.  Every agent needs a model before a run: MPPI_ERR_STATE names the
+ * first one without.  Replacing an agent's weights between two mppi_run_closed_loop calls needs no re-capture of a cached
+ * graph (MPPI_GRAPH=1): the kernels read the agents' models from a table in device memory.
+ * The single-agent entry points a batched handle serves -- mppi_eval_state_transition, and the visualisation rollouts'
+ * kernels -- use agent 0's model, as they use agent 0's scene.
+ */
+int mppi_set_agent_mlp(mppi_handle *h, int32_t agent, int32_t hidden, int32_t n_hidden, const float *w_in, const float *b_in,
+                       const float *const *w_hidden, const float *const *b_hidden, const float *w_out, const float *b_out);
+int mppi_set_agent_mlp_scaled(mppi_handle *h, int32_t agent, int32_t hidden, int32_t n_hidden, const float *w_in,
+                              const float *b_in, const float *const *w_hidden, const float *const *b_hidden, const float *w_out,
+                              const float *b_out, const double *in_mean, const double *in_scale, const double *out_mean,
+                              const double *out_scale);
 /* mutable controller state: `u_prev[T,2]` and `prev_way_point_idx` / `prev_waypoints_idx`
  * (mppi_differential_drive.py:82,:85); host pointers */
 int mppi_set_u_prev(mppi_handle *h, const double *u);

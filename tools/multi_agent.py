@@ -3,12 +3,13 @@ closed loops on the device.  Launches of different agents overlap (one agent's s
 others' rollouts), so the aggregate rate exceeds the single-agent one until the rollouts fill the chip.
 Prints one JSON line per agent count.
 
-    python tools/multi_agent.py [--batched-only] [--own-scenes] [--circles M] [--mlp HxN --K K] [--out FILE] [agents ...]
+    python tools/multi_agent.py [--batched-only] [--own-scenes] [--circles M] [--mlp HxN --K K [--own-models]] [--out FILE] [agents ...]
 
 --own-scenes: every agent of the batched handle follows its own path (the shared one shifted by the agent) and sees its own M
 circles (mppi_set_agent_ref_path / mppi_set_agent_obstacles) instead of the one scene all share; --circles M: M circles beside
 the path (shared, or each agent's own); --mlp HxN: the batched handles run learned dynamics of that shape (seeded random
-weights, K samples per agent) instead of config 2; --batched-only skips the one-handle-per-agent part; --out FILE appends the
+weights, K samples per agent) instead of config 2, with --own-models agent a on its own model (the weights seeded a,
+Engine.set_mlp(w, agent=a)) instead of the one all share; --batched-only skips the one-handle-per-agent part; --out FILE appends the
 batched lines to FILE as JSON lines tagged with the build id."""
 import json
 import os
@@ -44,7 +45,7 @@ def option(name, default=None):
     return default
 
 
-BATCHED_ONLY, OWN_SCENES = flag("--batched-only"), flag("--own-scenes")
+BATCHED_ONLY, OWN_SCENES, OWN_MODELS = flag("--batched-only"), flag("--own-scenes"), flag("--own-models")
 N_CIRCLES, MLP, OUT = int(option("--circles", "0")), option("--mlp"), option("--out")
 K_AGENT = int(option("--K", str(K_SAMPLES)))
 N_ITER = 3000 if not MLP else 100
@@ -114,7 +115,10 @@ for n_agents in [int(a) for a in (ARGV or ["1", "2", "4", "8", "16", "32"])]:
         eng.set_ref_path(path)
         if N_CIRCLES:
             eng.set_obstacles(circles)
-    if MLP:
+    if MLP and OWN_MODELS and n_agents > 1:
+        for a in range(n_agents):
+            eng.set_mlp(mo.random_mlp_weights(a, hidden=H, n_hidden=NH), agent=a)
+    elif MLP:
         eng.set_mlp(mlp_weights)
     eng.set_state(x0 if n_agents > 1 else x0[0])
     eng.run_closed_loop(200 if not MLP else 10)
@@ -125,6 +129,7 @@ for n_agents in [int(a) for a in (ARGV or ["1", "2", "4", "8", "16", "32"])]:
     dt = time.perf_counter() - t0
     line = {"agents_batched_in_one_handle": n_agents, "K": K_AGENT, "T": HORIZON, "iterations": N_ITER,
             "scenes": "own" if OWN_SCENES and n_agents > 1 else "shared", "circles_per_agent": N_CIRCLES, "mlp": MLP,
+            "models": "own" if MLP and OWN_MODELS and n_agents > 1 else "shared" if MLP else None,
             "kernel": eng.rollout_kernel(), "us_per_iteration_all_agents": 1e6 * dt / N_ITER,
             "aggregate_traj_steps_per_s": n_agents * K_AGENT * HORIZON * N_ITER / dt}
     print(json.dumps(line), flush=True)
