@@ -32,9 +32,25 @@ def source_id() -> str:
     return h.hexdigest()[:16]
 
 
+PRIMS_LIB = os.path.join(PKG, "lib", "libmppi_prims.so")
+PRIMS_SRC = os.path.join(os.path.dirname(PKG), "tests", "device", "prims_harness.hip")
+
+
+def prims_library() -> str:
+    """The test-only harness around the device headers (tests/device/prims_harness.hip -> lib/libmppi_prims.so, csrc/Makefile's
+    `prims` target, the product's flags): built if it is missing or older than its source or a header; returns its path."""
+    srcs = [PRIMS_SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    if not os.path.exists(PRIMS_LIB) or any(os.path.getmtime(s) > os.path.getmtime(PRIMS_LIB) for s in srcs):
+        res = subprocess.run(["make", "-C", CSRC, "prims"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if res.returncode != 0:
+            print(res.stdout)
+            raise RuntimeError("building libmppi_prims.so failed (hipcc, gfx950)")
+    return PRIMS_LIB
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 -shared ... -> lib/libmppi_hip.so; returns its path."""
-    if force or lib_is_stale():
+    if force or lib_is_stale() or not os.path.exists(PRIMS_LIB):  # (`all` makes the test harness library too)
         cmd = ["make", "-j4", "-C", CSRC] + (["-B"] if force else [])
         res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if verbose or res.returncode != 0:

@@ -100,10 +100,12 @@ __device__ __forceinline__ int nearest_in_window_split(const RefPair<R> *sh, int
         const int oj = __shfl_xor(bj, m);
         if (od < best || (od == best && oj < bj)) { best = od; bj = oj; }
     }
-    return c + __shfl(bj, lane << lg);  // lane t reads the result of its group's first lane
+    const int j = __shfl(bj, lane << lg);  // lane t reads the result of its group's first lane
+    return c + (j == 0x7fffffff ? 0 : j);  // (nothing compared smaller -- a NaN or overflowing position: the first candidate)
 }
 
-// Same search for ONE wave-uniform position with the candidates spread over the lanes.
+// Same search for ONE wave-uniform position with the candidates spread over the lanes.  (A position no candidate compares
+// smaller for -- NaN, infinite, or so far that d overflows -- gives c like the serial searches above: wv::argmin_first.)
 template <typename R>
 __device__ __forceinline__ int nearest_uniform(const R *__restrict__ ref, int c, int wlen, R x, R y, int lane) {
     R best = R(INFINITY);
@@ -114,6 +116,22 @@ __device__ __forceinline__ int nearest_uniform(const R *__restrict__ ref, int c,
     }
     wv::argmin_first(best, bj);
     return c + bj;
+}
+
+// The x0 call's search (mppi_differential_drive.py:96-99, mppi_race_car.py:61-65): nearest_uniform in f64 whatever the
+// handle's precision, so that the closed loop on the device and the same loop stepped from the host take the same index
+// at a near tie.
+template <typename R>
+__device__ __forceinline__ int nearest_x0(const R *__restrict__ ref, int p, int wlen, double x, double y, int lane) {
+    double best = INFINITY;
+    int bj = INT_MAX;
+    for (int j = lane; j < wlen; j += 64) {
+        const double dx = x - (double)ref[4 * (p + j)], dy = y - (double)ref[4 * (p + j) + 1];
+        const double d = dx * dx + dy * dy;
+        if (d < best) { best = d; bj = j; }
+    }
+    wv::argmin_first(best, bj);
+    return p + bj;
 }
 
 // the noise tensor [K][T][2] of (iteration, agent): the caller's tensor of this call, or the slot of a noise ring

@@ -47,17 +47,8 @@ __device__ unsigned long long g_stamps[128];  // [64 + n]: the same stamp of the
 template <typename R>
 __device__ __forceinline__ void x0_call(DevState *st, const R *ref, int n_ref, int window, int sequential, int lane,
                                         double x, double y, int p) {
-    double best = INFINITY;
-    int bj = INT_MAX;
-    const int wlen = window_len<R>(window, n_ref, p);
-    for (int j = lane; j < wlen; j += 64) {
-        const double dx = x - (double)ref[4 * (p + j)], dy = y - (double)ref[4 * (p + j) + 1];
-        const double d = dx * dx + dy * dy;
-        if (d < best) { best = d; bj = j; }
-    }
-    wv::argmin_first(best, bj);
+    const int c = nearest_x0(ref, p, window_len<R>(window, n_ref, p), x, y, lane);
     if (lane == 0) {
-        const int c = p + bj;
         st->c = c;  // the reference clamps to n_ref-1 here, which c already satisfies (:97-99)
         st->idx_start = c;
         st->path_end = c >= n_ref - 1;
@@ -658,7 +649,8 @@ __device__ __forceinline__ void per_rollout_thread(const KParams<R> &P, int c, c
             if (d < best) { best = d; bj = j; }
         }
         const R m = row_all_min(best);
-        p += row_all_min(best == m ? bj : INT_MAX);  // first minimum: the smallest offset among the nearest
+        const int off = row_all_min(best == m ? bj : INT_MAX);  // first minimum: the smallest offset among the nearest
+        p += off == INT_MAX ? 0 : off;  // (a NaN or overflowing position: the first candidate, as wv::argmin_first)
         if (sub == 0) sh_ix[s][t] = (short)p;
     }
 }

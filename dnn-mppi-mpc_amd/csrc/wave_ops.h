@@ -135,9 +135,13 @@ __device__ __forceinline__ double shfl_xor(double x, int m) { return __shfl_xor(
 // (d, j) -> the pair with the smallest d over the wave; ties go to the smaller j
 // (np.argmin / list.index semantics: first minimum).  Every lane gets the result.
 // Two DPP reductions (min of d, then min of j among the lanes that hold it): 12 VALU ops, no LDS traffic.
+// Total: where no lane holds the minimum with a j below INT_MAX -- NaN distances, which equal nothing, or searches that
+// start from j = INT_MAX and met only NaN / +inf distances, so that nothing compared smaller -- the result is j = 0, the
+// first candidate, as np.argmin over all-NaN or all-inf gives it (one scalar select; every other result is untouched).
 template <typename R> __device__ __forceinline__ void argmin_first(R &d, int &j) {
     const R m = reduce<OpMin>(d);
-    j = reduce<OpMinInt>(d == m ? j : 0x7fffffff);
+    const int jm = reduce<OpMinInt>(d == m ? j : 0x7fffffff);
+    j = jm == 0x7fffffff ? 0 : jm;
     d = m;
 }
 

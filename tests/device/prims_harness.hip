@@ -1,0 +1,397 @@
+// Test-only harness around the device primitives (mathfn.h, wave_ops.h, philox.h, mppi_device.h): libmppi_prims.so.
+// Every entry point takes HOST pointers, allocates, copies in, launches one tiny kernel, synchronises, copies out, frees and
+// returns the hipError_t as an int.  Wave-level kernels run as ONE block of 64 threads with every lane active; the search
+// kernels only STORE the index a search returns and never use it as an address.  tests/test_gpu_primitives.py drives it.
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "mppi_device.h"
+
+namespace {
+
+using namespace mppi;
+
+struct Scope {  // device buffers of one call, freed on every way out
+    std::vector<void *> ptrs;
+    ~Scope() {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+    hipError_t alloc(void **d, size_t bytes) {
+        const hipError_t e = hipMalloc(d, bytes ? bytes : 1);
+        if (e == hipSuccess) ptrs.push_back(*d);
+        return e;
+    }
+    template <typename T> hipError_t in(T *&d, const T *h, size_t n) {
+        hipError_t e = alloc((void **)&d, n * sizeof(T));
+        if (e == hipSuccess && n) e = hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
+        return e;
+    }
+    template <typename T> hipError_t out(T *&d, size_t n) {
+        hipError_t e = alloc((void **)&d, n * sizeof(T));
+        if (e == hipSuccess) e = hipMemset(d, 0xff, n * sizeof(T) ? n * sizeof(T) : 1);
+        return e;
+    }
+};
+
+#define CK(expr)                                \
+    do {                                        \
+        const hipError_t e_ = (expr);           \
+        if (e_ != hipSuccess) return (int)e_;   \
+    } while (0)
+
+template <typename T> hipError_t finish(T *h, const T *d, size_t n) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess && n) e = hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost);
+    return e;
+}
+
+// ------------------------------------------------------------------------------------------ mathfn
+enum { M_SINCOS = 0, M_TAN, M_PYMOD, M_EXP, M_CLAMP };
+
+template <typename R> __global__ __launch_bounds__(256) void k_map(int fn, const R *a, R b, R *o0, R *o1, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const R x = a[i];
+    switch (fn) {
+        case M_SINCOS: { R s, c; mf::sincos_(x, s, c); o0[i] = s; o1[i] = c; break; }
+        case M_TAN: o0[i] = mf::tan_(x); break;
+        case M_PYMOD: o0[i] = mf::pymod(x, b); break;
+        case M_EXP: o0[i] = mf::exp_(x); break;
+        default: o0[i] = mf::clamp(x, b); break;
+    }
+}
+
+template <typename R> int run_map(int fn, const R *a, R b, R *o0, R *o1, int n) {
+    if (n < 0 || n > (1 << 21) || fn < M_SINCOS || fn > M_CLAMP) return (int)hipErrorInvalidValue;
+    Scope sc;
+    R *da, *d0, *d1;
+    CK(sc.in(da, a, n));
+    CK(sc.out(d0, n));
+    CK(sc.out(d1, n));
+    if (n) k_map<R><<<(n + 255) / 256, 256>>>(fn, da, b, d0, d1, n);
+    CK(finish(o0, d0, n));
+    if (o1) CK(hipMemcpy(o1, d1, (size_t)n * sizeof(R), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ wave_ops
+enum { V_SCAN = 0, V_HALF, V_ROW, V_SEG1, V_SEG2, V_REDUCE };
+
+template <typename Op, typename R> __device__ __forceinline__ R scan_variant(int variant, R x) {
+    switch (variant) {
+        case V_SCAN: return wv::scan_incl<Op>(x);
+        case V_HALF: return wv::scan_incl_half<Op>(x);
+        case V_ROW: return wv::scan_incl_row<Op>(x);
+        case V_SEG1: return wv::scan_incl_seg<Op, 1>(x);
+        case V_SEG2: return wv::scan_incl_seg<Op, 2>(x);
+        default: return wv::reduce<Op>(x);
+    }
+}
+
+// op 0: OpAdd (fp) / OpMinInt (int), op 1: OpMin (fp) / OpMaxInt (int)
+template <typename R> __global__ __launch_bounds__(64) void k_scan(int op, int variant, const R *in, R *out) {
+    const R x = in[threadIdx.x];
+    out[threadIdx.x] = op == 0 ? scan_variant<wv::OpAdd>(variant, x) : scan_variant<wv::OpMin>(variant, x);
+}
+template <> __global__ __launch_bounds__(64) void k_scan<int>(int op, int variant, const int *in, int *out) {
+    const int x = in[threadIdx.x];
+    out[threadIdx.x] = op == 0 ? scan_variant<wv::OpMinInt>(variant, x) : scan_variant<wv::OpMaxInt>(variant, x);
+}
+
+template <typename R> int run_scan(int op, int variant, const R *in, R *out) {
+    if (op < 0 || op > 1 || variant < V_SCAN || variant > V_REDUCE) return (int)hipErrorInvalidValue;
+    Scope sc;
+    R *di, *dout;
+    CK(sc.in(di, in, 64));
+    CK(sc.out(dout, 64));
+    k_scan<R><<<1, 64>>>(op, variant, di, dout);
+    return (int)finish(out, dout, 64);
+}
+
+// variant 0: shift_up1, 1: shift_up1_half, 2: shift_up1_seg<1>, 3: shift_up1_seg<2>
+template <typename R> __global__ __launch_bounds__(64) void k_shift(int variant, const R *in, R carry, R *out) {
+    const R x = in[threadIdx.x];
+    R y;
+    switch (variant) {
+        case 0: y = wv::shift_up1(x, carry); break;
+        case 1: y = wv::shift_up1_half(x, carry); break;
+        case 2: y = wv::shift_up1_seg<1>(x, carry); break;
+        default: y = wv::shift_up1_seg<2>(x, carry); break;
+    }
+    out[threadIdx.x] = y;
+}
+template <typename R> int run_shift(int variant, const R *in, R carry, R *out) {
+    if (variant < 0 || variant > 3) return (int)hipErrorInvalidValue;
+    Scope sc;
+    R *di, *dout;
+    CK(sc.in(di, in, 64));
+    CK(sc.out(dout, 64));
+    k_shift<R><<<1, 64>>>(variant, di, carry, dout);
+    return (int)finish(out, dout, 64);
+}
+
+// out[l][lane] = read_lane(x, l)
+template <typename R> __global__ __launch_bounds__(64) void k_read_lane(const R *in, R *out) {
+    const R x = in[threadIdx.x];
+    for (int l = 0; l < 64; ++l) out[64 * l + threadIdx.x] = wv::read_lane(x, l);
+}
+template <typename R> int run_read_lane(const R *in, R *out) {
+    Scope sc;
+    R *di, *dout;
+    CK(sc.in(di, in, 64));
+    CK(sc.out(dout, 64 * 64));
+    k_read_lane<R><<<1, 64>>>(di, dout);
+    return (int)finish(out, dout, 64 * 64);
+}
+
+template <typename R> __global__ __launch_bounds__(64) void k_shfl_xor(int m, const R *in, R *out) {
+    out[threadIdx.x] = wv::shfl_xor(in[threadIdx.x], m);
+}
+template <typename R> int run_shfl_xor(int m, const R *in, R *out) {
+    if (m < 1 || m > 63) return (int)hipErrorInvalidValue;
+    Scope sc;
+    R *di, *dout;
+    CK(sc.in(di, in, 64));
+    CK(sc.out(dout, 64));
+    k_shfl_xor<R><<<1, 64>>>(m, di, dout);
+    return (int)finish(out, dout, 64);
+}
+
+template <typename R> __global__ __launch_bounds__(64) void k_argmin(const R *d_in, const int *j_in, R *d_out, int *j_out) {
+    R d = d_in[threadIdx.x];
+    int j = j_in[threadIdx.x];
+    wv::argmin_first(d, j);
+    d_out[threadIdx.x] = d;
+    j_out[threadIdx.x] = j;
+}
+template <typename R> int run_argmin(const R *d_in, const int *j_in, R *d_out, int *j_out) {
+    Scope sc;
+    R *dd, *dod;
+    int *dj, *doj;
+    CK(sc.in(dd, d_in, 64));
+    CK(sc.in(dj, j_in, 64));
+    CK(sc.out(dod, 64));
+    CK(sc.out(doj, 64));
+    k_argmin<R><<<1, 64>>>(dd, dj, dod, doj);
+    CK(finish(d_out, dod, 64));
+    return (int)hipMemcpy(j_out, doj, 64 * sizeof(int), hipMemcpyDeviceToHost);
+}
+
+template <typename R> __global__ __launch_bounds__(64) void k_ordered_sum(R acc, const R *v, int first, int n, R *out) {
+    out[threadIdx.x] = wv::ordered_sum(acc, v[threadIdx.x], first, n);
+}
+template <typename R> int run_ordered_sum(R acc, const R *v, int first, int n, R *out) {
+    if (first < 0 || n < 0 || first + n > 64) return (int)hipErrorInvalidValue;
+    Scope sc;
+    R *dv, *dout;
+    CK(sc.in(dv, v, 64));
+    CK(sc.out(dout, 64));
+    k_ordered_sum<R><<<1, 64>>>(acc, dv, first, n, dout);
+    return (int)finish(out, dout, 64);
+}
+
+// ------------------------------------------------------------------------------------------ searches
+// out[row][64]: 0 nearest_in_window, 1 nearest_in_window_lds, 2..5 nearest_in_window_split (split 2, 4, 8, 16: lanes
+// < 64 / split hold a result, the others -1), 6 nearest_uniform and 7 nearest_x0 for query q in entry q, 8: 1 where every
+// lane of the wave got the same result from the two wave-level searches of query q
+constexpr int SEARCH_ROWS = 9;
+
+template <typename R>
+__global__ __launch_bounds__(64) void k_search(const R *ref, int c, int wlen, const R *qx, const R *qy, int *out) {
+    __shared__ RefPair<R> sh[WINDOW_LDS_MAX / 2];
+    const int lane = threadIdx.x;
+    const R x = qx[lane], y = qy[lane];
+    stage_window(sh, ref, c, wlen, lane, 64);
+    __syncthreads();
+    out[0 * 64 + lane] = nearest_in_window(ref, c, wlen, x, y);
+    out[1 * 64 + lane] = nearest_in_window_lds(sh, c, wlen, x, y);
+    int row = 2;
+    for (int split = 2; split <= 16; split <<= 1, ++row) {
+        const int r = nearest_in_window_split(sh, c, wlen, x, y, split, lane);
+        out[row * 64 + lane] = lane < 64 / split ? r : -1;
+    }
+    int mine_u = -1, mine_x0 = -1, same = 0;
+    for (int q = 0; q < 64; ++q) {
+        const R xq = wv::read_lane(x, q), yq = wv::read_lane(y, q);
+        const int ru = nearest_uniform(ref, c, wlen, xq, yq, lane);
+        const int rx = nearest_x0(ref, c, wlen, (double)xq, (double)yq, lane);
+        const int all_same = __all(ru == wv::read_lane(ru, 0) && rx == wv::read_lane(rx, 0));
+        if (lane == q) { mine_u = ru; mine_x0 = rx; same = all_same; }
+    }
+    out[6 * 64 + lane] = mine_u;
+    out[7 * 64 + lane] = mine_x0;
+    out[8 * 64 + lane] = same;
+}
+
+template <typename R> int run_search(const R *ref, int n_ref, int c, int wlen, const R *qx, const R *qy, int *out) {
+    if (n_ref < 1 || c < 0 || wlen < 1 || wlen > WINDOW_LDS_MAX || c + wlen > n_ref) return (int)hipErrorInvalidValue;
+    Scope sc;
+    R *dref, *dx, *dy;
+    int *dout;
+    CK(sc.in(dref, ref, (size_t)n_ref * 4));
+    CK(sc.in(dx, qx, 64));
+    CK(sc.in(dy, qy, 64));
+    CK(sc.out(dout, SEARCH_ROWS * 64));
+    k_search<R><<<1, 64>>>(dref, c, wlen, dx, dy, dout);
+    return (int)finish(out, dout, SEARCH_ROWS * 64);
+}
+
+// ------------------------------------------------------------------------------------------ collision
+// out[0][n]: collided<true> / OBS_OUTLINE, out[1][n]: collided<false> / OBS_OUTLINE, out[2][n]: OBS_CIRCLE
+template <typename R>
+__global__ __launch_bounds__(64) void k_collide(int n_obs, const R *obs, const R *shape, const R *poses, int n, int *out) {
+    KParams<R> P = {};
+    P.n_obs = n_obs;
+    P.obs = obs;
+    for (int q = 0; q < 9; ++q) { P.shape_x[q] = shape[q]; P.shape_y[q] = shape[9 + q]; }
+    P.obstacle_model = OBS_OUTLINE;
+    const int lane = threadIdx.x;
+    const ObsLanes<R> tab = load_obstacles(P, lane);
+    for (int i = lane; i < n; i += 64) {  // n is a multiple of 64: every lane stays active
+        const R x = poses[3 * i], y = poses[3 * i + 1], yaw = poses[3 * i + 2];
+        P.obstacle_model = OBS_OUTLINE;
+        out[i] = collided<true>(P, x, y, yaw, tab) ? 1 : 0;
+        out[n + i] = collided<false>(P, x, y, yaw, tab) ? 1 : 0;
+        P.obstacle_model = OBS_CIRCLE;
+        out[2 * n + i] = collided<false>(P, x, y, yaw, tab) ? 1 : 0;
+    }
+}
+
+template <typename R> int run_collide(int n_obs, const R *obs, const R *shape, const R *poses, int n, int *out) {
+    if (n_obs < 1 || n_obs > 4096 || n < 64 || n % 64 || n > (1 << 20)) return (int)hipErrorInvalidValue;
+    Scope sc;
+    R *dobs, *dshape, *dposes;
+    int *dout;
+    CK(sc.in(dobs, obs, (size_t)n_obs * 4));
+    CK(sc.in(dshape, shape, 18));
+    CK(sc.in(dposes, poses, (size_t)n * 3));
+    CK(sc.out(dout, (size_t)n * 3));
+    k_collide<R><<<1, 64>>>(n_obs, dobs, dshape, dposes, n, dout);
+    return (int)finish(out, dout, (size_t)n * 3);
+}
+
+// ------------------------------------------------------------------------------------------ sampler
+__global__ __launch_bounds__(256) void k_philox(const unsigned *ctr, const unsigned *key, unsigned *out, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    unsigned r[4];
+    px::philox4x32_10(ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], key[2 * i], key[2 * i + 1], r);
+    for (int q = 0; q < 4; ++q) out[4 * i + q] = r[q];
+}
+
+__global__ __launch_bounds__(256) void k_uniform_open(const unsigned *r, float *out, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = px::uniform_open(r[i]);
+}
+
+struct Chol { float v[3]; };
+
+__global__ __launch_bounds__(256) void k_box_muller(const unsigned *ra, const unsigned *rb, Chol ch, float *e, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    px::box_muller(ra[i], rb[i], ch.v, e[2 * i], e[2 * i + 1]);
+}
+
+__global__ __launch_bounds__(256) void k_sample(unsigned seed_lo, unsigned seed_hi, unsigned iter, const unsigned *k,
+                                                const int *t, unsigned stream, Chol ch, float *e, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    px::sample(seed_lo, seed_hi, iter, k[i], t[i], ch.v, e[2 * i], e[2 * i + 1], stream);
+}
+
+constexpr int SAMPLER_MAX = 1 << 20;
+
+}  // namespace
+
+extern "C" {
+
+int prims_sincos_f32(const float *x, float *s, float *c, int n) { return run_map<float>(M_SINCOS, x, 0.f, s, c, n); }
+int prims_tan_f32(const float *x, float *y, int n) { return run_map<float>(M_TAN, x, 0.f, y, nullptr, n); }
+int prims_pymod_f32(const float *a, float m, float *r, int n) { return run_map<float>(M_PYMOD, a, m, r, nullptr, n); }
+int prims_exp_f32(const float *x, float *y, int n) { return run_map<float>(M_EXP, x, 0.f, y, nullptr, n); }
+int prims_clamp_f32(const float *v, float lim, float *r, int n) { return run_map<float>(M_CLAMP, v, lim, r, nullptr, n); }
+int prims_clamp_f64(const double *v, double lim, double *r, int n) { return run_map<double>(M_CLAMP, v, lim, r, nullptr, n); }
+
+int prims_scan_f32(int op, int variant, const float *in, float *out) { return run_scan(op, variant, in, out); }
+int prims_scan_f64(int op, int variant, const double *in, double *out) { return run_scan(op, variant, in, out); }
+int prims_scan_i32(int op, int variant, const int *in, int *out) { return run_scan(op, variant, in, out); }
+int prims_shift_f32(int variant, const float *in, float carry, float *out) { return run_shift(variant, in, carry, out); }
+int prims_shift_f64(int variant, const double *in, double carry, double *out) { return run_shift(variant, in, carry, out); }
+int prims_read_lane_f32(const float *in, float *out) { return run_read_lane(in, out); }
+int prims_read_lane_f64(const double *in, double *out) { return run_read_lane(in, out); }
+int prims_shfl_xor_f32(int m, const float *in, float *out) { return run_shfl_xor(m, in, out); }
+int prims_shfl_xor_f64(int m, const double *in, double *out) { return run_shfl_xor(m, in, out); }
+int prims_argmin_f32(const float *d, const int *j, float *d_out, int *j_out) { return run_argmin(d, j, d_out, j_out); }
+int prims_argmin_f64(const double *d, const int *j, double *d_out, int *j_out) { return run_argmin(d, j, d_out, j_out); }
+int prims_ordered_sum_f32(float acc, const float *v, int first, int n, float *out) { return run_ordered_sum(acc, v, first, n, out); }
+int prims_ordered_sum_f64(double acc, const double *v, int first, int n, double *out) { return run_ordered_sum(acc, v, first, n, out); }
+
+int prims_search_rows(void) { return SEARCH_ROWS; }
+int prims_search_f32(const float *ref, int n_ref, int c, int wlen, const float *qx, const float *qy, int *out) {
+    return run_search(ref, n_ref, c, wlen, qx, qy, out);
+}
+int prims_search_f64(const double *ref, int n_ref, int c, int wlen, const double *qx, const double *qy, int *out) {
+    return run_search(ref, n_ref, c, wlen, qx, qy, out);
+}
+
+// shape: shape_x[9] then shape_y[9]; poses [n][3] {x, y, yaw}; out [3][n]
+int prims_collide_f32(int n_obs, const float *obs, const float *shape, const float *poses, int n, int *out) {
+    return run_collide(n_obs, obs, shape, poses, n, out);
+}
+int prims_collide_f64(int n_obs, const double *obs, const double *shape, const double *poses, int n, int *out) {
+    return run_collide(n_obs, obs, shape, poses, n, out);
+}
+
+int prims_philox(const unsigned *ctr, const unsigned *key, unsigned *out, int n) {
+    if (n < 0 || n > SAMPLER_MAX) return (int)hipErrorInvalidValue;
+    Scope sc;
+    unsigned *dc, *dk, *dout;
+    CK(sc.in(dc, ctr, (size_t)n * 4));
+    CK(sc.in(dk, key, (size_t)n * 2));
+    CK(sc.out(dout, (size_t)n * 4));
+    if (n) k_philox<<<(n + 255) / 256, 256>>>(dc, dk, dout, n);
+    return (int)finish(out, dout, (size_t)n * 4);
+}
+
+int prims_uniform_open(const unsigned *r, float *out, int n) {
+    if (n < 0 || n > SAMPLER_MAX) return (int)hipErrorInvalidValue;
+    Scope sc;
+    unsigned *dr;
+    float *dout;
+    CK(sc.in(dr, r, n));
+    CK(sc.out(dout, n));
+    if (n) k_uniform_open<<<(n + 255) / 256, 256>>>(dr, dout, n);
+    return (int)finish(out, dout, n);
+}
+
+int prims_box_muller(const unsigned *ra, const unsigned *rb, const float *chol, float *e, int n) {
+    if (n < 0 || n > SAMPLER_MAX) return (int)hipErrorInvalidValue;
+    Scope sc;
+    unsigned *da, *db;
+    float *dout;
+    CK(sc.in(da, ra, n));
+    CK(sc.in(db, rb, n));
+    CK(sc.out(dout, (size_t)n * 2));
+    const Chol ch = {{chol[0], chol[1], chol[2]}};
+    if (n) k_box_muller<<<(n + 255) / 256, 256>>>(da, db, ch, dout, n);
+    return (int)finish(e, dout, (size_t)n * 2);
+}
+
+int prims_sample(unsigned seed_lo, unsigned seed_hi, unsigned iter, const unsigned *k, const int *t, unsigned stream,
+                 const float *chol, float *e, int n) {
+    if (n < 0 || n > SAMPLER_MAX) return (int)hipErrorInvalidValue;
+    Scope sc;
+    unsigned *dk;
+    int *dt;
+    float *dout;
+    CK(sc.in(dk, k, n));
+    CK(sc.in(dt, t, n));
+    CK(sc.out(dout, (size_t)n * 2));
+    const Chol ch = {{chol[0], chol[1], chol[2]}};
+    if (n) k_sample<<<(n + 255) / 256, 256>>>(seed_lo, seed_hi, iter, dk, dt, stream, ch, dout, n);
+    return (int)finish(e, dout, (size_t)n * 2);
+}
+
+}  // extern "C"
