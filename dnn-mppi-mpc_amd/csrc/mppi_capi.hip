@@ -56,6 +56,7 @@ static Switches read_switches() {
     const char *form = getenv("MPPI_MLP_FORM");
     sw.mlp.form = form && !strcmp(form, "4x64") ? 0 : form && !strcmp(form, "8x64") ? 1 : -1;
     if (const char *e = getenv("MPPI_EXCHANGE_TIMEOUT_MS")) sw.exchange_timeout_ms = atoll(e);
+    sw.lb_timeout_ticks = std::max(0, num("MPPI_LB_TIMEOUT_TICKS", (int)LB_TIMEOUT_TICKS));
     return sw;
 }
 
@@ -928,6 +929,7 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.accumulate = c.accumulate_stage_cost;
     P.sequential = c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL;
     P.per_rollout = c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT;
+    P.lb_timeout = h->sw.lb_timeout_ticks;
     P.obstacle_model = any_obstacles(h) ? c.obstacle_model : OBS_NONE;
     P.clamp_rollout = c.clamp_rollout;
     P.wrap_stage = c.wrap_yaw_stage;

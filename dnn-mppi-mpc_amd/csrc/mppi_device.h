@@ -287,4 +287,125 @@ __device__ __forceinline__ bool round_unresolved(const DevState *st, int K) {
     return fk != NO_TRIGGER && fk + 1 < K;
 }
 
+
+// ------------------------------------------------------------------------------------------
+// The pieces of the one-launch resolution of the sequential waypoint index (LB_CAND in mppi_kernels.h; fused_lookback and
+// k_rollout_dual<..., LB> in mppi_kernels.hip put them together).  Here so that the test harness reaches them one by one.
+// ------------------------------------------------------------------------------------------
+// Look-back (one wave): waits until the words of workgroups [0, b) carry this iteration's tag; E = the largest offset among
+// them, bad = one of them is marked.  Four words per lane and 16-byte load, copy b mod LB_COPIES of the words; volatile =
+// loads that bypass this XCD's L2 (the words come from the other XCDs' workgroups).  Returns false when the wait timed out
+// (never seen: the iteration is then redone by the speculation rounds) -- after `limit` ticks of the 100 MHz clock
+// (KParams::lb_timeout); limit 0: a workgroup with b > 0 gives up before its first poll, which is how a test times out
+// without a race.
+__device__ __forceinline__ bool lb_wait(const unsigned *slots, int b, unsigned tag, int lane, int &E, bool &bad, int limit) {
+    static_assert(HYP_MAX_BLOCKS <= 512, "two 16-byte loads per lane cover the words");
+    typedef unsigned lb_u4 __attribute__((ext_vector_type(4)));
+    const volatile __attribute__((address_space(1))) lb_u4 *src =
+        (const volatile __attribute__((address_space(1))) lb_u4 *)(slots + (b & (LB_COPIES - 1)) * LB_COPY_STRIDE);
+    E = 0;
+    bad = false;
+    if (b <= 0) return true;
+    if (limit <= 0) return false;
+    unsigned long long t0 = 0ull;
+    for (int n = 0;; ++n) {
+        bool ready = true, bd = false;
+        int mx = 0;
+#pragma unroll
+        for (int i = 0; i < HYP_MAX_BLOCKS / 256; ++i) {
+            const int first = 4 * (lane + 64 * i);
+            if (first < b) {
+                const lb_u4 w4 = src[lane + 64 * i];
+                const unsigned w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (first + j < b) {
+                        ready &= (w[j] & LB_TAG_MASK) == tag;
+                        bd |= (w[j] & LB_BAD) != 0u;
+                        mx = max(mx, (int)(w[j] & (LB_BAD - 1)));
+                    }
+                }
+            }
+        }
+        if (__ballot(!ready) == 0ull) {
+            E = wv::reduce<wv::OpMaxInt>(mx);
+            bad = __ballot(bd) != 0ull;
+            return true;
+        }
+        if ((n & 15) == 15) {  // (the clock is a memory round trip of its own: looked at every 16th poll only)
+            const unsigned long long now = wall_clock64();
+            if (t0 == 0ull) t0 = now;
+            if (now - t0 > (unsigned long long)limit) return false;
+        }
+    }
+}
+// the word of workgroup b into every copy (lanes < LB_COPIES of one wave)
+__device__ __forceinline__ void lb_publish(unsigned *slots, int b, unsigned word, int lane) {
+    if (lane < LB_COPIES) __hip_atomic_store(&slots[b + lane * LB_COPY_STRIDE], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// the offsets a workgroup's calls were entered at stay within the candidates' reach (see LB_CAND)
+__device__ __forceinline__ bool lb_reach(int leave, int window, int n_ref, int c) {
+    return leave < window && (leave + window <= LB_CAND || n_ref - c <= LB_CAND);
+}
+
+// pass A of one pair of candidates {x_2q, x_2q+1, y_2q, y_2q+1}: does this lane's distance fall at the first / the second
+// of them (f32: two packed subtractions, a packed product and a packed fma)
+typedef float lb_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void lb_pair(const RefPair<float> &rp, float x, float y, float &prev, bool &g0, bool &g1) {
+    const lb_f2 dx = lb_f2{x, x} - lb_f2{rp.x0, rp.x1}, dy = lb_f2{y, y} - lb_f2{rp.y0, rp.y1};
+    const lb_f2 d = dx * dx + dy * dy;
+    g0 = d.x < prev;
+    g1 = d.y < d.x;
+    prev = d.y;
+}
+__device__ __forceinline__ void lb_pair(const RefPair<double> &rp, double x, double y, double &prev, bool &g0, bool &g1) {
+    const double dx0 = x - rp.x0, dx1 = x - rp.x1, dy0 = y - rp.y0, dy1 = y - rp.y1;
+    const double d0 = dx0 * dx0 + dy0 * dy0, d1 = dx1 * dx1 + dy1 * dy1;
+    g0 = d0 < prev;
+    g1 = d1 < d0;
+    prev = d1;
+}
+
+// Pass A for the NP positions a lane owns (an idle one: x = NaN, it never descends): m[i] = this lane's count of descents
+// over the LB_CAND candidates of sh_c, `bad` = a call of this lane whose descents do not all come first.  Per candidate a
+// comparison and ONE add-with-carry per lane: the comparisons are shifted into a word, first candidate in the top bit
+// (w <- w + w + g), so that the count is a population count and "the descents come first" reads w == 1..10..0.  (Nothing
+// on the scalar unit: lane masks per candidate had the compiler spill SGPRs into VGPR lanes in the two-samples-per-wave
+// kernel, 330 lane moves per wave.)
+template <int NP, typename R>
+__device__ __forceinline__ void lb_scan(const RefPair<R> *sh_c, const R (&x)[NP], const R (&y)[NP], int (&m)[NP], bool &bad) {
+    static_assert(LB_CAND == 32, "one bit per candidate");
+    unsigned w[NP];
+    R prev[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        w[i] = 0u;
+        prev[i] = R(INFINITY);  // (candidate 0 is compared against +inf: the top bit, counted off below)
+    }
+#pragma unroll
+    for (int q0 = 0; q0 < LB_CAND / 2; q0 += 4) {
+        RefPair<R> rp[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rp[j] = sh_c[q0 + j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int i = 0; i < NP; ++i) {
+                bool g0, g1;
+                lb_pair(rp[j], x[i], y[i], prev[i], g0, g1);
+                w[i] = w[i] + w[i] + (g0 ? 1u : 0u);
+                w[i] = w[i] + w[i] + (g1 ? 1u : 0u);
+            }
+        }
+    }
+    bad = false;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int pc = __popc(w[i]);
+        m[i] = pc - 1;
+        // (an idle position: w = 0, nothing to check)
+        bad |= pc > 0 && w[i] != (0xffffffffu << (32 - pc));
+    }
+}
+
 }  // namespace mppi

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -152,7 +153,8 @@ template <typename R> struct KParams {
     int n_agents, layout;   // layout: rollout_layout() of the handle (host side only)
     // MPPI_WAYPOINT_PER_ROLLOUT: the index threads through a sample's own cost calls (as `sequential` threads it through
     // all samples' calls) and starts from the x0 call's index at every sample: samples stay independent
-    int per_rollout, pad_pr;
+    int per_rollout;
+    int lb_timeout;         // ticks of the 100 MHz clock a look-back may wait (lb_wait; Switches::lb_timeout_ticks), 0: not at all
     // one-launch resolution of the sequential index (see LB_CAND)
     int hyp;                // the look-back serves the handle (lookback_serves, mppi_capi.hip) and the index can still move:
                             // what the rollout planners read; RolloutPlan::lookback says whether the launch they picked publishes words
@@ -165,6 +167,10 @@ template <typename R> struct KParams {
     const AgentScene *scenes;
     long long pad_scenes[3];
 };
+// (lb_timeout took the place of a padding word: the layout the kernels' argument loads were tuned for stays as it was)
+static_assert(sizeof(KParams<float>) == 424 && sizeof(KParams<double>) == 576, "KParams layout");
+static_assert(offsetof(KParams<float>, hyp) == 376 && offsetof(KParams<double>, hyp) == 528, "KParams layout");
+static_assert(offsetof(KParams<float>, scenes) == 392 && offsetof(KParams<double>, scenes) == 544, "KParams layout");
 
 struct FinalizeParams {
     int T, K, n_part, pad2;
@@ -263,6 +269,7 @@ struct Switches {
     // (-1 the default form, 0 "4x64", 1 "8x64")
     struct Mlp { bool f32 = false; int terms = 3, form = -1; } mlp;
     long long exchange_timeout_ms = 0;   // MPPI_EXCHANGE_TIMEOUT_MS (> 0: set)
+    int lb_timeout_ticks = (int)LB_TIMEOUT_TICKS;  // MPPI_LB_TIMEOUT_TICKS (>= 0; 0: a look-back never waits -- see lb_wait)
 };
 
 // One kernel launch, resolved once: which instantiation and how it is launched.  Made by the planners -- plan_rollout, plan_merge,

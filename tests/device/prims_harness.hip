@@ -1,4 +1,5 @@
-// Test-only harness around the device primitives (mathfn.h, wave_ops.h, philox.h, mppi_device.h): libmppi_prims.so.
+// Test-only harness around the device primitives (mathfn.h, wave_ops.h, philox.h, mppi_device.h -- the pieces of the
+// one-launch waypoint index, lb_*, among them): libmppi_prims.so.
 // Every entry point takes HOST pointers, allocates, copies in, launches one tiny kernel, synchronises, copies out, frees and
 // returns the hipError_t as an int.  Wave-level kernels run as ONE block of 64 threads with every lane active; the search
 // kernels only STORE the index a search returns and never use it as an address.  tests/test_gpu_primitives.py drives it.
@@ -303,6 +304,87 @@ __global__ __launch_bounds__(256) void k_sample(unsigned seed_lo, unsigned seed_
 
 constexpr int SAMPLER_MAX = 1 << 20;
 
+// ------------------------------------------------------------------------------------------ look-back pieces
+// lb_scan: thread i owns positions NP i .. NP i + NP - 1 (one past n: idle, x = NaN); every block stages the 32 candidates in
+// sh_c as the rollout kernels do (thread j writes its candidate into its pair).  m[n]; bad[n]: the lane's flag (NP = 2: the OR
+// over its pair, stored at both positions)
+template <int NP, typename R> __global__ __launch_bounds__(64) void k_lb_scan(const R *cand, const R *pos, int n, int *m_out, int *bad_out) {
+    __shared__ RefPair<R> sh_c[LB_CAND / 2];
+    if (threadIdx.x < LB_CAND) {
+        const int j = threadIdx.x;
+        R *pair = reinterpret_cast<R *>(&sh_c[j >> 1]);  // {x_2q, x_2q+1, y_2q, y_2q+1}
+        pair[j & 1] = cand[2 * j];
+        pair[2 + (j & 1)] = cand[2 * j + 1];
+    }
+    __syncthreads();
+    const int first = NP * (blockIdx.x * 64 + threadIdx.x);
+    R xs[NP], ys[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const bool have = first + i < n;
+        xs[i] = have ? pos[2 * (first + i)] : R(NAN);
+        ys[i] = have ? pos[2 * (first + i) + 1] : R(0);
+    }
+    int m[NP];
+    bool bad;
+    lb_scan<NP, R>(sh_c, xs, ys, m, bad);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        if (first + i < n) {
+            m_out[first + i] = m[i];
+            bad_out[first + i] = bad ? 1 : 0;
+        }
+    }
+}
+
+template <typename R> int run_lb_scan(int np, const R *cand, const R *pos, int n, int *m, int *bad) {
+    if ((np != 1 && np != 2) || n < 1 || n > (1 << 20) || n % np) return (int)hipErrorInvalidValue;
+    Scope sc;
+    R *dc, *dp;
+    int *dm, *db;
+    CK(sc.in(dc, cand, (size_t)LB_CAND * 2));
+    CK(sc.in(dp, pos, (size_t)n * 2));
+    CK(sc.out(dm, n));
+    CK(sc.out(db, n));
+    const int blocks = (n / np + 63) / 64;
+    if (np == 1) k_lb_scan<1, R><<<blocks, 64>>>(dc, dp, n, dm, db);
+    else k_lb_scan<2, R><<<blocks, 64>>>(dc, dp, n, dm, db);
+    CK(finish(m, dm, n));
+    return (int)hipMemcpy(bad, db, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
+}
+
+__global__ __launch_bounds__(256) void k_lb_reach(const int *tab, int n, int *out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = lb_reach(tab[4 * i], tab[4 * i + 1], tab[4 * i + 2], tab[4 * i + 3]) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void k_lb_tag(const unsigned *seq, int n, unsigned *out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = lb_tag(seq[i]);
+}
+
+// Workgroup b (one wave) publishes word[b] unless skip[b], then waits for the words of [0, b) under `tag` for at most `limit`
+// ticks: out[b] = {ok, E, bad, every lane returned the same}.  Every wait ends by its own clock (lb_wait).
+__global__ __launch_bounds__(64) void k_lb_exchange(unsigned *slots, const unsigned *word, const int *skip, unsigned tag, int limit,
+                                                    int *out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (!skip[b]) lb_publish(slots, b, word[b], lane);
+    int E = -1;
+    bool bad = true;
+    const bool ok = lb_wait(slots, b, tag, lane, E, bad, limit);
+    const int mine = (ok ? 1 : 0) | (bad ? 2 : 0) | (E << 2);
+    const int same = __all(mine == wv::read_lane(mine, 0));
+    if (lane == 0) {
+        out[4 * b] = ok ? 1 : 0;
+        out[4 * b + 1] = E;
+        out[4 * b + 2] = bad ? 1 : 0;
+        out[4 * b + 3] = same;
+    }
+}
+
+constexpr int LB_SLOT_WORDS = LB_COPIES * LB_COPY_STRIDE;
+constexpr int LB_LIMIT_MAX = 1000000;  // 10 ms at 100 MHz: what a launch of this harness may wait at the most
+
 }  // namespace
 
 extern "C" {
@@ -392,6 +474,49 @@ int prims_sample(unsigned seed_lo, unsigned seed_hi, unsigned iter, const unsign
     const Chol ch = {{chol[0], chol[1], chol[2]}};
     if (n) k_sample<<<(n + 255) / 256, 256>>>(seed_lo, seed_hi, iter, dk, dt, stream, ch, dout, n);
     return (int)finish(e, dout, (size_t)n * 2);
+}
+
+// candidates [32][2], positions [n][2] (n a multiple of np, np 1 or 2: positions per lane) -> m[n], bad[n]
+int prims_lb_scan_f32(int np, const float *cand, const float *pos, int n, int *m, int *bad) { return run_lb_scan(np, cand, pos, n, m, bad); }
+int prims_lb_scan_f64(int np, const double *cand, const double *pos, int n, int *m, int *bad) { return run_lb_scan(np, cand, pos, n, m, bad); }
+
+// tab [n][4] = {leave, window, n_ref, c} -> out[n] = 0 / 1
+int prims_lb_reach(const int *tab, int n, int *out) {
+    if (n < 1 || n > (1 << 20)) return (int)hipErrorInvalidValue;
+    Scope sc;
+    int *dt, *dout;
+    CK(sc.in(dt, tab, (size_t)n * 4));
+    CK(sc.out(dout, n));
+    k_lb_reach<<<(n + 255) / 256, 256>>>(dt, n, dout);
+    return (int)finish(out, dout, n);
+}
+
+int prims_lb_tag(const unsigned *seq, int n, unsigned *out) {
+    if (n < 1 || n > (1 << 20)) return (int)hipErrorInvalidValue;
+    Scope sc;
+    unsigned *ds, *dout;
+    CK(sc.in(ds, seq, n));
+    CK(sc.out(dout, n));
+    k_lb_tag<<<(n + 255) / 256, 256>>>(ds, n, dout);
+    return (int)finish(out, dout, n);
+}
+
+int prims_lb_slot_words(void) { return LB_SLOT_WORDS; }
+int prims_lb_default_limit(void) { return (int)LB_TIMEOUT_TICKS; }
+// word[B], skip[B]; slots [LB_COPIES * LB_COPY_STRIDE]: what the buffer holds before the launch, returned whole after it;
+// out [B][4] = {ok, E, bad, lanes agree}
+int prims_lb_exchange(int B, const unsigned *word, const int *skip, unsigned tag, int limit, unsigned *slots, int *out) {
+    if (B < 1 || B > HYP_MAX_BLOCKS || limit < 0 || limit > LB_LIMIT_MAX) return (int)hipErrorInvalidValue;
+    Scope sc;
+    unsigned *dw, *dslots;
+    int *dskip, *dout;
+    CK(sc.in(dw, word, B));
+    CK(sc.in(dskip, skip, B));
+    CK(sc.in(dslots, slots, LB_SLOT_WORDS));
+    CK(sc.out(dout, (size_t)B * 4));
+    k_lb_exchange<<<B, 64>>>(dslots, dw, dskip, tag, limit, dout);
+    CK(finish(out, dout, (size_t)B * 4));
+    return (int)hipMemcpy(slots, dslots, (size_t)LB_SLOT_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-"""Inputs, f64 references and comparisons for the device primitives (mathfn.h, wave_ops.h, philox.h, mppi_device.h) as
+"""Inputs, f64 references and comparisons for the device primitives (mathfn.h, wave_ops.h, philox.h, mppi_device.h -- the
+pieces of the one-launch waypoint index, lb_*, among them) as
 tests/device/prims_harness.hip exposes them.  TEST INFRASTRUCTURE: tests/test_gpu_primitives.py asserts on what these
 functions return, tools/prims_report.py prints the same figures.
 
@@ -21,6 +22,11 @@ SEARCH_ROWS = ("window", "lds", "split2", "split4", "split8", "split16", "unifor
 WORDS = (0, 0x1FF, 0x200, 0x7FFFFFFF, 0x80000000, 0xFFFFFE00, 0xFFFFFFFF)
 SIGMA = np.array([[0.5, 0.1], [0.1, 0.2]])
 
+
+# the words of the one-launch waypoint index (mppi_kernels.h)
+LB_CAND, LB_BAD, LB_COPIES, LB_COPY_STRIDE = 32, 0x80, 8, 2048
+LB_SLOT_WORDS, LB_TAG_MASK, LB_MAX_BLOCKS = LB_COPIES * LB_COPY_STRIDE, 0xFFFFFF00, 512
+LB_ABSENT = 1e30  # a candidate beyond the path's end, as the kernels stage it
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
@@ -124,6 +130,51 @@ class Prims:
                    C.c_int(poses.shape[0]), _p(o))
         assert set(np.unique(o)) <= {0, 1}
         return o.astype(bool)
+
+    # ---- look-back pieces (lb_* of mppi_device.h)
+    def lb_scan(self, positions_per_lane, cand, pos):
+        """candidates [32][2], positions [n][2] -> (m int32[n], bad bool[n]); two positions per lane: n is padded with an idle
+        position (x = NaN) to an even count, and `bad` is the lane's flag at both of its positions"""
+        cand = np.ascontiguousarray(cand)
+        pos = np.ascontiguousarray(pos, cand.dtype)
+        assert cand.shape == (LB_CAND, 2) and pos.ndim == 2 and pos.shape[1] == 2
+        n = pos.shape[0]
+        if n % positions_per_lane:
+            pos = np.concatenate([pos, np.array([[np.nan, 0.0]], cand.dtype)])
+        m, bad = np.empty(pos.shape[0], I32), np.empty(pos.shape[0], I32)
+        self._call("prims_lb_scan_" + _sfx(cand.dtype), C.c_int(positions_per_lane), _p(cand), _p(pos), C.c_int(pos.shape[0]),
+                   _p(m), _p(bad))
+        assert set(np.unique(bad)) <= {0, 1}
+        return m[:n], bad[:n].astype(bool)
+
+    def lb_reach(self, table):
+        table = np.ascontiguousarray(table, I32)
+        assert table.ndim == 2 and table.shape[1] == 4
+        o = np.empty(table.shape[0], I32)
+        self._call("prims_lb_reach", _p(table), C.c_int(table.shape[0]), _p(o))
+        assert set(np.unique(o)) <= {0, 1}
+        return o.astype(bool)
+
+    def lb_tag(self, seq):
+        seq = np.ascontiguousarray(seq, U32)
+        o = np.empty(seq.size, U32)
+        self._call("prims_lb_tag", _p(seq), C.c_int(seq.size), _p(o))
+        return o
+
+    def lb_default_limit(self):
+        return int(self.lib.prims_lb_default_limit())
+
+    def lb_exchange(self, words, skip, tag, limit, slots):
+        """B one-wave workgroups in one launch -> (ok bool[B], E int[B], bad bool[B], slots after the launch)"""
+        words, skip = np.ascontiguousarray(words, U32), np.ascontiguousarray(skip, I32)
+        slots = np.array(slots, U32)  # (a copy: the call returns the buffer in place)
+        assert self.lib.prims_lb_slot_words() == LB_SLOT_WORDS == slots.size and words.shape == skip.shape
+        o = np.empty((words.size, 4), I32)
+        self._call("prims_lb_exchange", C.c_int(words.size), _p(words), _p(skip), C.c_uint(int(tag)), C.c_int(limit), _p(slots),
+                   _p(o))
+        assert (o[:, 3] == 1).all(), "the lanes of a wave disagree on what lb_wait returned"
+        assert set(np.unique(o[:, [0, 2]])) <= {0, 1}
+        return o[:, 0].astype(bool), o[:, 1].copy(), o[:, 2].astype(bool), slots
 
     # ---- sampler
     def philox(self, ctr, key):
@@ -407,6 +458,174 @@ def collision_check(P, n_obs, dtype):
                      "flips_inside": int((flip & (mar <= COLLISION_MARGIN)).sum()),
                      "frac_outside": float((mar > COLLISION_MARGIN).mean()), "frac_hit": float(hit.mean())}
     return res
+
+
+# ------------------------------------------------------------------------------------------ look-back pieces
+F32_OVERFLOW = 2.0 ** 128 - 2.0 ** 103  # from here on a float result rounds to +inf
+
+
+def lb_distances(cand, pos):
+    """d[call][candidate] in f64 from the inputs widened to f64.  For float inputs a distance beyond the format's range is +inf,
+    as the device has it (an absent candidate, a position of 1e20); the inputs keep every other distance far below that."""
+    c, q = np.asarray(cand).astype(F64), np.asarray(pos).astype(F64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        d = (q[:, None, 0] - c[None, :, 0]) ** 2 + (q[:, None, 1] - c[None, :, 1]) ** 2
+    if np.asarray(cand).dtype == F32:
+        fin = d[np.isfinite(d)]
+        assert not ((fin > 1e30) & (fin < 1e39)).any()  # (nothing near the threshold, where the order of rounding would matter)
+        d = np.where(d >= F32_OVERFLOW, np.inf, d)
+    return d
+
+
+def lb_scan_reference(cand, pos):
+    """(m, bad, descent bits[call][32], smallest relative gap between consecutive finite candidate distances per call).
+    g_j = d_j < d_(j-1) with d_(-1) = +inf; m = popcount(g) - 1; bad unless the set bits are a prefix.  Where a call has a
+    descent and is not bad, m is its first minimum -- asserted here, it is what the kernels rely on."""
+    d = lb_distances(cand, pos)
+    with np.errstate(invalid="ignore"):
+        prev = np.concatenate([np.full((d.shape[0], 1), np.inf), d[:, :-1]], axis=1)
+        g = d < prev
+        both = np.isfinite(d) & np.isfinite(prev)
+        gap = np.where(both, np.abs(d - prev) / np.maximum(np.maximum(d, prev), np.finfo(F64).tiny), np.inf).min(axis=1)
+    pcnt = g.sum(axis=1)
+    m = (pcnt - 1).astype(I32)
+    bad = (g[:, 1:] & ~g[:, :-1]).any(axis=1)  # a descent behind a non-descent
+    good = ~bad & (pcnt > 0)
+    assert (m[good] == np.argmin(d[good], axis=1)).all()
+    return m, bad, g, gap
+
+
+def lb_pairs_bad(bad):
+    """the flag of a lane that owns positions 2i and 2i + 1, at both of them"""
+    b = np.concatenate([bad, [False] * (bad.size % 2)]).reshape(-1, 2).any(axis=1)
+    return np.repeat(b, 2)[:bad.size]
+
+
+def _row(xy, nc=LB_CAND):
+    r = np.full((LB_CAND, 2), LB_ABSENT)
+    r[:nc] = np.asarray(xy, F64)[:nc]
+    return r
+
+
+def lb_lattice_rows():
+    """{name: candidates[32][2]}: integers and quarters, so that every distance and every comparison is exact in float"""
+    j = np.arange(LB_CAND, dtype=F64)
+    line = np.stack([j, np.zeros(LB_CAND)], 1)
+    rows = {"line": line}
+    # every second candidate repeats the one before it: exact ties between consecutive candidates
+    rows["ties"] = np.stack([np.floor(j / 2), np.zeros(LB_CAND)], 1)
+    # out for 16 candidates, back beside them for 16: the descents resume after a rise
+    rows["fold"] = np.stack([np.where(j < 16, j, 31 - j), np.where(j < 16, 0.0, 1.0)], 1)
+    # away from everything the positions cover and a last candidate one step back: the only descent behind the first bit
+    last = line.copy()
+    last[:, 0] += 40.0
+    last[31, 0] = 69.5
+    rows["last_only"] = last
+    rows["quarter_steps"] = np.stack([0.25 * j, 0.5 * (j % 2)], 1)
+    for nc in (2, 5, 31, 32):
+        rows[f"line_nc{nc}"] = _row(line, nc)
+        rows[f"fold_nc{nc}"] = _row(rows["fold"], nc)
+    return rows
+
+
+def lb_lattice_positions():
+    """[n][2]: a quarter grid over and around the candidates (positions on a candidate, positions halfway between two), before
+    the first candidate, beyond the last, and one idle position"""
+    x, y = np.meshgrid(np.arange(-4.0, 36.01, 0.25), np.array([-2.0, -0.25, 0.0, 0.5, 1.0, 3.0]), indexing="ij")
+    grid = np.stack([x.ravel(), y.ravel()], 1)
+    return np.concatenate([grid, [[-3.0, 0.0], [40.0, 0.0], [np.nan, 0.0]]])
+
+
+LB_NONFINITE = ((np.nan, 0.0), (np.inf, 0.0), (0.0, np.nan), (1e20, 0.0))  # the first: an idle position
+
+
+def lb_nonfinite_positions(dtype):
+    q = LB_NONFINITE if dtype == F32 else LB_NONFINITE[:3]  # 1e20: d^2 overflows in f32 only
+    return np.array(q, dtype)
+
+
+LB_REAL_N, LB_REAL_SIGMA, LB_REAL_SEED = 4096, 0.3, 71
+LB_GAP = {F32: 1e-5, F64: 1e-13}  # one float distance carries about 2e-7 relative error: a bit is certain beyond 4e-7; 25 x that
+LB_LEFT_OUT_MAX = 0.02
+
+
+def lb_real_case(dtype):
+    """(candidates, positions) in `dtype`: 32 candidates 0.25 apart on an arc of radius 12, positions scattered around them
+    with sigma = 0.3"""
+    rng = np.random.default_rng(LB_REAL_SEED)
+    a = 0.25 * np.arange(LB_CAND) / 12.0
+    cand = np.stack([12.0 * np.sin(a), 12.0 * (1.0 - np.cos(a))], 1)
+    pos = cand[rng.integers(0, LB_CAND, LB_REAL_N)] + rng.normal(0.0, LB_REAL_SIGMA, (LB_REAL_N, 2))
+    return cand.astype(dtype), pos.astype(dtype)
+
+
+def lb_real_reference(dtype):
+    """(candidates, positions, m, bad, compared[call]): `compared` is False where two consecutive candidate distances of the call
+    differ by less than LB_GAP relative in f64 -- there a rounded distance may order them otherwise"""
+    cand, pos = lb_real_case(dtype)
+    m, bad, _, gap = lb_scan_reference(cand, pos)
+    return cand, pos, m, bad, gap >= LB_GAP[dtype]
+
+
+def lb_reach_table():
+    """(table[n][4] = {leave, window, n_ref, c}, want[n]): the exactness argument stated by brute force -- every index p the
+    workgroup's calls may have been entered at, 0 .. leave, keeps its window inside the candidates (or the path ends first),
+    and the index stays below the window"""
+    rows, want = [], []
+    for W in (10, 20):
+        for rem in (2, 20, 32, 33, 100):
+            for c in (0, 7):
+                for leave in range(41):
+                    rows.append((leave, W, c + rem, c))
+                    want.append(leave < W and all(min(p + W, rem) <= LB_CAND for p in range(leave + 1)))
+    return np.array(rows, I32), np.array(want)
+
+
+def lb_reach_reference(leave, W, n_ref, c):
+    return bool(leave < W and all(min(p + W, n_ref - c) <= LB_CAND for p in range(leave + 1)))
+
+
+def lb_tag_reference(seq):
+    return (np.asarray(seq, np.uint64) & 0xFFFFFF) << 8
+
+
+LB_EXCHANGE_B = (1, 2, 4, 5, 8, 9, 255, 256, 257, 511, 512)
+
+
+def lb_exchange_words(B, tag, marks, seed=81):
+    """(words[B], offset[B], badbit[B]): random offsets 0 .. 127 under `tag`, the bad bit at the workgroups `marks` names"""
+    rng = np.random.default_rng(seed + B)
+    off = rng.integers(0, 128, B)
+    off[rng.integers(0, B)] = 127  # (the whole offset field somewhere)
+    badbit = np.zeros(B, bool)
+    badbit[[b for b in marks if 0 <= b < B]] = True
+    return (np.uint64(tag) | (badbit * LB_BAD).astype(np.uint64) | off.astype(np.uint64)).astype(U32), off, badbit
+
+
+def lb_exchange_marks(B):
+    """{name: workgroups whose word carries the bad bit}"""
+    rng = np.random.default_rng(82 + B)
+    return {"none": [], "first": [0], "last_read": [B - 2], "last": [B - 1],
+            "sparse": sorted(set(rng.integers(0, B, max(1, B // 40)).tolist()))}
+
+
+def lb_exchange_reference(off, badbit, published):
+    """(ok, E, bad) per workgroup: b waits for [0, b); it gives up where one of them never publishes"""
+    B = off.size
+    ok = np.array([published[:b].all() for b in range(B)])
+    E = np.array([off[:b].max() if b and ok[b] else 0 for b in range(B)])
+    bad = np.array([bool(badbit[:b].any()) and ok[b] for b in range(B)])
+    return ok, E, bad
+
+
+def lb_slots(fill=0):
+    return np.full(LB_SLOT_WORDS, fill, U32)
+
+
+def lb_published_everywhere(slots, words, published):
+    """every copy of the returned buffer holds the words of the workgroups that published"""
+    copies = slots.reshape(LB_COPIES, LB_COPY_STRIDE)[:, :words.size]
+    return bool((copies[:, published] == words[None, published]).all())
 
 
 # ------------------------------------------------------------------------------------------ sampler

@@ -1,8 +1,10 @@
-"""The device primitives at their edges, one by one: mathfn.h, wave_ops.h, philox.h and the searches and collision tests of
-mppi_device.h, through the test-only harness tests/device/prims_harness.hip (libmppi_prims.so, the product's compiler flags).
+"""The device primitives at their edges, one by one: mathfn.h, wave_ops.h, philox.h and the searches, the collision tests and
+the pieces of the one-launch waypoint index (lb_scan, lb_reach, lb_tag, lb_publish / lb_wait) of mppi_device.h, through the
+test-only harness tests/device/prims_harness.hip (libmppi_prims.so, the product's compiler flags).
 Inputs, f64 references and comparisons live in tests/prims_checks.py; tools/prims_report.py prints the figures these tests
 bound (profiles/prims_measured.json).  The search kernels only store the index a search returns, so a wrong index is a
-failed assertion here and never an address."""
+failed assertion here and never an address.  The look-back exchange runs B one-wave workgroups whose waits end by their own
+clock and return a status: a word that never arrives is a result (ok = 0), not a hang."""
 import numpy as np
 import pytest
 
@@ -256,6 +258,126 @@ def test_collision_tests_agree_with_f64_outside_the_margin(P, n_obs, dtype):
     for name, r in res.items():
         assert r["frac_outside"] >= 0.95 and 0.0 < r["frac_hit"] < 1.0, (name, r)  # the scene discriminates (f64 alone)
         assert r["flips_outside"] == 0, (name, r)
+
+
+# ------------------------------------------------------------------------------------------ look-back pieces
+def _lb_mismatches(tag, got_m, got_bad, m, bad, where=None):
+    where = np.ones(m.size, bool) if where is None else where
+    wrong = where & ((got_m != m) | (got_bad != bad))
+    return [f"{tag}: call {i} got m {int(got_m[i])} bad {int(got_bad[i])}, want {int(m[i])} {int(bad[i])}"
+            for i in np.nonzero(wrong)[0][:4]]
+
+
+@pytest.mark.parametrize("dtype", FP)
+def test_lb_scan_on_a_lattice_bitwise(P, dtype):
+    """Exact distances: ties between consecutive candidates (no descent), positions on a candidate, rows that fold back (bad),
+    a descent at the first candidate only, at the last only, at all 32, absent candidates from nc on -- m and bad of every
+    call, one and two positions per lane."""
+    pos = pc.lb_lattice_positions().astype(dtype)
+    wrong = []
+    for name, row in pc.lb_lattice_rows().items():
+        cand = row.astype(dtype)
+        m, bad, _, _ = pc.lb_scan_reference(cand, pos)
+        m1, bad1 = P.lb_scan(1, cand, pos)
+        m2, bad2 = P.lb_scan(2, cand, pos)
+        wrong += _lb_mismatches(f"{name} NP=1", m1, bad1, m, bad) + _lb_mismatches(f"{name} NP=2", m2, bad2, m, pc.lb_pairs_bad(bad))
+        assert np.array_equal(m1, m2), name
+    assert not wrong, wrong[:12]
+
+
+@pytest.mark.parametrize("dtype", FP)
+def test_lb_scan_non_finite_positions(P, dtype):
+    """An idle position (x = NaN) counts nothing: m = -1 and no flag.  (inf, 0), (0, NaN) and, for float, (1e20, 0), whose
+    squared distance overflows: m stays in [-1, 31] and equals the reference's bits."""
+    pos = pc.lb_nonfinite_positions(dtype)
+    for name in ("line", "fold", "line_nc5"):
+        cand = pc.lb_lattice_rows()[name].astype(dtype)
+        m, bad, _, _ = pc.lb_scan_reference(cand, pos)
+        assert m[0] == -1 and not bad[0]
+        for positions_per_lane in (1, 2):
+            gm, gb = P.lb_scan(positions_per_lane, cand, pos)
+            assert ((gm >= -1) & (gm <= 31)).all(), (name, gm)
+            assert np.array_equal(gm, m), (name, positions_per_lane, gm, m)
+            assert np.array_equal(gb, bad if positions_per_lane == 1 else pc.lb_pairs_bad(bad)), (name, positions_per_lane, gb)
+
+
+@pytest.mark.parametrize("dtype", FP)
+def test_lb_scan_on_real_data_outside_the_margin(P, dtype):
+    """Positions scattered (sigma 0.3) around a gently curved stretch of 32 candidates: every call whose consecutive candidate
+    distances differ by more than LB_GAP relative in f64 must give the reference's m and bad; at most 2 % may be left out."""
+    cand, pos, m, bad, compared = pc.lb_real_reference(dtype)
+    left_out = 1.0 - float(compared.mean())
+    print("lb_scan real data: share left out", left_out)
+    assert left_out <= pc.LB_LEFT_OUT_MAX
+    m1, bad1 = P.lb_scan(1, cand, pos)
+    m2, bad2 = P.lb_scan(2, cand, pos)
+    assert np.array_equal(m1, m2)
+    wrong = _lb_mismatches("NP=1", m1, bad1, m, bad, compared)
+    pair_ok = pc.lb_pairs_bad(~compared) == 0  # a pair's flag is compared where both of its calls are
+    wrong += _lb_mismatches("NP=2", m2, bad2, m, pc.lb_pairs_bad(bad), compared & pair_ok)
+    assert not wrong, wrong
+
+
+def test_lb_reach_is_the_exactness_argument(P):
+    table, want = pc.lb_reach_table()
+    assert 0.2 < want.mean() < 0.8  # (the table discriminates)
+    got = P.lb_reach(table)
+    assert np.array_equal(got, want), table[got != want][:8]
+
+
+def test_lb_tag_keeps_the_low_byte_free_and_aliases_after_2_24(P):
+    seq = np.array([1, 0xFFFFFF, 0x1000001, 0xFFFFFFFF], np.uint64)
+    tag = P.lb_tag(seq)
+    assert np.array_equal(tag, pc.lb_tag_reference(seq).astype(U32))
+    assert ((tag & 0xFF) == 0).all() and (tag != 0).all()
+    assert tag[2] == tag[0]  # the aliasing period: 2^24 launch pairs
+
+
+LB_TAG = 0x00ABCD00
+
+
+@pytest.mark.parametrize("B", pc.LB_EXCHANGE_B)
+def test_lb_exchange_of_fresh_words(P, B):
+    """Every workgroup publishes: b reads the largest offset and any bad bit of [0, b), workgroup 0 nothing, and all 8 copies
+    hold the words.  (256 / 257: the lane's second 16-byte load; 4 / 5: the four words of a lane.)"""
+    for name, marks in pc.lb_exchange_marks(B).items():
+        words, off, badbit = pc.lb_exchange_words(B, LB_TAG, marks)
+        published = np.ones(B, bool)
+        want_ok, want_E, want_bad = pc.lb_exchange_reference(off, badbit, published)
+        assert want_ok.all() and want_E[0] == 0 and not want_bad[0]
+        ok, E, bad, slots = P.lb_exchange(words, ~published, LB_TAG, P.lb_default_limit(), pc.lb_slots(0))
+        assert ok.all(), (name, np.nonzero(~ok)[0][:8])
+        assert np.array_equal(E, want_E), (name, np.nonzero(E != want_E)[0][:8])
+        assert np.array_equal(bad, want_bad), (name, np.nonzero(bad != want_bad)[0][:8])
+        assert pc.lb_published_everywhere(slots, words, published), name
+
+
+@pytest.mark.parametrize("B", [5, 16])
+def test_lb_exchange_never_takes_a_stale_word(P, B):
+    """The buffer holds words of another launch pair -- offset 127, bad bit -- and workgroup s never publishes: everyone up to
+    s reads fresh words only, everyone behind s gives up after 2000 ticks (20 us)."""
+    stale = pc.lb_slots((LB_TAG ^ 0x5500) | pc.LB_BAD | 127)
+    for s in (0, 3, B - 1):
+        words, off, badbit = pc.lb_exchange_words(B, LB_TAG, [])
+        off = np.minimum(off, 100)  # (below the stale offset, so that a leak shows)
+        words = ((words & pc.LB_TAG_MASK) | off).astype(U32)
+        published = np.arange(B) != s
+        want_ok, want_E, want_bad = pc.lb_exchange_reference(off, badbit, published)
+        assert np.array_equal(want_ok, np.arange(B) <= s) and not want_bad.any()
+        ok, E, bad, slots = P.lb_exchange(words, ~published, LB_TAG, 2000, stale)
+        assert np.array_equal(ok, want_ok), (s, ok)
+        assert np.array_equal(E, want_E) and np.array_equal(bad, want_bad), (s, E, bad)
+        assert pc.lb_published_everywhere(slots, words, published), s
+        assert (slots.reshape(pc.LB_COPIES, -1)[:, s] == stale[0]).all(), s
+
+
+def test_lb_exchange_with_limit_0_gives_up_before_the_first_poll(P):
+    for B in (1, 9):
+        words, off, badbit = pc.lb_exchange_words(B, LB_TAG, [])
+        ok, E, bad, slots = P.lb_exchange(words, np.zeros(B, I32), LB_TAG, 0, pc.lb_slots(0))
+        assert np.array_equal(ok, np.arange(B) == 0), ok
+        assert (E == 0).all() and not bad.any()
+        assert pc.lb_published_everywhere(slots, words, np.ones(B, bool))
 
 
 # ------------------------------------------------------------------------------------------ sampler

@@ -35,6 +35,14 @@ def main():
     rep["collision"] = {"margin": pc.COLLISION_MARGIN, "poses": pc.N_POSES,
                         "flips": {f"{pc._sfx(t)}_n_obs_{n}": pc.collision_check(P, n, t) for t in (np.float32, np.float64)
                                   for n in pc.N_OBS}}
+    rep["lb_scan"] = {}
+    for t in (np.float32, np.float64):
+        cand, pos, m, bad, compared = pc.lb_real_reference(t)
+        gm, gb = P.lb_scan(1, cand, pos)
+        rep["lb_scan"][pc._sfx(t)] = {"calls": int(m.size), "margin": pc.LB_GAP[t], "share_left_out": float(1.0 - compared.mean()),
+                                      "bound_share_left_out": pc.LB_LEFT_OUT_MAX,
+                                      "mismatches_compared": int((compared & ((gm != m) | (gb != bad))).sum()),
+                                      "mismatches_left_out": int((~compared & ((gm != m) | (gb != bad))).sum())}
     text = json.dumps(rep, indent=1)
     print(text)
     if args.out:
