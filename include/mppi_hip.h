@@ -112,7 +112,10 @@ typedef struct {
     int32_t clamp_rollout;       /* `_g` inside the rollout (off only in mppi_differential_drive_torch.py:128) */
     int32_t clamp_u_after_update;/* in-place clamp of u by the visualisation loop (mppi_differential_drive.py:145-149) */
     int32_t filter_mode;         /* mppi_filter_mode */
-    int32_t filter_window;       /* 10 */
+    int32_t filter_window;       /* 10 in every reference file; any window >= 1 is served (< 1 => 10).  DIFFDRIVE needs
+                                    T >= window, RACECAR and TORCH T >= (window + 1) / 2 (they pad with the last
+                                    -(-window // 2) rows: one more than window / 2 at an odd window); shorter horizons, at
+                                    which the reference's own filter raises, are MPPI_ERR_SHAPE */
     int32_t obstacle_model;      /* mppi_obstacle_model */
     int32_t raise_at_path_end;   /* 1: mppi_step returns MPPI_ERR_PATH_END (mppi_race_car.py:63-65) */
     double safety_margin;        /* diff: safety_margin_rate; race: collision_safety_margin_rate */

@@ -2,9 +2,9 @@
 
 Run in the build container only (``/root/reference`` does not exist on the GPU box):
 
-    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py dd rc paths filters c5 vehicle ddtorch
+    MPLBACKEND=Agg PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py dd rc paths filters filters_windows c5 vehicle ddtorch
 
-(every generator; each name selects one, no name = `dd rc paths`; all 28 committed fixtures regenerate bit for bit)
+(every generator; each name selects one, no name = `dd rc paths`; all 29 committed fixtures regenerate bit for bit)
 
 It imports ``/root/reference/controllers/mppi_*.py`` unmodified, replaces the instance's
 ``_calc_epsilon`` with an injected noise tensor (recipe: SURVEY.md section 8c), spies on
@@ -315,6 +315,40 @@ def gen_filters():
 
 if __name__ == "__main__" and "filters" in sys.argv[1:]:
     gen_filters()
+
+
+FILTER_WINDOWS = (3, 4, 5, 9, 11)
+
+
+def gen_filters_windows():
+    """The same three filters at windows other than the 10 every reference file passes: {3, 4, 5, 9, 11} x horizons
+    {W, W + 1, 2 W + 3}, and (W + 1) // 2 -- the shortest the padded variants accept -- for the race-car and torch forms
+    (np.convolve 'same' makes the diff-drive form raise below T = W).  Odd windows matter: `xx[-kernel_size//2:]`
+    (mppi_race_car.py:219) is the last W // 2 + 1 rows there, not the last W // 2."""
+    import torch
+    from controllers.mppi_differential_drive import MPPIAlgorithms as DD
+    from controllers.mppi_race_car import MPPIRacecarController as RC
+    from controllers.mppi_differential_drive_torch import MPPIAlgorithms as DDT
+    from controllers.mppi_race_car_torch import MPPIRacecarController as RCT
+    rng = np.random.default_rng(20240808)
+    arrays, cases = {}, []
+    for W in FILTER_WINDOWS:
+        for T in sorted({(W + 1) // 2, W, W + 1, 2 * W + 3}):
+            xx = rng.normal(size=(T, 2))
+            key = f"W{W}_T{T}"
+            cases.append([W, T])
+            arrays[f"in_{key}"] = xx
+            if T >= W:
+                arrays[f"dd_{key}"] = DD._moving_average_filter(None, xx=xx.copy(), window_size=W)
+            arrays[f"rc_{key}"] = RC._moving_average_filter(None, xx.astype(np.float32), window_size=W)
+            xt = torch.from_numpy(xx.astype(np.float32))
+            arrays[f"ddtorch_{key}"] = DDT._moving_average_filter(None, xt.clone(), W).numpy()
+            arrays[f"rctorch_{key}"] = RCT._moving_average_filter(None, xt.clone(), W).numpy()
+    save("filters_windows", {"cases": cases, "torch": torch.__version__}, arrays)
+
+
+if __name__ == "__main__" and "filters_windows" in sys.argv[1:]:
+    gen_filters_windows()
 
 
 # ---------------------------------------------------------------------------------------

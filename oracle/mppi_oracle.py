@@ -59,30 +59,32 @@ def moving_average_diffdrive(xx: np.ndarray, window_size: int = 10) -> np.ndarra
     return xx_mean
 
 
-def moving_average_torch(xx: np.ndarray, window_size: int = 10) -> np.ndarray:
+def moving_average_torch(xx: np.ndarray, window_size: int = 10, dtype=np.float32) -> np.ndarray:
     """mppi_differential_drive_torch.py:252-263 == mppi_race_car_torch.py:211-222: the signal padded with copies of
-    its first / last window//2 rows goes through ``conv1d(padding=window//2)`` and the FIRST T outputs are kept --
-    so output n averages padded rows n-5 .. n+4 with zeros before the start, i.e. the NumPy race-car filter delayed
-    by window//2 rows (pinned by tests/golden/filters.npz; f32 like the torch files)."""
+    its first window//2 / last -(-window//2) rows goes through ``conv1d(padding=window//2)`` and the FIRST T outputs
+    are kept -- so output n averages padded rows n-5 .. n+4 with zeros before the start, i.e. the NumPy race-car filter
+    delayed by window//2 rows; the trailing copies are never read (pinned by tests/golden/filters.npz and
+    filters_windows.npz; f32 like the torch files.  ``dtype=np.float64``: the same sums in f64, for error bounds)."""
     h = window_size // 2
-    xx = np.asarray(xx, np.float32)
+    xx = np.asarray(xx, dtype)
     T = xx.shape[0]
-    padded = np.concatenate([np.zeros((h, xx.shape[1]), np.float32), xx[:h], xx, xx[T - h:]], axis=0)
+    padded = np.concatenate([np.zeros((h, xx.shape[1]), dtype), xx[:h], xx, xx[T - h:]], axis=0)
     out = np.zeros_like(xx)
-    w = np.float32(1.0 / window_size)
+    w = dtype(1.0 / window_size)
     for n in range(T):
-        acc = np.zeros(xx.shape[1], np.float32)
+        acc = np.zeros(xx.shape[1], dtype)
         for k in range(window_size):
             acc = acc + padded[n + k] * w
         out[n] = acc
     return out
 
 
-def moving_average_racecar(xx: np.ndarray, window_size: int = 10) -> np.ndarray:
-    """mppi_race_car.py:211-222 -- pad with copies of the first/last 5 rows, 'same'
-    convolution, slice the padding off.  dtype follows ``xx`` (f32 in the reference)."""
+def moving_average_racecar(xx: np.ndarray, window_size: int = 10, kernel_dtype=np.float32) -> np.ndarray:
+    """mppi_race_car.py:211-222 -- pad with copies of the first 5 / last 5 rows (``xx[-ks // 2:]``: the last
+    ks // 2 + 1 rows at an odd window), 'same' convolution, slice the padding off.  dtype follows ``xx`` (f32 in the
+    reference); the taps are f32(1 / ks) as there (``kernel_dtype=np.float64``: exact taps, for error bounds)."""
     ks = window_size
-    kernel = np.ones(ks, dtype=np.float32) / ks
+    kernel = np.ones(ks, dtype=kernel_dtype) / ks
     dim = xx.shape[1]
     xx_mean = np.zeros_like(xx)
     for d in range(dim):

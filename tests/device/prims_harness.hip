@@ -1,13 +1,15 @@
 // Test-only harness around the device primitives (mathfn.h, wave_ops.h, philox.h, mppi_device.h -- the pieces of the
 // one-launch waypoint index, lb_*, among them): libmppi_prims.so.
 // Every entry point takes HOST pointers, allocates, copies in, launches one tiny kernel, synchronises, copies out, frees and
-// returns the hipError_t as an int.  Wave-level kernels run as ONE block of 64 threads with every lane active; the search
+// returns the hipError_t as an int.  Also the rescale merge of mppi_merge.h in the product's instantiations (merge_combine<A,
+// 256, 1 / 2>, merge_abi<A>), on buffers allocated as the product allocates them.  Wave-level kernels run as ONE block of 64 threads with every lane active; the search
 // kernels only STORE the index a search returns and never use it as an address.  tests/test_gpu_primitives.py drives it.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
 #include "mppi_device.h"
+#include "mppi_merge.h"
 
 namespace {
 
@@ -385,6 +387,71 @@ __global__ __launch_bounds__(64) void k_lb_exchange(unsigned *slots, const unsig
 constexpr int LB_SLOT_WORDS = LB_COPIES * LB_COPY_STRIDE;
 constexpr int LB_LIMIT_MAX = 1000000;  // 10 ms at 100 MHz: what a launch of this harness may wait at the most
 
+// ------------------------------------------------------------------------------------------ mppi_merge.h
+// merge_combine<A, 256, NWIN> as k_merge / k_finalize call it: every load first, then the merge.  out = {rho, eta, eta2, n_hit,
+// w_eps[2T]}; want_hits 0 leaves the count out (n_hit stays -1)
+template <typename A, int NWIN>
+__global__ __launch_bounds__(MERGE_THREADS) void k_harness_combine(const A *__restrict__ recs, const A *__restrict__ heads, int n,
+                                                                   int T, A beta, int want_hits, A *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const MergeLds<A> L(smem, T, 0);
+    MergeRegs<A, MERGE_THREADS, NWIN> mr;
+    merge_load_heads<A, MERGE_THREADS, NWIN>(heads, mr);
+    merge_load_tile<A, MERGE_THREADS, NWIN>(recs, T, 0, mr);
+    A rho, eta, eta2, n_hit = want_hits ? A(0) : A(-1);
+    merge_combine<A, MERGE_THREADS, NWIN>(recs, n, T, beta, mr, L.s, L.part, rho, eta, eta2, [&](int i, A v) { out[4 + i] = v; },
+                                          &n_hit);
+    if (threadIdx.x == 0) { out[0] = rho; out[1] = eta; out[2] = eta2; out[3] = n_hit; }
+}
+
+// merge_abi<A> over n records {rho, eta, eta2, W[2T]} in doubles.  out = {rho, eta, eta2, w_eps[2T]}
+template <typename A>
+__global__ __launch_bounds__(MERGE_THREADS) void k_harness_abi(const double *__restrict__ recs, int n, int T, A beta,
+                                                               A *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const MergeLds<A> L(smem, T, 0);
+    A rho, eta, eta2;
+    merge_abi<A>(recs, n, T, beta, L.s, L.red, rho, eta, eta2, [&](int i, A v) { out[3 + i] = v; });
+    if (threadIdx.x == 0) { out[0] = rho; out[1] = eta; out[2] = eta2; }
+}
+
+constexpr int MERGE_T_MAX = 512;  // (merge_lds_elems(512, 0, 8) doubles: 22 KiB of LDS)
+
+// heads [slots][4], recs [slots][record_len(T)]: the first `slots` slots of buffers of nwin * 256 + 256 zero-filled slots -- what
+// the product allocates whatever n is (merge_load_* read whole windows unconditionally); n <= slots: the slots past n are the
+// caller's "absent" ones
+template <typename A> int run_merge_combine(int nwin, const A *heads, const A *recs, int slots, int n, int T, A beta, int want_hits, A *out) {
+    const int cap = nwin * MERGE_MAX_RECORDS + MERGE_MAX_RECORDS;
+    if (nwin < 1 || nwin > MERGE_MAX_WINDOWS || n < 1 || n > nwin * MERGE_MAX_RECORDS || slots < n || slots > cap || T < 1 ||
+        T > MERGE_T_MAX)
+        return (int)hipErrorInvalidValue;
+    const size_t rl = (size_t)record_len(T, (int)sizeof(A));
+    Scope sc;
+    A *dh, *dr, *dout;
+    CK(sc.alloc((void **)&dh, (size_t)cap * 4 * sizeof(A)));
+    CK(sc.alloc((void **)&dr, (size_t)cap * rl * sizeof(A)));
+    CK(hipMemset(dh, 0, (size_t)cap * 4 * sizeof(A)));
+    CK(hipMemset(dr, 0, (size_t)cap * rl * sizeof(A)));
+    CK(hipMemcpy(dh, heads, (size_t)slots * 4 * sizeof(A), hipMemcpyHostToDevice));
+    CK(hipMemcpy(dr, recs, (size_t)slots * rl * sizeof(A), hipMemcpyHostToDevice));
+    CK(sc.out(dout, (size_t)4 + 2 * T));
+    const size_t lds = sizeof(A) * merge_lds_elems(T, 0, sizeof(A));
+    if (nwin == 1) k_harness_combine<A, 1><<<1, MERGE_THREADS, lds>>>(dr, dh, n, T, beta, want_hits, dout);
+    else k_harness_combine<A, 2><<<1, MERGE_THREADS, lds>>>(dr, dh, n, T, beta, want_hits, dout);
+    return (int)finish(out, dout, (size_t)4 + 2 * T);
+}
+
+template <typename A> int run_merge_abi(const double *recs, int n, int T, A beta, A *out) {
+    if (n < 1 || n > MERGE_MAX_RECORDS || T < 1 || T > MERGE_T_MAX) return (int)hipErrorInvalidValue;
+    Scope sc;
+    double *dr;
+    A *dout;
+    CK(sc.in(dr, recs, (size_t)n * partial_len(T)));
+    CK(sc.out(dout, (size_t)3 + 2 * T));
+    k_harness_abi<A><<<1, MERGE_THREADS, sizeof(A) * merge_lds_elems(T, 0, sizeof(A))>>>(dr, n, T, beta, dout);
+    return (int)finish(out, dout, (size_t)3 + 2 * T);
+}
+
 }  // namespace
 
 extern "C" {
@@ -518,5 +585,18 @@ int prims_lb_exchange(int B, const unsigned *word, const int *skip, unsigned tag
     CK(finish(out, dout, (size_t)B * 4));
     return (int)hipMemcpy(slots, dslots, (size_t)LB_SLOT_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost);
 }
+
+int prims_merge_record_len_f32(int T) { return record_len(T, 4); }
+int prims_merge_record_len_f64(int T) { return record_len(T, 8); }
+int prims_merge_combine_f32(int nwin, const float *heads, const float *recs, int slots, int n, int T, float beta, int want_hits,
+                            float *out) {
+    return run_merge_combine(nwin, heads, recs, slots, n, T, beta, want_hits, out);
+}
+int prims_merge_combine_f64(int nwin, const double *heads, const double *recs, int slots, int n, int T, double beta, int want_hits,
+                            double *out) {
+    return run_merge_combine(nwin, heads, recs, slots, n, T, beta, want_hits, out);
+}
+int prims_merge_abi_f32(const double *recs, int n, int T, float beta, float *out) { return run_merge_abi(recs, n, T, beta, out); }
+int prims_merge_abi_f64(const double *recs, int n, int T, double beta, double *out) { return run_merge_abi(recs, n, T, beta, out); }
 
 }  // extern "C"

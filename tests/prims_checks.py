@@ -205,6 +205,39 @@ class Prims:
 
 
 # ------------------------------------------------------------------------------------------ mathfn
+    # ---- mppi_merge.h
+    def merge_record_len(self, dtype, T):
+        return int(getattr(self.lib, f"prims_merge_record_len_{_sfx(dtype)}")(C.c_int(T)))
+
+    def merge_combine(self, dtype, nwin, rho, eta, eta2, hits, W, n, beta, want_hits=True, pad=0.0):
+        """merge_combine<dtype, 256, nwin> over the first n of the given slots (the slots past n: the caller's absent ones; the
+        harness zero-fills up to nwin * 256 + 256).  W [slots, 2T]; ``pad``: what the record words outside {heads, W} hold.
+        Returns (rho, eta, eta2, n_hit, w_eps[2T]) in ``dtype``."""
+        W = np.asarray(W, np.float64)
+        slots, T = W.shape[0], W.shape[1] // 2
+        rl = self.merge_record_len(dtype, T)
+        heads = np.stack([rho, eta, eta2, hits], axis=1).astype(dtype)
+        recs = np.full((slots, rl), pad, dtype)
+        recs[:, :3] = heads[:, :3]
+        recs[:, 4:4 + 2 * T] = W.astype(dtype)
+        heads, recs = np.ascontiguousarray(heads), np.ascontiguousarray(recs)
+        out = np.empty(4 + 2 * T, dtype)
+        real = C.c_float if np.dtype(dtype) == np.dtype(F32) else C.c_double
+        self._call(f"prims_merge_combine_{_sfx(dtype)}", C.c_int(nwin), _p(heads), _p(recs), C.c_int(slots), C.c_int(n), C.c_int(T),
+                   real(float(dtype(beta))), C.c_int(int(bool(want_hits))), _p(out))
+        return out[0], out[1], out[2], out[3], out[4:]
+
+    def merge_abi(self, dtype, rho, eta, eta2, W, beta):
+        """merge_abi<dtype> over n records {rho, eta, eta2, W[2T]} in doubles.  Returns (rho, eta, eta2, w_eps[2T])."""
+        W = np.asarray(W, np.float64)
+        n, T = W.shape[0], W.shape[1] // 2
+        recs = np.ascontiguousarray(np.concatenate([np.stack([rho, eta, eta2], axis=1), W], axis=1), dtype=np.float64)
+        out = np.empty(3 + 2 * T, dtype)
+        real = C.c_float if np.dtype(dtype) == np.dtype(F32) else C.c_double
+        self._call(f"prims_merge_abi_{_sfx(dtype)}", _p(recs), C.c_int(n), C.c_int(T), real(float(dtype(beta))), _p(out))
+        return out[0], out[1], out[2], out[3:]
+
+
 def ulp_err(got, want64):
     """|got - want| in units of the spacing of want rounded to f32."""
     w32 = want64.astype(F32)

@@ -107,6 +107,13 @@ def test_boundary_errors():
     with pytest.raises(pkg.MppiError) as ex:  # horizon below the filter window (the reference's filter raises)
         pkg.Engine(**dict(base, T=9))
     assert ex.value.code == capi.ERR_SHAPE
+    # the padded filters copy the last (window + 1) // 2 rows: an odd window needs one row more than window // 2
+    for mode in (capi.FILTER_RACECAR, capi.FILTER_TORCH):
+        for window, T_short in ((11, 5), (3, 1), (10, 4), (4, 1)):
+            with pytest.raises(pkg.MppiError) as ex:
+                pkg.Engine(**dict(base, filter_mode=mode, filter_window=window, T=T_short))
+            assert ex.value.code == capi.ERR_SHAPE
+            pkg.Engine(**dict(base, filter_mode=mode, filter_window=window, T=T_short + 1)).close()
     u, u0, st = e.step(np.zeros(3))  # and the handle still works after the failed calls
     assert np.isfinite(u).all() and st.iteration == 1
 

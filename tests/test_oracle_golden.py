@@ -107,6 +107,31 @@ def test_moving_average_filters_match_reference(T):
     np.testing.assert_allclose(fx[f"rctorch_T{T}"][5:], fx[f"rc_T{T}"][:T - 5], rtol=1e-4, atol=1e-6)
 
 
+FILTER_WINDOW_CASES = [tuple(c) for c in gu.load("filters_windows")["meta"]["cases"].tolist()]
+
+
+@pytest.mark.parametrize("W,T", FILTER_WINDOW_CASES)
+def test_moving_average_filters_match_reference_at_other_windows(W, T):
+    """tests/golden/filters_windows.npz: the reference's three filters called at windows {3, 4, 5, 9, 11} (every variant
+    could be called at every window; the diff-drive form from T = W, the padded ones from T = (W + 1) // 2).  At an odd
+    window the race-car form pads with the last W // 2 + 1 rows.  The f64 forms of the oracle filters (what the merge
+    checks push their bounds through) are the same sums: they agree with the f32 ones to f32 rounding."""
+    fx = gu.load("filters_windows")
+    key = f"W{W}_T{T}"
+    xx = fx[f"in_{key}"]
+    if T >= W:
+        np.testing.assert_allclose(mppi_oracle.moving_average_diffdrive(xx, W), fx[f"dd_{key}"], rtol=1e-12, atol=1e-15)
+    else:
+        assert f"dd_{key}" not in fx
+    rc = mppi_oracle.moving_average_racecar(xx.astype(np.float32), W)
+    np.testing.assert_allclose(rc, fx[f"rc_{key}"], rtol=1e-5, atol=1e-6)
+    np.testing.assert_array_equal(fx[f"ddtorch_{key}"], fx[f"rctorch_{key}"])
+    tc = mppi_oracle.moving_average_torch(xx, W)
+    np.testing.assert_allclose(tc, fx[f"rctorch_{key}"], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(mppi_oracle.moving_average_racecar(xx, W, kernel_dtype=np.float64), rc, rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(mppi_oracle.moving_average_torch(xx, W, dtype=np.float64), tc, rtol=1e-5, atol=1e-6)
+
+
 @pytest.mark.parametrize("name", gu.names("ddtorch_"))
 def test_diffdrive_torch_variant_matches_reference(name):
     """controllers/mppi_differential_drive_torch.py run on the CPU in f32 (its x0 aliasing removed, see
