@@ -15,6 +15,7 @@
 
 #include "../../include/mppi_hip.h"
 #include "mppi_kernels.h"
+#include "mppi_owner.h"
 
 using namespace mppi;
 
@@ -70,21 +71,35 @@ struct mppi_handle {
     bool fused = false;       // rollout + softmin partial in one launch (T <= 128)
     int B = 1;                // agents (mppi_config.n_agents); per-agent buffers are B consecutive copies
     int slots = 0;            // records per agent in d_partials / d_heads (the most a launch leaves + zero padding)
-    void *d_partials2 = nullptr;    // what a merge launch in front of the reader leaves (merge_tree)
-    void *d_heads = nullptr, *d_heads2 = nullptr;  // compact {rho, eta, eta2, 0} of d_partials / d_partials2
-    float *d_mlp = nullptr;         // packed residual-model weights (config 5): the model every agent shares (mppi_set_mlp)
-    unsigned short *d_mlp16 = nullptr;  // the same as f16 hi / lo planes (k_rollout_mlp_h3, k_rollout_mlp_w)
+    // Everything the runtime hands out is held by an owner (mppi_owner.h) and released by `delete h`, last member first, on the
+    // device mppi_destroy selected: a new buffer is a field, nothing else.  The events, the stream and the graph objects stand
+    // before the buffers, so they go after them as they always have (the first hipFree waits for the device); the graph
+    // executables stand behind the stream and the events their launches use, so they go first of these.
+    std::vector<Event> ev;  // pairs around the rollout / reduce / finalize kernels
+    size_t ev_used = 0;
+    Event ev_step[2];
+    // closed-loop iterations replayed from a HIP graph once the waypoint index rests (closed_loop_impl)
+    bool graph_on = false;
+    std::vector<char> graph_key;      // the kernel arguments the cached graph was captured with
+    Stream graph_stream;              // (stream and events: created by the first capture, reused by every later one)
+    Event graph_ev_in, graph_ev_out;
+    Event graph_done[2];
+    GraphExec graph_exec[2];          // two instances, launched in turn (see closed_loop_impl)
+    DevBuf<void> d_partials2;       // what a merge launch in front of the reader leaves (merge_tree)
+    DevBuf<void> d_heads, d_heads2;  // compact {rho, eta, eta2, 0} of d_partials / d_partials2
+    DevBuf<float> d_mlp;            // packed residual-model weights (config 5): the model every agent shares (mppi_set_mlp)
+    DevBuf<unsigned short> d_mlp16;  // the same as f16 hi / lo planes (k_rollout_mlp_h3, k_rollout_mlp_w)
     size_t mlp_cap = 0, mlp16_cap = 0;  // their sizes in elements
     // one-launch resolution of the sequential waypoint index (LB_CAND in mppi_kernels.h)
     bool hyp = false;
-    unsigned *d_hyp_slots = nullptr;  // one look-back word per workgroup (LB_COPIES copies)
+    DevBuf<unsigned> d_hyp_slots;     // one look-back word per workgroup (LB_COPIES copies)
     unsigned lb_seq = 0;              // tag of the last rollout / finalize launch pair that used them
     std::vector<double> ref_host;   // [n_ref][4] as the kernels see it (rounded to the handle's precision)
-    StepResult *res_mapped = nullptr;  // device-side address of the pinned host result (polled completion)
+    StepResult *res_mapped = nullptr;  // borrowed: device-side address of h_res, the pinned host result (polled completion)
     long long seq = 0;
     bool idx_valid = true;
     int layout = 0;  // rollout_layout(K, T): which fused rollout kernel serves this handle
-    const char *rollout_kernel = "";  // RolloutPlan::name of the last rollout launch, or of the model mppi_set_mlp loaded (mppi_get_rollout_kernel)
+    const char *rollout_kernel = "";  // borrowed: RolloutPlan::name of the last rollout launch, or of the model mppi_set_mlp loaded (mppi_get_rollout_kernel)
     // The learned model.  mlp_shared / shared_set: the kernels' view of d_mlp / d_mlp16, what mppi_set_mlp loaded for every
     // agent.  Several agents: own_mlp[a] holds what mppi_set_agent_mlp gave agent a instead (a buffer pair it owns, reused
     // while large enough), and d_models is the table the batched kernels read: every agent's view, rewritten by every model
@@ -92,66 +107,57 @@ struct mppi_handle {
     // planners read -- is agent 0's view; hidden, n_hidden and use_h3 in it are the batch's (one shape per handle).
     MlpParams mlp = {}, mlp_shared = {};
     bool shared_set = false;
-    struct OwnModel {
-        float *d_mlp = nullptr;
-        unsigned short *d_mlp16 = nullptr;
+    struct OwnModel {  // (move-only; `o = OwnModel{}` releases the pair)
+        DevBuf<float> d_mlp;
+        DevBuf<unsigned short> d_mlp16;
         size_t cap = 0, cap16 = 0;
         MlpParams q = {};
         bool set = false;
     };
     std::vector<OwnModel> own_mlp;
-    MlpParams *d_models = nullptr;
-    void *d_ref = nullptr, *d_obs = nullptr, *d_u = nullptr, *d_uhist = nullptr, *d_S = nullptr;
+    DevBuf<MlpParams> d_models;
+    DevBuf<void> d_ref, d_obs, d_u, d_uhist, d_S;
     // Several agents: d_ref / n_ref / d_obs / n_obs above are the scene every agent shares (mppi_set_ref_path /
     // mppi_set_obstacles); own[a] holds what mppi_set_agent_ref_path / mppi_set_agent_obstacles gave agent a instead (buffers
     // it owns), and d_scenes is the table the batched kernels read: every agent's view, rewritten by every setter (scene_of,
     // upload_scenes).  A single-agent handle has neither.
-    struct OwnScene {
-        void *d_ref = nullptr, *d_obs = nullptr;
+    struct OwnScene {  // (move-only)
+        DevBuf<void> d_ref, d_obs;
         int n_ref = 0, n_obs = 0;
         bool has_obs = false;  // (an own set of m = 0 circles has no buffer)
     };
     std::vector<OwnScene> own;
-    AgentScene *d_scenes = nullptr;
-    int *d_pout = nullptr;
-    void *d_partials = nullptr;     // block records in the handle's precision
-    double *d_w = nullptr, *d_trace = nullptr;
+    DevBuf<AgentScene> d_scenes;
+    DevBuf<int> d_pout;
+    DevBuf<void> d_partials;        // block records in the handle's precision
+    DevBuf<double> d_w, d_trace;
     long long trace_cap = 0;
-    DevState *d_st = nullptr;
-    StepResult *d_res = nullptr, *h_res = nullptr;
+    DevBuf<DevState> d_st;
+    DevBuf<StepResult> d_res;
+    PinnedBuf<StepResult> h_res;
     size_t res_bytes = 0;
-    const float *last_eps = nullptr;    // the tensor the last iteration drew its noise from (null: the in-kernel sampler)
-    const float *noise_ring = nullptr;  // mppi_set_noise_ring: [noise_slots][n_agents][K][T][2] device floats (caller's)
+    const float *last_eps = nullptr;    // borrowed: the tensor the last iteration drew its noise from (null: the in-kernel sampler)
+    const float *noise_ring = nullptr;  // borrowed: mppi_set_noise_ring: [noise_slots][n_agents][K][T][2] device floats (caller's)
     int noise_slots = 0;
     bool begun = false, timing = false, dev_loop_primed = false, slot_timed = false;
     long long iter = 0;
     int idx = 0, rollout_repeats = 1;
-    std::vector<hipEvent_t> ev;  // pairs around the rollout / reduce / finalize kernels
-    size_t ev_used = 0;
-    hipEvent_t ev_step[2] = {nullptr, nullptr};
     float last_ms[4] = {0, 0, 0, 0};
     double last_iter_us = 0.0;  // host wall time per iteration of the last step / closed-loop call (mppi_stats::iter_us)
     // peer-to-peer exchange (mppi_comm_*)
-    char *xbuf = nullptr;            // this rank's exchange buffer (fine-grained device memory)
+    FineBuf<char> xbuf;              // this rank's exchange buffer (fine-grained device memory)
     size_t xbuf_bytes = 0;
     int x_rank = 0, x_nranks = 0, x_export_nranks = 0;
-    std::vector<void *> x_opened;    // peers' buffers mapped through IPC handles
-    char **d_xpeers = nullptr;       // device array [x_nranks]
-    int *d_xerr = nullptr, *d_xok = nullptr;
+    std::vector<IpcMap> x_opened;    // peers' buffers mapped through IPC handles
+    DevBuf<char *> d_xpeers;         // device array [x_nranks]
+    DevBuf<int> d_xerr, d_xok;
     long long xseq = 0, x_timeout = 300000000LL;
     // RCCL carrier inside the library (mppi_comm_init): communicator, this rank's record and the gathered records
-    void *rccl_comm = nullptr;
+    void *rccl_comm = nullptr;  // (released through the dlopen'ed API: rccl_release)
     int rccl_rank = 0, rccl_nranks = 0;
-    double *d_rccl_part = nullptr, *d_rccl_gath = nullptr;
+    DevBuf<double> d_rccl_part, d_rccl_gath;
     long long n_rollout_launches = 0, n_finalize_launches = 0;  // mppi_get_counters
     double t_enqueue_s = 0.0, t_loop_s = 0.0;  // mppi_get_host_timing: closed-loop calls, enqueueing / whole call
-    // closed-loop iterations replayed from a HIP graph once the waypoint index rests (closed_loop_impl)
-    bool graph_on = false;
-    std::vector<char> graph_key;      // the kernel arguments the cached graph was captured with
-    hipGraphExec_t graph_exec[2] = {nullptr, nullptr};  // two instances, launched in turn (see closed_loop_impl)
-    hipEvent_t graph_done[2] = {nullptr, nullptr};
-    hipStream_t graph_stream = nullptr;
-    hipEvent_t graph_ev_in = nullptr, graph_ev_out = nullptr;
     std::string err;
 };
 
@@ -162,6 +168,7 @@ struct mppi_handle {
         if (h) (h)->err = _b; else g_create_error = _b;      \
         return (code);                                       \
     } while (0)
+#define CREATE_FAIL(code, ...) FAIL((mppi_handle *)nullptr, code, __VA_ARGS__)  // (before there is a handle)
 
 #define HIPCHECK(h, call)                                                                          \
     do {                                                                                           \
@@ -251,84 +258,77 @@ static int download_real(mppi_handle *h, double *dst, const void *src, size_t n)
 }
 
 extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
-    if (!cfg || !out) FAIL((mppi_handle *)nullptr, MPPI_ERR_BAD_ARG, "mppi_create: null argument");
+    if (!cfg || !out) CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: null argument");
     if (cfg->struct_size != (int32_t)sizeof(mppi_config))
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_BAD_ARG, "mppi_create: struct_size %d != %zu (ABI mismatch)",
-             cfg->struct_size, sizeof(mppi_config));
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: struct_size %d != %zu (ABI mismatch)", cfg->struct_size, sizeof(mppi_config));
     mppi_config c = *cfg;
     const Switches sw = read_switches();
     if (c.K_global == 0) c.K_global = c.K;
     if (c.K > (1 << 20) || c.T > 2048)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_SHAPE, "K=%d / T=%d beyond the supported 2^20 samples / 2048 steps", c.K, c.T);
+        CREATE_FAIL(MPPI_ERR_SHAPE, "K=%d / T=%d beyond the supported 2^20 samples / 2048 steps", c.K, c.T);
     if (c.K < 1 || c.T < 1 || c.K_global < c.K || c.k_offset < 0 || c.k_offset + c.K > c.K_global)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_SHAPE, "mppi_create: bad K=%d T=%d K_global=%d k_offset=%d", c.K, c.T,
-             c.K_global, c.k_offset);
+        CREATE_FAIL(MPPI_ERR_SHAPE, "mppi_create: bad K=%d T=%d K_global=%d k_offset=%d", c.K, c.T, c.K_global, c.k_offset);
     if (c.model != MPPI_MODEL_DIFFDRIVE && c.model != MPPI_MODEL_RACECAR && c.model != MPPI_MODEL_DIFFDRIVE_MLP)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_BAD_ARG, "mppi_create: unknown model %d", c.model);
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: unknown model %d", c.model);
     if (c.model == MPPI_MODEL_DIFFDRIVE_MLP && c.precision != MPPI_PREC_F32)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED, "the learned-dynamics rollout runs on the f32 MFMA path only");
+        CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "the learned-dynamics rollout runs on the f32 MFMA path only");
     if (c.precision != MPPI_PREC_F32 && c.precision != MPPI_PREC_F64)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_BAD_ARG, "mppi_create: unknown precision %d", c.precision);
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: unknown precision %d", c.precision);
     if (c.waypoint_mode != MPPI_WAYPOINT_SEQUENTIAL && c.waypoint_mode != MPPI_WAYPOINT_FROZEN && c.waypoint_mode != MPPI_WAYPOINT_PER_ROLLOUT)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_BAD_ARG, "mppi_create: unknown waypoint_mode %d", c.waypoint_mode);
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: unknown waypoint_mode %d", c.waypoint_mode);
     if (c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT && c.model == MPPI_MODEL_RACECAR)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED,
+        CREATE_FAIL(MPPI_ERR_UNSUPPORTED,
              "MPPI_WAYPOINT_PER_ROLLOUT restates the diff-drive files' index bookkeeping (mppi_differential_drive.py:228,:244); "
              "the race-car files search from the x0 call's index (MPPI_WAYPOINT_FROZEN)");
     if (c.filter_window < 1) c.filter_window = 10;
-    if (c.search_window < 1)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_BAD_ARG, "mppi_create: search_window must be >= 1");
+    if (c.search_window < 1) CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: search_window must be >= 1");
     // the reference's filters fail on short horizons (np.convolve 'same' returns max(M, N) samples)
     if (c.filter_mode == MPPI_FILTER_DIFFDRIVE && c.T < c.filter_window)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_SHAPE, "horizon T=%d is shorter than the moving-average window %d", c.T,
-             c.filter_window);
+        CREATE_FAIL(MPPI_ERR_SHAPE, "horizon T=%d is shorter than the moving-average window %d", c.T, c.filter_window);
     // (the padded variants copy the last -(-window // 2) = (window + 1) / 2 rows, mppi_race_car.py:219)
     if ((c.filter_mode == MPPI_FILTER_RACECAR || c.filter_mode == MPPI_FILTER_TORCH) && c.T < (c.filter_window + 1) / 2)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_SHAPE, "horizon T=%d is shorter than half the filter window %d (rounded up)", c.T,
-             c.filter_window);
+        CREATE_FAIL(MPPI_ERR_SHAPE, "horizon T=%d is shorter than half the filter window %d (rounded up)", c.T, c.filter_window);
     if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL && c.K_global != c.K)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED,
+        CREATE_FAIL(MPPI_ERR_UNSUPPORTED,
              "the sequential waypoint index threads through all samples in order and cannot be sharded; "
              "use MPPI_WAYPOINT_PER_ROLLOUT or MPPI_WAYPOINT_FROZEN with K_global > K");
     if (c.n_agents < 1) c.n_agents = 1;
     if (c.n_agents > 1) {
-        if (c.n_agents > 4096) FAIL((mppi_handle *)nullptr, MPPI_ERR_SHAPE, "mppi_create: n_agents %d > 4096", c.n_agents);
+        if (c.n_agents > 4096) CREATE_FAIL(MPPI_ERR_SHAPE, "mppi_create: n_agents %d > 4096", c.n_agents);
         if (c.model == MPPI_MODEL_DIFFDRIVE_MLP) {
             // one learned model for every agent: k_rollout_mlp_h3_agents / k_rollout_mlp_w_agents, one 64-sample tile per
             // workgroup and agent; at most the 512 records per agent k_finalize merges itself (k_merge is not agent-aware)
             if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL || c.K_global != c.K || merge_tree(mlp_blocks(c.K, 64), true).group)
-                FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED,
+                CREATE_FAIL(MPPI_ERR_UNSUPPORTED,
                      "several agents per learned-dynamics handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, at most 512 rollout "
                      "workgroups of 64 samples per agent (K <= 32768) and no sharding (got K = %d, K_global = %d)", c.K, c.K_global);
         } else if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL || c.K_global != c.K || !fused_supported(c.T) ||
                    merge_tree(fused_blocks(c.K, c.T, rollout_layout(sw, c.K, c.T, c.n_agents, kernel_model(c), c.precision == MPPI_PREC_F64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT)), true).group) {
-            FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED,
+            CREATE_FAIL(MPPI_ERR_UNSUPPORTED,
                  "several agents per handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, T <= 128, at most 512 rollout workgroups "
                  "(K <= 8192) and no sharding");
         }
     }
     const double det = c.sigma[0] * c.sigma[3] - c.sigma[1] * c.sigma[2];
     if (!(c.sigma[0] > 0) || !(det > 0))
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_BAD_ARG, "sigma must be a symmetric positive definite 2x2 matrix");
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "sigma must be a symmetric positive definite 2x2 matrix");
     if (!(c.param_exploration >= 0) || !(c.param_lambda > 0))
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_BAD_ARG, "param_exploration must be >= 0 and param_lambda > 0");
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "param_exploration must be >= 0 and param_lambda > 0");
     if (c.beta_mode == MPPI_BETA_INV_EXPLORATION && !(c.param_exploration > 0))
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_BAD_ARG, "beta = 1/param_exploration needs param_exploration > 0");
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "beta = 1/param_exploration needs param_exploration > 0");
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_NO_DEVICE, "no HIP device is visible: libmppi_hip.so needs an MI355X");
+        CREATE_FAIL(MPPI_ERR_NO_DEVICE, "no HIP device is visible: libmppi_hip.so needs an MI355X");
     if (c.device < 0 || c.device >= ndev)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_NO_DEVICE, "device %d out of range (%d visible)", c.device, ndev);
+        CREATE_FAIL(MPPI_ERR_NO_DEVICE, "device %d out of range (%d visible)", c.device, ndev);
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c.device) != hipSuccess)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
+    if (hipGetDeviceProperties(&prop, c.device) != hipSuccess) CREATE_FAIL(MPPI_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only",
-             c.device, prop.gcnArchName);
+        CREATE_FAIL(MPPI_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", c.device, prop.gcnArchName);
 
     if (c.n_agents > 1 && c.model != MPPI_MODEL_DIFFDRIVE_MLP && sw.force_unfused)
-        FAIL((mppi_handle *)nullptr, MPPI_ERR_UNSUPPORTED, "several agents per handle need the fused rollout kernels");
+        CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "several agents per handle need the fused rollout kernels");
     mppi_handle *h = new mppi_handle();
     h->cfg = c;
     h->sw = sw;
@@ -356,19 +356,19 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         return (int)MPPI_ERR_HIP;
     };
     // a device buffer, allocated and zero-filled; a failure names the call that failed
-    const auto zeroed = [&](void **p, size_t bytes, const char *malloc_call) -> int {
+    const auto zeroed = [&](auto &buf, size_t bytes, const char *malloc_call) -> int {
         hipError_t e;
-        if ((e = hipMalloc(p, bytes)) != hipSuccess) return fail(e, malloc_call);
-        if ((e = hipMemset(*p, 0, bytes)) != hipSuccess) return fail(e, "hipMemset");
+        if ((e = buf.alloc(bytes)) != hipSuccess) return fail(e, malloc_call);
+        if ((e = hipMemset(buf, 0, bytes)) != hipSuccess) return fail(e, "hipMemset");
         return MPPI_OK;
     };
     hipError_t e;
     if ((e = hipSetDevice(c.device)) != hipSuccess) return fail(e, "hipSetDevice");
     const size_t r = rsz(h), B = (size_t)c.n_agents;
-    if (int rc = zeroed(&h->d_u, B * r * 2 * c.T, "hipMalloc(u)")) return rc;  // u_prev = 0 (:82)
-    if (int rc = zeroed(&h->d_uhist, B * r * 4 * c.T, "hipMalloc(u history)")) return rc;
-    if (int rc = zeroed(&h->d_S, B * r * c.K, "hipMalloc(S)")) return rc;
-    if (int rc = zeroed((void **)&h->d_pout, B * sizeof(int) * c.K, "hipMalloc(pout)")) return rc;
+    if (int rc = zeroed(h->d_u, B * r * 2 * c.T, "hipMalloc(u)")) return rc;  // u_prev = 0 (:82)
+    if (int rc = zeroed(h->d_uhist, B * r * 4 * c.T, "hipMalloc(u history)")) return rc;
+    if (int rc = zeroed(h->d_S, B * r * c.K, "hipMalloc(S)")) return rc;
+    if (int rc = zeroed(h->d_pout, B * sizeof(int) * c.K, "hipMalloc(pout)")) return rc;
     const size_t rec_bytes = sizeof(double) * (size_t)record_len(c.T, 8);  // enough for either precision
     // zero-filled and padded by 256 records: the merge kernels read 256 slots unconditionally
     // (a launch may leave more records than the handle's own count -- fused_max_records: room for the larger of the two)
@@ -376,26 +376,25 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     // (the second level: a merge launch leaves at most one window, and only more records than a window are ever merged)
     const size_t slots = n_rec_max + 256, n1 = B * slots, n2 = (merge_tree((int)n_rec_max, false).group ? MERGE_MAX_RECORDS : 0) + 256;
     h->slots = (int)slots;
-    if (int rc = zeroed(&h->d_partials, rec_bytes * n1, "hipMalloc(partials)")) return rc;
-    if (int rc = zeroed(&h->d_partials2, rec_bytes * n2, "hipMalloc(partials2)")) return rc;
-    if (int rc = zeroed(&h->d_heads, 32 * n1, "hipMalloc(heads)")) return rc;
-    if (int rc = zeroed(&h->d_heads2, 32 * n2, "hipMalloc(heads2)")) return rc;
+    if (int rc = zeroed(h->d_partials, rec_bytes * n1, "hipMalloc(partials)")) return rc;
+    if (int rc = zeroed(h->d_partials2, rec_bytes * n2, "hipMalloc(partials2)")) return rc;
+    if (int rc = zeroed(h->d_heads, 32 * n1, "hipMalloc(heads)")) return rc;
+    if (int rc = zeroed(h->d_heads2, 32 * n2, "hipMalloc(heads2)")) return rc;
     h->hyp = lookback_serves(h, n_part);
     if (h->hyp)
-        if (int rc = zeroed((void **)&h->d_hyp_slots, sizeof(unsigned) * (size_t)LB_COPIES * LB_COPY_STRIDE, "hipMalloc(look-back words)")) return rc;
+        if (int rc = zeroed(h->d_hyp_slots, sizeof(unsigned) * (size_t)LB_COPIES * LB_COPY_STRIDE, "hipMalloc(look-back words)")) return rc;
     h->res_bytes = (h->res_bytes + 15) & ~(size_t)15;  // (the agents' results are stored back to back)
-    if ((e = hipMalloc((void **)&h->d_st, B * sizeof(DevState))) != hipSuccess) return fail(e, "hipMalloc(state)");  // (filled below)
-    if (int rc = zeroed((void **)&h->d_res, B * h->res_bytes, "hipMalloc(result)")) return rc;
-    if ((e = hipHostMalloc((void **)&h->h_res, B * h->res_bytes, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
-        return fail(e, "hipHostMalloc(result)");
+    if ((e = h->d_st.alloc(B * sizeof(DevState))) != hipSuccess) return fail(e, "hipMalloc(state)");  // (filled below)
+    if (int rc = zeroed(h->d_res, B * h->res_bytes, "hipMalloc(result)")) return rc;
+    if ((e = h->h_res.alloc(B * h->res_bytes)) != hipSuccess) return fail(e, "hipHostMalloc(result)");
     if ((e = hipHostGetDevicePointer((void **)&h->res_mapped, h->h_res, 0)) != hipSuccess)
         return fail(e, "hipHostGetDevicePointer(result)");
     if (B > 1) {
         h->own.resize(B);
-        if (int rc = zeroed((void **)&h->d_scenes, B * sizeof(AgentScene), "hipMalloc(agent scenes)")) return rc;
+        if (int rc = zeroed(h->d_scenes, B * sizeof(AgentScene), "hipMalloc(agent scenes)")) return rc;
         if (c.model == MPPI_MODEL_DIFFDRIVE_MLP) {
             h->own_mlp.resize(B);
-            if (int rc = zeroed((void **)&h->d_models, B * sizeof(MlpParams), "hipMalloc(agent models)")) return rc;
+            if (int rc = zeroed(h->d_models, B * sizeof(MlpParams), "hipMalloc(agent models)")) return rc;
         }
     }
     DevState st0;
@@ -404,8 +403,8 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     for (size_t a = 0; a < B; ++a)
         if ((e = hipMemcpy(h->d_st + a, &st0, sizeof(st0), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
     memset(h->h_res, 0, B * h->res_bytes);
-    if ((e = hipEventCreate(&h->ev_step[0])) != hipSuccess) return fail(e, "hipEventCreate");
-    if ((e = hipEventCreate(&h->ev_step[1])) != hipSuccess) return fail(e, "hipEventCreate");
+    if ((e = hipEventCreate(h->ev_step[0].put())) != hipSuccess) return fail(e, "hipEventCreate");
+    if ((e = hipEventCreate(h->ev_step[1].put())) != hipSuccess) return fail(e, "hipEventCreate");
     *out = h;
     return MPPI_OK;
 }
@@ -416,31 +415,6 @@ extern "C" int mppi_destroy(mppi_handle *h) {
     if (!h) return MPPI_OK;
     hipSetDevice(h->cfg.device);
     if (h->xbuf || h->rccl_comm) mppi_comm_close(h);
-    void *bufs[] = {h->d_ref, h->d_obs, h->d_u, h->d_uhist, h->d_S, h->d_pout, h->d_partials, h->d_partials2, h->d_mlp,
-                    h->d_w,   h->d_trace, h->d_st, h->d_res, h->d_heads, h->d_heads2, h->d_hyp_slots, h->d_mlp16};
-    for (void *b : bufs)
-        if (b) hipFree(b);
-    for (const mppi_handle::OwnScene &o : h->own) {
-        if (o.d_ref) hipFree(o.d_ref);
-        if (o.d_obs) hipFree(o.d_obs);
-    }
-    if (h->d_scenes) hipFree(h->d_scenes);
-    for (const mppi_handle::OwnModel &o : h->own_mlp) {
-        if (o.d_mlp) hipFree(o.d_mlp);
-        if (o.d_mlp16) hipFree(o.d_mlp16);
-    }
-    if (h->d_models) hipFree(h->d_models);
-    if (h->h_res) hipHostFree(h->h_res);
-    for (int i = 0; i < 2; ++i) {
-        if (h->graph_exec[i]) hipGraphExecDestroy(h->graph_exec[i]);
-        if (h->graph_done[i]) hipEventDestroy(h->graph_done[i]);
-    }
-    if (h->graph_ev_in) hipEventDestroy(h->graph_ev_in);
-    if (h->graph_ev_out) hipEventDestroy(h->graph_ev_out);
-    if (h->graph_stream) hipStreamDestroy(h->graph_stream);
-    for (hipEvent_t e : h->ev) hipEventDestroy(e);
-    for (hipEvent_t e : h->ev_step)
-        if (e) hipEventDestroy(e);
     delete h;
     return MPPI_OK;
 }
@@ -458,8 +432,8 @@ static int upload_scenes(mppi_handle *h) {
 
 // `self.ref_path` into *d_ref / *n_ref (the shared scene's or one agent's): validated, packed to [n][4], the device idle before
 // the old buffer goes; host_copy (nullable): the packed path as the kernels see it
-static int set_path(mppi_handle *h, const char *who, const double *path, int32_t n, int32_t ncols, void **d_ref, int *n_ref,
-                    std::vector<double> *host_copy) {
+static int set_path(mppi_handle *h, const char *who, const double *path, int32_t n, int32_t ncols, DevBuf<void> *d_ref,
+                    int *n_ref, std::vector<double> *host_copy) {
     if (!path) FAIL(h, MPPI_ERR_BAD_ARG, "%s: null argument", who);
     const int need = h->cfg.model == MPPI_MODEL_RACECAR ? 4 : 3;
     if (n < 1 || ncols < need || ncols > 4)
@@ -469,10 +443,9 @@ static int set_path(mppi_handle *h, const char *who, const double *path, int32_t
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < ncols; ++j) packed[(size_t)i * 4 + j] = path[(size_t)i * ncols + j];
     HIPCHECK(h, hipDeviceSynchronize());
-    if (*d_ref) HIPCHECK(h, hipFree(*d_ref));
-    *d_ref = nullptr;
     *n_ref = 0;
-    HIPCHECK(h, hipMalloc(d_ref, rsz(h) * 4 * n));
+    HIPCHECK(h, d_ref->reset());
+    HIPCHECK(h, d_ref->alloc(rsz(h) * 4 * n));
     *n_ref = n;
     h->dev_loop_primed = false;
     if (host_copy) {
@@ -484,13 +457,12 @@ static int set_path(mppi_handle *h, const char *who, const double *path, int32_t
 }
 
 // `self.obstacle_circles` into *d_obs / *n_obs, likewise
-static int set_circles(mppi_handle *h, const char *who, const double *xyr, int32_t m, void **d_obs, int *n_obs) {
+static int set_circles(mppi_handle *h, const char *who, const double *xyr, int32_t m, DevBuf<void> *d_obs, int *n_obs) {
     if (m > 0 && !xyr) FAIL(h, MPPI_ERR_BAD_ARG, "%s: null argument", who);
     if (m < 0) FAIL(h, MPPI_ERR_SHAPE, "%s: m < 0", who);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
-    if (*d_obs) HIPCHECK(h, hipFree(*d_obs));
-    *d_obs = nullptr;
+    HIPCHECK(h, d_obs->reset());
     *n_obs = m;
     if (m == 0) return MPPI_OK;
     std::vector<double> packed((size_t)m * 4, 0.0);
@@ -502,7 +474,7 @@ static int set_circles(mppi_handle *h, const char *who, const double *xyr, int32
         packed[4 * i + 1] = xyr[3 * i + 1];
         packed[4 * i + 2] = thr * thr;
     }
-    HIPCHECK(h, hipMalloc(d_obs, rsz(h) * 4 * m));
+    HIPCHECK(h, d_obs->alloc(rsz(h) * 4 * m));
     return upload_real(h, *d_obs, packed.data(), packed.size());
 }
 
@@ -510,9 +482,8 @@ extern "C" int mppi_set_ref_path(mppi_handle *h, const double *path, int32_t n, 
     if (!h) return MPPI_ERR_BAD_ARG;
     if (int rc = set_path(h, "mppi_set_ref_path", path, n, ncols, &h->d_ref, &h->n_ref, &h->ref_host)) return rc;
     for (mppi_handle::OwnScene &o : h->own) {  // several agents: every agent follows this path again
-        if (o.d_ref) HIPCHECK(h, hipFree(o.d_ref));
-        o.d_ref = nullptr;
         o.n_ref = 0;
+        HIPCHECK(h, o.d_ref.reset());
     }
     return upload_scenes(h);
 }
@@ -521,10 +492,9 @@ extern "C" int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m) 
     if (!h) return MPPI_ERR_BAD_ARG;
     if (int rc = set_circles(h, "mppi_set_obstacles", xyr, m, &h->d_obs, &h->n_obs)) return rc;
     for (mppi_handle::OwnScene &o : h->own) {
-        if (o.d_obs) HIPCHECK(h, hipFree(o.d_obs));
-        o.d_obs = nullptr;
         o.n_obs = 0;
         o.has_obs = false;
+        HIPCHECK(h, o.d_obs.reset());
     }
     return upload_scenes(h);
 }
@@ -568,10 +538,7 @@ extern "C" int mppi_get_agent_status(mppi_handle *h, int32_t *idx_out, int32_t *
 
 // (the caller has synchronised the device: no instance is running)
 static void drop_graph(mppi_handle *h) {
-    for (int i = 0; i < 2; ++i) {
-        if (h->graph_exec[i]) (void)hipGraphExecDestroy(h->graph_exec[i]);
-        h->graph_exec[i] = nullptr;
-    }
+    for (GraphExec &g : h->graph_exec) (void)g.reset();
     h->graph_key.clear();
 }
 
@@ -689,27 +656,17 @@ static int pack_mlp(mppi_handle *h, const char *who, int32_t hidden, int32_t n_h
 // A packed model into a buffer pair (the shared one or an agent's own; grown when too small -- the new buffers are
 // allocated before the old ones go, so a failed allocation leaves the pair and *q as they were) and its view into *q.
 // The caller has synchronised the device.
-static int place_mlp(mppi_handle *h, const HostMlp &m, float **d, size_t *cap, unsigned short **d16, size_t *cap16, MlpParams *q) {
-    float *nd = nullptr;
-    unsigned short *nd16 = nullptr;
-    if (!*d || *cap < m.f32.size()) HIPCHECK(h, hipMalloc((void **)&nd, m.f32.size() * sizeof(float)));
+static int place_mlp(mppi_handle *h, const HostMlp &m, DevBuf<float> *d, size_t *cap, DevBuf<unsigned short> *d16, size_t *cap16,
+                     MlpParams *q) {
+    DevBuf<float> nd;  // (released on the way out unless they move in)
+    DevBuf<unsigned short> nd16;
+    if (!*d || *cap < m.f32.size()) HIPCHECK(h, nd.alloc(m.f32.size() * sizeof(float)));
     if (!*d16 || *cap16 < m.f16.size()) {
-        const hipError_t e = hipMalloc((void **)&nd16, m.f16.size() * sizeof(unsigned short));
-        if (e != hipSuccess) {
-            if (nd) (void)hipFree(nd);
-            FAIL(h, MPPI_ERR_HIP, "hipMalloc(model) failed: %s", hipGetErrorString(e));
-        }
+        const hipError_t e = nd16.alloc(m.f16.size() * sizeof(unsigned short));
+        if (e != hipSuccess) FAIL(h, MPPI_ERR_HIP, "hipMalloc(model) failed: %s", hipGetErrorString(e));
     }
-    if (nd) {
-        if (*d) (void)hipFree(*d);
-        *d = nd;
-        *cap = m.f32.size();
-    }
-    if (nd16) {
-        if (*d16) (void)hipFree(*d16);
-        *d16 = nd16;
-        *cap16 = m.f16.size();
-    }
+    if (nd) *d = std::move(nd), *cap = m.f32.size();  // (the old buffer goes here, behind both allocations)
+    if (nd16) *d16 = std::move(nd16), *cap16 = m.f16.size();
     HIPCHECK(h, hipMemcpy(*d, m.f32.data(), m.f32.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHECK(h, hipMemcpy(*d16, m.f16.data(), m.f16.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
     *q = m.q;
@@ -739,11 +696,7 @@ static int set_model(mppi_handle *h, const char *who, int agent, const HostMlp &
         drop_graph(h);
         if (int rc = place_mlp(h, m, &h->d_mlp, &h->mlp_cap, &h->d_mlp16, &h->mlp16_cap, &h->mlp_shared)) return rc;
         h->shared_set = true;
-        for (mppi_handle::OwnModel &o : h->own_mlp) {  // several agents: every agent runs this model again
-            if (o.d_mlp) (void)hipFree(o.d_mlp);
-            if (o.d_mlp16) (void)hipFree(o.d_mlp16);
-            o = mppi_handle::OwnModel{};
-        }
+        for (mppi_handle::OwnModel &o : h->own_mlp) o = mppi_handle::OwnModel{};  // several agents: every agent runs this model again
     } else {
         mppi_handle::OwnModel &o = h->own_mlp[agent];
         if (int rc = place_mlp(h, m, &o.d_mlp, &o.cap, &o.d_mlp16, &o.cap16, &o.q)) return rc;
@@ -972,16 +925,16 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.ref = (const R *)sc0.ref;
     P.obs = (const R *)sc0.obs;
     P.scenes = h->d_scenes;
-    P.u = (const R *)h->d_u;
+    P.u = (const R *)h->d_u.get();
     P.eps = noise;
-    P.S = (R *)h->d_S;
+    P.S = (R *)h->d_S.get();
     P.pout = h->d_pout;
     P.st = h->d_st;
     P.noise_stream = c.noise_stream;
     P.slots = h->slots;
     P.n_agents = h->B;
     P.layout = h->layout;
-    P.heads = (R *)h->d_heads;
+    P.heads = (R *)h->d_heads.get();
     // the kernels that can resolve the sequential index in one launch -- while that index can still move: after that the
     // lean kernels serve
     P.hyp = index_can_move(h);
@@ -1051,11 +1004,7 @@ constexpr int EV_PER_SLOT = 8;
 constexpr size_t EV_MAX = 8u * 200000u;
 
 static hipEvent_t next_event(mppi_handle *h) {
-    if (h->ev_used == h->ev.size()) {
-        hipEvent_t e;
-        hipEventCreate(&e);
-        h->ev.push_back(e);
-    }
+    if (h->ev_used == h->ev.size()) hipEventCreate(h->ev.emplace_back().put());
     return h->ev[h->ev_used++];
 }
 
@@ -1468,7 +1417,7 @@ extern "C" int mppi_get_weights(mppi_handle *h, double *w) {
     SINGLE_AGENT_ONLY(h, "mppi_get_weights");
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
-    if (!h->d_w) HIPCHECK(h, hipMalloc((void **)&h->d_w, sizeof(double) * h->cfg.K));
+    if (!h->d_w) HIPCHECK(h, h->d_w.alloc(sizeof(double) * h->cfg.K));
     with_real(h, [&](auto r) {
         using R = decltype(r);
         launch_weights<R>(make_params<R>(h, nullptr), h->h_res->rho, h->h_res->eta, h->d_w, nullptr);
@@ -1519,7 +1468,7 @@ extern "C" int mppi_rollout_viz(mppi_handle *h, float *optimal_traj, float *samp
     with_real(h, [&](auto r) {
         using R = decltype(r);
         const KParams<R> P = make_params<R>(h, h->last_eps);
-        const R *hist = (const R *)h->d_uhist, *hist_after = hist + 2 * h->cfg.T;
+        const R *hist = (const R *)h->d_uhist.get(), *hist_after = hist + 2 * h->cfg.T;
         if constexpr (sizeof(R) == 4)  // (the learned model: f32 handles only, checked at create)
             if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP)
                 return launch_viz_mlp(P, h->mlp, h->sw, hist, hist_after, h->iter - 1, optimal_traj, sampled_traj, (hipStream_t)stream);
@@ -1576,10 +1525,9 @@ RcclApi &rccl_api() {
 
 static void rccl_release(mppi_handle *h) {
     if (h->rccl_comm) rccl_api().CommDestroy(h->rccl_comm);
-    if (h->d_rccl_part) hipFree(h->d_rccl_part);
-    if (h->d_rccl_gath) hipFree(h->d_rccl_gath);
+    (void)h->d_rccl_part.reset();
+    (void)h->d_rccl_gath.reset();
     h->rccl_comm = nullptr;
-    h->d_rccl_part = h->d_rccl_gath = nullptr;
     h->rccl_nranks = 0;
 }
 
@@ -1620,8 +1568,8 @@ extern "C" int mppi_comm_init(mppi_handle *h, const void *unique_id, int32_t ran
     memcpy(&id, unique_id, sizeof(id));
     RCCLCHECK(h, a.CommInitRank(&h->rccl_comm, nranks, id, rank));
     const size_t len = (size_t)partial_len(h->cfg.T);
-    HIPCHECK(h, hipMalloc((void **)&h->d_rccl_part, sizeof(double) * len));
-    HIPCHECK(h, hipMalloc((void **)&h->d_rccl_gath, sizeof(double) * len * nranks));
+    HIPCHECK(h, h->d_rccl_part.alloc(sizeof(double) * len));
+    HIPCHECK(h, h->d_rccl_gath.alloc(sizeof(double) * len * nranks));
     h->rccl_rank = rank;
     h->rccl_nranks = nranks;
     return MPPI_OK;
@@ -1631,12 +1579,12 @@ extern "C" int mppi_comm_init(mppi_handle *h, const void *unique_id, int32_t ran
 // the absolute iteration, finds row h->iter.
 static int trace_rows(mppi_handle *h, int n_iters, double **rows) {
     if (h->trace_cap < n_iters) {
-        if (h->d_trace) HIPCHECK(h, hipFree(h->d_trace));
-        h->d_trace = nullptr;
-        HIPCHECK(h, hipMalloc((void **)&h->d_trace, sizeof(double) * 2 * n_iters));
+        h->trace_cap = 0;
+        HIPCHECK(h, h->d_trace.reset());
+        HIPCHECK(h, h->d_trace.alloc(sizeof(double) * 2 * n_iters));
         h->trace_cap = n_iters;
     }
-    *rows = h->d_trace - 2 * h->iter;
+    *rows = h->d_trace.get() - 2 * h->iter;
     return MPPI_OK;
 }
 
@@ -1700,15 +1648,11 @@ extern "C" int mppi_comm_close(mppi_handle *h) {
     if (!h) return MPPI_ERR_BAD_ARG;
     hipSetDevice(h->cfg.device);
     hipDeviceSynchronize();
-    for (void *p : h->x_opened) hipIpcCloseMemHandle(p);
     h->x_opened.clear();
-    if (h->d_xpeers) hipFree(h->d_xpeers);
-    if (h->d_xerr) hipFree(h->d_xerr);
-    if (h->d_xok) hipFree(h->d_xok);
-    if (h->xbuf) hipFree(h->xbuf);
-    h->d_xpeers = nullptr;
-    h->d_xerr = h->d_xok = nullptr;
-    h->xbuf = nullptr;
+    (void)h->d_xpeers.reset();
+    (void)h->d_xerr.reset();
+    (void)h->d_xok.reset();
+    (void)h->xbuf.reset();
     h->x_nranks = h->x_export_nranks = 0;
     rccl_release(h);
     return MPPI_OK;
@@ -1728,8 +1672,7 @@ extern "C" int mppi_comm_export(mppi_handle *h, int32_t nranks, void *handle_out
     if (h->xbuf) mppi_comm_close(h);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     h->xbuf_bytes = 2 * xchg_slot_bytes(h->cfg.T, nranks);
-    // fine-grained: stores of a peer GPU become visible to this GPU's loads without a cache writeback here
-    HIPCHECK(h, hipExtMallocWithFlags((void **)&h->xbuf, h->xbuf_bytes, hipDeviceMallocFinegrained));
+    HIPCHECK(h, h->xbuf.alloc(h->xbuf_bytes));  // (fine-grained: a peer's stores are visible here without a cache writeback)
     HIPCHECK(h, hipMemset(h->xbuf, 0, h->xbuf_bytes));
     HIPCHECK(h, hipDeviceSynchronize());
     hipIpcMemHandle_t ipc;
@@ -1753,7 +1696,10 @@ extern "C" int mppi_comm_connect(mppi_handle *h, int32_t rank, int32_t nranks, c
         FAIL(h, MPPI_ERR_STATE, "mppi_comm_connect: call mppi_comm_export with the same nranks first");
     if (rank < 0 || rank >= nranks) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_comm_connect: rank %d of %d", rank, nranks);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
+    // The new wiring is built in local owners and moves into the handle once all of it stands: a failure on the way leaves
+    // the previous wiring as it was and nothing behind.
     std::vector<char *> peers(nranks, nullptr);
+    std::vector<IpcMap> opened;
     for (int r = 0; r < nranks; ++r) {
         if (r == rank) {
             peers[r] = h->xbuf;
@@ -1783,20 +1729,21 @@ extern "C" int mppi_comm_connect(mppi_handle *h, int32_t rank, int32_t nranks, c
             if (!handles) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_comm_connect: no handle for rank %d", r);
             hipIpcMemHandle_t ipc;
             memcpy(&ipc, (const char *)handles + sizeof(ipc) * (size_t)r, sizeof(ipc));
-            void *p = nullptr;
-            HIPCHECK(h, hipIpcOpenMemHandle(&p, ipc, hipIpcMemLazyEnablePeerAccess));
-            h->x_opened.push_back(p);
-            peers[r] = (char *)p;
+            HIPCHECK(h, hipIpcOpenMemHandle(opened.emplace_back().put(), ipc, hipIpcMemLazyEnablePeerAccess));
+            peers[r] = (char *)opened.back().get();
         }
     }
-    if (h->d_xpeers) { hipFree(h->d_xpeers); h->d_xpeers = nullptr; }  // (connected before: the new wiring replaces it)
-    if (h->d_xerr) { hipFree(h->d_xerr); h->d_xerr = nullptr; }
-    if (h->d_xok) { hipFree(h->d_xok); h->d_xok = nullptr; }
-    HIPCHECK(h, hipMalloc((void **)&h->d_xpeers, sizeof(char *) * nranks));
-    HIPCHECK(h, hipMemcpy(h->d_xpeers, peers.data(), sizeof(char *) * nranks, hipMemcpyHostToDevice));
-    HIPCHECK(h, hipMalloc((void **)&h->d_xerr, sizeof(int)));
-    HIPCHECK(h, hipMalloc((void **)&h->d_xok, sizeof(int)));
-    HIPCHECK(h, hipMemset(h->d_xerr, 0, sizeof(int)));
+    DevBuf<char *> d_xpeers;
+    DevBuf<int> d_xerr, d_xok;
+    HIPCHECK(h, d_xpeers.alloc(sizeof(char *) * nranks));
+    HIPCHECK(h, hipMemcpy(d_xpeers, peers.data(), sizeof(char *) * nranks, hipMemcpyHostToDevice));
+    HIPCHECK(h, d_xerr.alloc(sizeof(int)));
+    HIPCHECK(h, d_xok.alloc(sizeof(int)));
+    HIPCHECK(h, hipMemset(d_xerr, 0, sizeof(int)));
+    h->d_xpeers = std::move(d_xpeers);  // (connected before: the new wiring replaces the old one, whose mappings stay open
+    h->d_xerr = std::move(d_xerr);      // until mppi_comm_close, as they always have)
+    h->d_xok = std::move(d_xok);
+    for (IpcMap &m : opened) h->x_opened.push_back(std::move(m));
     if (const long long ms = read_switches().exchange_timeout_ms; ms > 0) h->x_timeout = ms * 100000LL;  // the wall clock counts at 100 MHz
     h->x_rank = rank;
     h->x_nranks = nranks;
@@ -1857,35 +1804,31 @@ template <typename R>
 static bool ensure_graph(mppi_handle *h, const SlotPlan &sp, const KParams<R> &P, const FinalizeParams &F) {
     // (the learned model's parameters too: its launches carry MlpParams -- weight pointers, shape, output bias -- by value,
     // agent 0's; a batched launch carries the address of the agents' table instead, whose entries a replay reads afresh)
-    std::vector<char> key(sizeof(P) + sizeof(F) + 2 * sizeof(int) + sizeof(MlpParams) + sizeof(h->d_models));
+    const MlpParams *const models = h->d_models;  // (the raw address: that is what a launch carries)
+    std::vector<char> key(sizeof(P) + sizeof(F) + 2 * sizeof(int) + sizeof(MlpParams) + sizeof(models));
     memcpy(key.data(), &P, sizeof(P));
     memcpy(key.data() + sizeof(P), &F, sizeof(F));
     const int tail[2] = {h->rollout_repeats, (int)sizeof(R)};
     memcpy(key.data() + sizeof(P) + sizeof(F), tail, sizeof(tail));
     memcpy(key.data() + sizeof(P) + sizeof(F) + sizeof(tail), &h->mlp, sizeof(MlpParams));
-    memcpy(key.data() + sizeof(P) + sizeof(F) + sizeof(tail) + sizeof(MlpParams), &h->d_models, sizeof(h->d_models));
+    memcpy(key.data() + sizeof(P) + sizeof(F) + sizeof(tail) + sizeof(MlpParams), &models, sizeof(models));
     if (h->graph_exec[0] && key == h->graph_key) return true;
     if (h->sw.graph_verbose) fprintf(stderr, "[mppi] capturing a graph of %d iterations\n", GRAPH_SLOTS);
-    for (int i = 0; i < 2; ++i) {
-        if (h->graph_exec[i]) hipGraphExecDestroy(h->graph_exec[i]);
-        h->graph_exec[i] = nullptr;
-    }
+    drop_graph(h);
     hipError_t e = hipSuccess;
-    if (!h->graph_stream) e = hipStreamCreateWithFlags(&h->graph_stream, hipStreamNonBlocking);
-    if (e == hipSuccess && !h->graph_ev_in) e = hipEventCreateWithFlags(&h->graph_ev_in, hipEventDisableTiming);
-    if (e == hipSuccess && !h->graph_ev_out) e = hipEventCreateWithFlags(&h->graph_ev_out, hipEventDisableTiming);
+    if (!h->graph_stream) e = hipStreamCreateWithFlags(h->graph_stream.put(), hipStreamNonBlocking);
+    if (e == hipSuccess && !h->graph_ev_in) e = hipEventCreateWithFlags(h->graph_ev_in.put(), hipEventDisableTiming);
+    if (e == hipSuccess && !h->graph_ev_out) e = hipEventCreateWithFlags(h->graph_ev_out.put(), hipEventDisableTiming);
     for (int i = 0; i < 2 && e == hipSuccess; ++i)
-        if (!h->graph_done[i]) e = hipEventCreateWithFlags(&h->graph_done[i], hipEventDisableTiming);
-    hipGraph_t graph = nullptr;
-    if (e == hipSuccess) e = capture_slots<R>(h, sp, P, F, GRAPH_SLOTS, h->graph_stream, &graph);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipGraphInstantiate(&h->graph_exec[i], graph, nullptr, nullptr, 0);
-    if (graph) hipGraphDestroy(graph);
+        if (!h->graph_done[i]) e = hipEventCreateWithFlags(h->graph_done[i].put(), hipEventDisableTiming);
+    {
+        Graph graph;  // (the executables keep what they need of it)
+        if (e == hipSuccess) e = capture_slots<R>(h, sp, P, F, GRAPH_SLOTS, h->graph_stream, graph.put());
+        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipGraphInstantiate(h->graph_exec[i].put(), graph, nullptr, nullptr, 0);
+    }
     if (e != hipSuccess) {  // no graphs on this runtime: the eager loop serves
         (void)hipGetLastError();
-        for (int i = 0; i < 2; ++i) {
-            if (h->graph_exec[i]) hipGraphExecDestroy(h->graph_exec[i]);
-            h->graph_exec[i] = nullptr;
-        }
+        drop_graph(h);
         h->graph_on = false;
         return false;
     }
@@ -1965,7 +1908,7 @@ static int closed_loop_impl(mppi_handle *h, int n_iters, double *u0_trace, mppi_
         }
         for (int a = 1; a < h->B; ++a) {  // an agent at the end of its path stops the batch like the single agent does
             const StepResult *ra =
-                reinterpret_cast<const StepResult *>(reinterpret_cast<const char *>(h->h_res) + (size_t)a * h->res_bytes);
+                reinterpret_cast<const StepResult *>(reinterpret_cast<const char *>(h->h_res.get()) + (size_t)a * h->res_bytes);
             if (ra->status == STATUS_PATH_END) h->h_res->status = STATUS_PATH_END;
         }
         if (h->h_res->status == STATUS_PATH_END || h->h_res->status == STATUS_EXCHANGE_FAILED) break;
@@ -2022,29 +1965,20 @@ static int time_rollout_impl(mppi_handle *h, int n_slots, int extra, hipStream_t
                                 "inside a stream capture)");
     if (!h->dev_loop_primed) launch_set_state<R>(P, nullptr, s);
     HIPCHECK(h, hipStreamSynchronize(s));
-    struct Scope {  // the stream and the event pair are released on every exit
-        hipStream_t gs = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Scope() {
-            if (e0) hipEventDestroy(e0);
-            if (e1) hipEventDestroy(e1);
-            if (gs) hipStreamDestroy(gs);
-        }
-    } sc;
-    HIPCHECK(h, hipStreamCreateWithFlags(&sc.gs, hipStreamNonBlocking));
-    HIPCHECK(h, hipEventCreate(&sc.e0));
-    HIPCHECK(h, hipEventCreate(&sc.e1));
-    const hipStream_t gs = sc.gs;
-    const hipEvent_t e0 = sc.e0, e1 = sc.e1;
+    Stream gs;  // (the events go before the stream, on every exit)
+    Event e1, e0;
+    HIPCHECK(h, hipStreamCreateWithFlags(gs.put(), hipStreamNonBlocking));
+    HIPCHECK(h, hipEventCreate(e0.put()));
+    HIPCHECK(h, hipEventCreate(e1.put()));
     const int saved = h->rollout_repeats, reps = 4;
     double ms[2] = {0.0, 0.0};
     int rc = MPPI_OK;
     for (int v = 0; v < 2 && rc == MPPI_OK; ++v) {
         h->rollout_repeats = v == 0 ? 1 : 1 + extra;
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        hipError_t e = capture_slots<R>(h, sp, P, F, n_slots, gs, &graph);  // (a diagnostic: the caller's launch counters stay)
-        if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        Graph graph;  // (both go at the end of the variant, the executable first)
+        GraphExec exec;
+        hipError_t e = capture_slots<R>(h, sp, P, F, n_slots, gs, graph.put());  // (a diagnostic: the caller's launch counters stay)
+        if (e == hipSuccess) e = hipGraphInstantiate(exec.put(), graph, nullptr, nullptr, 0);
         if (e == hipSuccess) e = hipGraphLaunch(exec, gs);  // warm
         if (e == hipSuccess) e = hipStreamSynchronize(gs);
         const double w0 = now_s();
@@ -2056,8 +1990,6 @@ static int time_rollout_impl(mppi_handle *h, int n_slots, int extra, hipStream_t
         float t = 0.f;
         if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
         ms[v] = t;
-        if (exec) hipGraphExecDestroy(exec);
-        if (graph) hipGraphDestroy(graph);
         if (e != hipSuccess) {
             h->err = std::string("mppi_time_rollout_launch: ") + hipGetErrorString(e);
             rc = MPPI_ERR_HIP;
@@ -2093,12 +2025,6 @@ extern "C" int mppi_time_rollout_launch(mppi_handle *h, int32_t n_slots, int32_t
 // Batched stage methods (include/mppi_hip.h, mppi_eval_*): host arrays in, host arrays out; the arithmetic is the
 // device code of the rollout kernels in the handle's precision.
 // ------------------------------------------------------------------------------------------
-struct DevBuf {  // scratch device buffer released at scope exit
-    void *p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-};
-
 static void eval_transition_mlp(mppi_handle *h, const KParams<float> &P, const void *x, const void *v, int n, void *out) {
     launch_eval_mlp(P, h->mlp, h->sw, (const float *)x, (const float *)v, n, (float *)out, nullptr);
 }
@@ -2112,37 +2038,38 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
     const bool need_x = what != EVAL_CLAMP, need_v = what == EVAL_TRANSITION || what == EVAL_CLAMP;
     const bool need_idx = what == EVAL_COST_STAGE || what == EVAL_COST_TERMINAL || what < 0;  // what < 0: index only
     const int n_out = what == EVAL_TRANSITION ? nx : what == EVAL_CLAMP ? 2 : 1;
-    DevBuf dx, dv, di, dp, dout;
+    DevBuf<R> dx, dv, dout;
+    DevBuf<int> di, dp;
     if (need_x) {
         HIPCHECK(h, dx.alloc(sizeof(R) * (size_t)n * nx));
-        if (int rc = upload_real(h, dx.p, x, (size_t)n * nx)) return rc;
+        if (int rc = upload_real(h, dx, x, (size_t)n * nx)) return rc;
     }
     if (need_v) {
         HIPCHECK(h, dv.alloc(sizeof(R) * (size_t)n * 2));
-        if (int rc = upload_real(h, dv.p, v, (size_t)n * 2)) return rc;
+        if (int rc = upload_real(h, dv, v, (size_t)n * 2)) return rc;
     }
     if (need_idx) {
         if (!prev_idx) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval: prev_idx is null");
         if (*prev_idx < 0 || *prev_idx >= P.n_ref) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval: waypoint index %d out of range", *prev_idx);
         HIPCHECK(h, di.alloc(sizeof(int) * (size_t)n));
         HIPCHECK(h, dp.alloc(sizeof(int)));
-        launch_eval_index<R>(P, (const R *)dx.p, nx, n, *prev_idx, update ? 1 : 0, (int *)di.p, (int *)dp.p, nullptr);
+        launch_eval_index<R>(P, dx, nx, n, *prev_idx, update ? 1 : 0, di, dp, nullptr);
     }
     if (what >= 0) {
         HIPCHECK(h, dout.alloc(sizeof(R) * (size_t)n * n_out));
         if (what == EVAL_TRANSITION && h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP)  // x + dt (f + MLP([x, v])), fp32 handles only
-            eval_transition_mlp(h, P, dx.p, dv.p, n, dout.p);
+            eval_transition_mlp(h, P, dx, dv, n, dout);
         else
-            launch_eval<R>(P, what, (const R *)dx.p, (const R *)dv.p, (const int *)di.p, n, (R *)dout.p, nullptr);
+            launch_eval<R>(P, what, dx, dv, di, n, dout, nullptr);
     }
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipDeviceSynchronize());
     if (what >= 0)
-        if (int rc = download_real(h, out, dout.p, (size_t)n * n_out)) return rc;
+        if (int rc = download_real(h, out, dout, (size_t)n * n_out)) return rc;
     if (need_idx) {
-        if (idx_out) HIPCHECK(h, hipMemcpy(idx_out, di.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+        if (idx_out) HIPCHECK(h, hipMemcpy(idx_out, di, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
         int pn = *prev_idx;
-        HIPCHECK(h, hipMemcpy(&pn, dp.p, sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHECK(h, hipMemcpy(&pn, dp, sizeof(int), hipMemcpyDeviceToHost));
         if (update) *prev_idx = pn;
     }
     return MPPI_OK;
@@ -2183,30 +2110,30 @@ extern "C" int mppi_eval_moving_average(mppi_handle *h, const double *xx, double
     if (!h || !xx || !out) return MPPI_ERR_BAD_ARG;
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     const int T = h->cfg.T;
-    DevBuf in, o;
+    DevBuf<void> in, o;
     HIPCHECK(h, in.alloc(rsz(h) * 2 * T));
     HIPCHECK(h, o.alloc(rsz(h) * 2 * T));
-    if (int rc = upload_real(h, in.p, xx, (size_t)2 * T)) return rc;
+    if (int rc = upload_real(h, in, xx, (size_t)2 * T)) return rc;
     with_real(h, [&](auto r) {
         using R = decltype(r);
-        launch_eval_filter<R>((const R *)in.p, (R *)o.p, T, h->cfg.filter_window, h->cfg.filter_mode, nullptr);
+        launch_eval_filter<R>((const R *)in.get(), (R *)o.get(), T, h->cfg.filter_window, h->cfg.filter_mode, nullptr);
     });
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipDeviceSynchronize());
-    return download_real(h, out, o.p, (size_t)2 * T);
+    return download_real(h, out, o, (size_t)2 * T);
 }
 
 extern "C" int mppi_eval_weights(mppi_handle *h, const double *S, int32_t n, double *w) {
     if (!h || !S || !w || n < 1) return MPPI_ERR_BAD_ARG;
     HIPCHECK(h, hipSetDevice(h->cfg.device));
-    DevBuf in, o;
+    DevBuf<double> in, o;
     HIPCHECK(h, in.alloc(sizeof(double) * (size_t)n));
     HIPCHECK(h, o.alloc(sizeof(double) * (size_t)n));
-    HIPCHECK(h, hipMemcpy(in.p, S, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    launch_eval_weights((const double *)in.p, n, softmin_beta(h->cfg), (double *)o.p, nullptr);
+    HIPCHECK(h, hipMemcpy(in, S, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    launch_eval_weights(in, n, softmin_beta(h->cfg), o, nullptr);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipDeviceSynchronize());
-    HIPCHECK(h, hipMemcpy(w, o.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(w, o, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
     return MPPI_OK;
 }
 

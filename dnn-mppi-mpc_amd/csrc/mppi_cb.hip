@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/mppi_hip.h"
+#include "mppi_owner.h"
 #include "philox.h"
 
 namespace {
@@ -214,7 +215,7 @@ __global__ void k_cb_nominal(const CbParams P, const float *__restrict__ U, cons
 struct mppi_cb_handle {
     mppi_cb_config cfg;
     CbParams P;
-    float *d_U = nullptr, *d_state = nullptr, *d_cost = nullptr, *d_omega = nullptr, *d_action = nullptr, *d_uinit = nullptr;
+    mppi::DevBuf<float> d_U, d_state, d_cost, d_omega, d_action, d_uinit;  // (released by `delete h`)
     long long iter = 0;
     std::string err;
 };
@@ -299,12 +300,12 @@ extern "C" int mppi_cb_create(const mppi_cb_config *c, mppi_cb_handle **out) {
     };
     hipError_t e;
     if ((e = hipSetDevice(c->device)) != hipSuccess) return fail("hipSetDevice", e);
-    if ((e = hipMalloc((void **)&h->d_U, sizeof(float) * c->T * nu)) != hipSuccess) return fail("hipMalloc", e);
-    if ((e = hipMalloc((void **)&h->d_state, sizeof(float) * CB_NX)) != hipSuccess) return fail("hipMalloc", e);
-    if ((e = hipMalloc((void **)&h->d_cost, sizeof(float) * c->K)) != hipSuccess) return fail("hipMalloc", e);
-    if ((e = hipMalloc((void **)&h->d_omega, sizeof(float) * c->K)) != hipSuccess) return fail("hipMalloc", e);
-    if ((e = hipMalloc((void **)&h->d_action, sizeof(float) * CB_NU)) != hipSuccess) return fail("hipMalloc", e);
-    if ((e = hipMalloc((void **)&h->d_uinit, sizeof(float) * CB_NU)) != hipSuccess) return fail("hipMalloc", e);
+    if ((e = h->d_U.alloc(sizeof(float) * c->T * nu)) != hipSuccess) return fail("hipMalloc", e);
+    if ((e = h->d_state.alloc(sizeof(float) * CB_NX)) != hipSuccess) return fail("hipMalloc", e);
+    if ((e = h->d_cost.alloc(sizeof(float) * c->K)) != hipSuccess) return fail("hipMalloc", e);
+    if ((e = h->d_omega.alloc(sizeof(float) * c->K)) != hipSuccess) return fail("hipMalloc", e);
+    if ((e = h->d_action.alloc(sizeof(float) * CB_NU)) != hipSuccess) return fail("hipMalloc", e);
+    if ((e = h->d_uinit.alloc(sizeof(float) * CB_NU)) != hipSuccess) return fail("hipMalloc", e);
     if ((e = hipMemset(h->d_U, 0, sizeof(float) * c->T * nu)) != hipSuccess) return fail("hipMemset", e);
     float ui[CB_NU];
     for (int i = 0; i < CB_NU; ++i) ui[i] = (float)c->u_init[i];
@@ -316,8 +317,6 @@ extern "C" int mppi_cb_create(const mppi_cb_config *c, mppi_cb_handle **out) {
 extern "C" int mppi_cb_destroy(mppi_cb_handle *h) {
     if (!h) return MPPI_OK;
     hipSetDevice(h->cfg.device);
-    for (float *p : {h->d_U, h->d_state, h->d_cost, h->d_omega, h->d_action, h->d_uinit})
-        if (p) hipFree(p);
     delete h;
     return MPPI_OK;
 }
@@ -384,14 +383,10 @@ extern "C" int mppi_cb_eval(mppi_cb_handle *h, int32_t what, const double *state
     if (!h || !states || !actions || !out || n < 1 || (what != 0 && what != 1)) return MPPI_ERR_BAD_ARG;
     CB_HIP(h, hipSetDevice(h->cfg.device));
     const int nx = h->P.nx, nu = h->P.nu, n_out = what == 0 ? nx : 1;
-    struct Scratch {  // released on every exit, the early ones of CB_HIP included
-        float *p = nullptr;
-        ~Scratch() { if (p) hipFree(p); }
-    } s_ds, s_du, s_dout;
-    CB_HIP(h, hipMalloc((void **)&s_ds.p, sizeof(float) * (size_t)n * nx));
-    CB_HIP(h, hipMalloc((void **)&s_du.p, sizeof(float) * (size_t)n * nu));
-    CB_HIP(h, hipMalloc((void **)&s_dout.p, sizeof(float) * (size_t)n * n_out));
-    float *ds = s_ds.p, *du = s_du.p, *dout = s_dout.p;
+    mppi::DevBuf<float> ds, du, dout;  // released on every exit, the early ones of CB_HIP included
+    CB_HIP(h, ds.alloc(sizeof(float) * (size_t)n * nx));
+    CB_HIP(h, du.alloc(sizeof(float) * (size_t)n * nu));
+    CB_HIP(h, dout.alloc(sizeof(float) * (size_t)n * n_out));
     int rc = cb_io(h, ds, nullptr, states, (size_t)n * nx);
     if (!rc) rc = cb_io(h, du, nullptr, actions, (size_t)n * nu);
     if (!rc) {
@@ -407,12 +402,8 @@ extern "C" int mppi_cb_nominal_trajectory(mppi_cb_handle *h, const double *state
     CB_HIP(h, hipSetDevice(h->cfg.device));
     float st[CB_NX] = {0, 0, 0, 0, 0};
     for (int i = 0; i < h->P.nx; ++i) st[i] = (float)state[i];
-    struct Scratch {
-        float *p = nullptr;
-        ~Scratch() { if (p) hipFree(p); }
-    } s_dt;
-    CB_HIP(h, hipMalloc((void **)&s_dt.p, sizeof(float) * (size_t)h->P.T * h->P.nx));
-    float *dt = s_dt.p;
+    mppi::DevBuf<float> dt;
+    CB_HIP(h, dt.alloc(sizeof(float) * (size_t)h->P.T * h->P.nx));
     CB_HIP(h, hipMemcpy(h->d_state, st, sizeof(st), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_cb_nominal, dim3(1), dim3(64), 0, nullptr, h->P, h->d_U, h->d_state, dt);
     int rc = hipDeviceSynchronize() == hipSuccess ? MPPI_OK : MPPI_ERR_HIP;
