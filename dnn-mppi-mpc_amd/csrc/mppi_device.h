@@ -43,6 +43,7 @@ __device__ __forceinline__ int nearest_in_window(const R *__restrict__ ref, int 
 constexpr int WINDOW_LDS_MAX = 256;  // candidates
 
 template <typename R> struct alignas(16) RefPair { R x0, x1, y0, y1; };
+template <typename R> struct alignas(4 * sizeof(R)) VecT4 { R x, y, z, w; };  // four values, one aligned load / store
 
 template <typename R>
 __device__ __forceinline__ void stage_window(RefPair<R> *sh, const R *__restrict__ ref, int c, int wlen, int tid,
@@ -241,6 +242,140 @@ __device__ __forceinline__ R tracking_cost(const KParams<R> &P, const R (&w)[4],
     return tracking_cost_row<R, MODEL>(P, w, wrap, P.ref + 4 * i, x, y, yaw, vel);
 }
 
+// ------------------------------------------------------------------------------------------
+// The per-step formulas of the reference, one definition each, for every rollout layout to call ("Per-step
+// formulas", lists the callers and the sites that keep their own text).  Which lane owns which step, what is masked beyond
+// the horizon and what stays in registers is the kernels' business.
+// ------------------------------------------------------------------------------------------
+// noise of sample k at step t (`_calc_epsilon` mppi_differential_drive.py:273-283): drawn (philox.h; k_offset: the shard's
+// first sample, noise_stream + agent: the counter's fourth word) or read from the tensor of (iter, agent).  The caller
+// keeps t inside the horizon.  `philox`: P.use_philox, or the constant true of a PLAIN instantiation.
+template <typename R>
+__device__ __forceinline__ void noise_at(const KParams<R> &P, bool philox, unsigned iter, int agent, int k, int t, float &e0, float &e1) {
+    if (philox) {
+        px::sample(P.seed_lo, P.seed_hi, iter, (unsigned)(k + P.k_offset), t, P.chol, e0, e1, (unsigned)(P.noise_stream + agent));
+    } else {
+        const float2 e = *reinterpret_cast<const float2 *>(eps_tensor(P, iter, agent) + ((size_t)k * P.T + t) * 2);
+        e0 = e.x; e1 = e.y;
+    }
+}
+// the same for a lane that owns steps 2l and 2l+1: ONE Philox block feeds both (words r0,r1 -> step 2l, r2,r3 -> step
+// 2l+1: the sampler's layout), or two 8-byte loads.  Step 2l lies inside the horizon (the caller's condition); `a1`: so does
+// step 2l+1 -- otherwise its noise comes back 0.
+template <typename R>
+__device__ __forceinline__ void noise_pair(const KParams<R> &P, bool philox, unsigned iter, int agent, int k, int l, bool a1,
+                                           float &e00, float &e01, float &e10, float &e11) {
+    e10 = 0.f; e11 = 0.f;
+    if (philox) {
+        unsigned r[4];
+        px::philox4x32_10((unsigned)(k + P.k_offset), (unsigned)l, iter, (unsigned)(P.noise_stream + agent), P.seed_lo, P.seed_hi, r);
+        px::box_muller(r[0], r[1], P.chol, e00, e01);
+        px::box_muller(r[2], r[3], P.chol, e10, e11);
+        if (!a1) { e10 = 0.f; e11 = 0.f; }
+    } else {
+        const float *pe = eps_tensor(P, iter, agent) + ((size_t)k * P.T + 2 * l) * 2;
+        const float2 ea = *reinterpret_cast<const float2 *>(pe);
+        e00 = ea.x; e01 = ea.y;
+        if (a1) {
+            const float2 eb = *reinterpret_cast<const float2 *>(pe + 2);
+            e10 = eb.x; e11 = eb.y;
+        }
+    }
+}
+
+// perturb (the first (1 - exploration) K samples explore around u, the rest around 0: :116-119) and clamp (`_g` :285-289;
+// the visualisation rollouts always clamp, :148,:158)
+// (the two halves apart for the learned model's visualisation rows, which clamp the nominal row in the same statement)
+template <typename R> __device__ __forceinline__ void perturb(bool exploit, R u0, R u1, float e0, float e1, R &v0, R &v1) {
+    v0 = exploit ? u0 + (R)e0 : (R)e0;
+    v1 = exploit ? u1 + (R)e1 : (R)e1;
+}
+template <typename R> __device__ __forceinline__ void clamp_controls(const KParams<R> &P, R &v0, R &v1) {
+    v0 = mf::clamp(v0, P.umax0);
+    v1 = mf::clamp(v1, P.umax1);
+}
+template <typename R>
+__device__ __forceinline__ void perturb_clamp(const KParams<R> &P, bool exploit, bool clamp, R u0, R u1, float e0, float e1, R &v0, R &v1) {
+    perturb(exploit, u0, u1, e0, e1, v0, v1);
+    if (clamp) clamp_controls(P, v0, v1);
+}
+
+// the control term of the stage cost.  The two models associate it differently and f32 parity depends on that:
+// u^T Sigma^-1 v (mppi_differential_drive.py:124) and u (Sigma^-1 v) (mppi_race_car.py:84)
+template <typename R, int MODEL> __device__ __forceinline__ R control_cost(const KParams<R> &P, R u0, R u1, R v0, R v1) {
+    if (MODEL == MODEL_DIFF) return (u0 * P.sinv[0] + u1 * P.sinv[2]) * v0 + (u0 * P.sinv[1] + u1 * P.sinv[3]) * v1;
+    return u0 * (P.sinv[0] * v0 + P.sinv[1] * v1) + u1 * (P.sinv[2] * v0 + P.sinv[3] * v1);
+}
+
+// cost of one state: tracking error + the collision penalty (`_compute_cost` / `_c`, `_terminal_cost` / `_phi` with
+// `_is_collided`); stage cost = that under the stage weights + gamma * control term (:124, mppi_race_car.py:84), terminal
+// cost = that under the terminal weights (:128).  `hit`: collided() of the state; `ctrl`: control_cost of the step where
+// the caller already holds it (the look-back moves it across lanes), else stage_cost takes it behind the tracking error.
+// _row: against a waypoint's row {x, y, yaw, v} instead of its index (the look-back prices a sample under every candidate).
+template <typename R, int MODEL>
+__device__ __forceinline__ R state_cost_row(const KParams<R> &P, const R (&w)[4], bool wrap, const R *r, R x, R y, R yaw, R vel, bool hit) {
+    R c = tracking_cost_row<R, MODEL>(P, w, wrap, r, x, y, yaw, vel);
+    if (hit) c += P.penalty;
+    return c;
+}
+template <typename R, int MODEL>
+__device__ __forceinline__ R stage_cost_row(const KParams<R> &P, bool wrap, const R *r, R x, R y, R yaw, R vel, bool hit, R ctrl) {
+    return state_cost_row<R, MODEL>(P, P.ws, wrap, r, x, y, yaw, vel, hit) + P.gamma * ctrl;
+}
+template <typename R, int MODEL>
+__device__ __forceinline__ R stage_cost(const KParams<R> &P, bool wrap, int i, R x, R y, R yaw, R vel, bool hit, R u0, R u1, R v0, R v1) {
+    const R c = state_cost_row<R, MODEL>(P, P.ws, wrap, P.ref + 4 * i, x, y, yaw, vel, hit);
+    return c + P.gamma * control_cost<R, MODEL>(P, u0, u1, v0, v1);
+}
+template <typename R, int MODEL>
+__device__ __forceinline__ R terminal_cost_row(const KParams<R> &P, bool wrap, const R *r, R x, R y, R yaw, R vel, bool hit) {
+    return state_cost_row<R, MODEL>(P, P.wt, wrap, r, x, y, yaw, vel, hit);
+}
+template <typename R, int MODEL>
+__device__ __forceinline__ R terminal_cost(const KParams<R> &P, bool wrap, int i, R x, R y, R yaw, R vel, bool hit) {
+    return terminal_cost_row<R, MODEL>(P, wrap, P.ref + 4 * i, x, y, yaw, vel, hit);
+}
+
+// `S[k] += ...` one step at a time (mppi_race_car.py:84) over a sample's T stage costs and its terminal cost in a row of
+// LDS: in f32 with 1e10 collision penalties the order of the additions decides which tracking terms survive
+__device__ __forceinline__ float sum_rows_in_order(const float *row, int T) {
+    float S = 0.f;
+    for (int t = 0; t <= T; ++t) S += row[t];
+    return S;
+}
+
+// The workgroup's softmin record {rho_b, eta_b, eta2_b, pad, W_b[T][2]} (:132-135, :175 with the 1/eta factored out):
+// column i of W_b = the sum over the rows of sh_acc (row q: e_q eps[q, :, :], or a half-wave's private sums) ...
+template <int ROWS, int PITCH, typename R>
+__device__ __forceinline__ void record_columns(R *out, const R (&sh_acc)[ROWS][PITCH], int T) {
+    for (int i = threadIdx.x; i < 2 * T; i += blockDim.x) {
+        R s = 0;
+#pragma unroll
+        for (int q = 0; q < ROWS; ++q) s += sh_acc[q][i];
+        out[4 + i] = s;
+    }
+}
+// ... and its head (one thread): eta = sum e, eta2 = sum e^2 over sh_e, or over the half-waves' rescaled {eta, eta2, n_hit}
+// of sh_eta; {rho, eta, eta2} into the record and {rho, eta, eta2, n_hit} into the compact copy the merge kernels read
+// (n_hit: samples whose cost carries a collision penalty, mppi_stats::n_collided)
+template <typename R> __device__ __forceinline__ void record_head_store(const KParams<R> &P, R *out, size_t slot, R rho, R eta, R eta2, R n_hit) {
+    out[0] = rho; out[1] = eta; out[2] = eta2;
+    *reinterpret_cast<VecT4<R> *>(P.heads + 4 * slot) = VecT4<R>{rho, eta, eta2, n_hit};
+}
+template <int N, typename R>
+__device__ __forceinline__ void record_head(const KParams<R> &P, R *out, size_t slot, R rho, const R (&sh_e)[N], R n_hit) {
+    R eta = 0, eta2 = 0;
+#pragma unroll
+    for (int q = 0; q < N; ++q) { const R ew = sh_e[q]; eta += ew; eta2 += ew * ew; }
+    record_head_store(P, out, slot, rho, eta, eta2, n_hit);
+}
+template <int N, typename R>
+__device__ __forceinline__ void record_head(const KParams<R> &P, R *out, size_t slot, R rho, const R (&sh_eta)[N][3]) {
+    R eta = 0, eta2 = 0, n_hit = 0;
+#pragma unroll
+    for (int q = 0; q < N; ++q) { eta += sh_eta[q][0]; eta2 += sh_eta[q][1]; n_hit += sh_eta[q][2]; }
+    record_head_store(P, out, slot, rho, eta, eta2, n_hit);
+}
 
 // controller state of this launch: *st, with the observed state / x0 index overridden by kernel arguments
 // The controller state as ONE vector load (lane i <- dword i) + readlanes: a struct copy through scalar loads is

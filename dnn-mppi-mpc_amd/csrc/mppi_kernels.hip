@@ -120,16 +120,7 @@ template <typename R, int MODEL, bool OBS = true, bool PLAIN = false> struct Rol
         const int t = ch * 64 + lane;
         e0 = 0.f;
         e1 = 0.f;
-        if (t < P.T) {
-            if (use_philox()) {
-                px::sample(P.seed_lo, P.seed_hi, iter, (unsigned)(k + P.k_offset), t, P.chol, e0, e1,
-                           (unsigned)(P.noise_stream + agent));
-            } else {
-                const float2 e = *reinterpret_cast<const float2 *>(eps_tensor(P, iter, agent) + ((size_t)k * P.T + t) * 2);
-                e0 = e.x;
-                e1 = e.y;
-            }
-        }
+        if (t < P.T) noise_at(P, use_philox(), iter, agent, k, t, e0, e1);
     }
 
     // S2-S3 of steps [64 ch, 64 ch + 64): this lane's controls and the state after its step (returns the noise it used)
@@ -282,14 +273,7 @@ template <typename R, int MODEL, bool OBS = true, bool PLAIN = false> struct Rol
         const bool last_chunk = ch == n_chunk - 1;
         if (P.accumulate || last_chunk) {
             const bool hit = OBS ? collided<MODEL == MODEL_RACE>(P, x, y, yaw, obs) : false;
-            R st_c = tracking_cost<R, MODEL>(P, P.ws, wrap_stage(), my_idx, x, y, yaw, vel);
-            if (hit) st_c += P.penalty;
-            R ctrl;
-            if (MODEL == MODEL_DIFF)  // u^T Sigma^-1 v, :124
-                ctrl = (u0 * P.sinv[0] + u1 * P.sinv[2]) * v0 + (u0 * P.sinv[1] + u1 * P.sinv[3]) * v1;
-            else  // u (Sigma^-1 v), mppi_race_car.py:84
-                ctrl = u0 * (P.sinv[0] * v0 + P.sinv[1] * v1) + u1 * (P.sinv[2] * v0 + P.sinv[3] * v1);
-            const R stage = st_c + P.gamma * ctrl;
+            const R stage = stage_cost<R, MODEL>(P, wrap_stage(), my_idx, x, y, yaw, vel, hit, u0, u1, v0, v1);
             if (P.accumulate) {
                 if (sizeof(R) == 4) {
                     // `S[k] += ...` one step at a time (mppi_race_car.py:84): with 1e10 collision penalties
@@ -315,8 +299,7 @@ template <typename R, int MODEL, bool OBS = true, bool PLAIN = false> struct Rol
                     p = nearest_uniform(ref, p, window_len<R>(P.window, P.n_ref, p), xt, yt, lane);
                     idx_term = p;
                 }
-                R term = tracking_cost<R, MODEL>(P, P.wt, wrap_term(), idx_term, x, y, yaw, vel);
-                if (hit) term += P.penalty;
+                const R term = terminal_cost<R, MODEL>(P, wrap_term(), idx_term, x, y, yaw, vel, hit);
                 s_last = P.accumulate ? term : stage + term;
             }
         }
@@ -448,18 +431,14 @@ __device__ __forceinline__ R fused_lookback(const KParams<R> &P, const DevState 
         if (valid) {  // (every lane takes part in the ballot and the lane reads; lanes >= LB_CAND price the last candidate again)
             const int ll = r.lane_last;
             const R xT = wv::read_lane(sp.x, ll), yT = wv::read_lane(sp.y, ll), yawT = wv::read_lane(sp.yaw, ll);
-            const R ctrl = (sp.u0 * P.sinv[0] + sp.u1 * P.sinv[2]) * sp.v0 + (sp.u0 * P.sinv[1] + sp.u1 * P.sinv[3]) * sp.v1;  // :124
+            const R ctrl = control_cost<R, MODEL_DIFF>(P, sp.u0, sp.u1, sp.v0, sp.v1);
             const R ctrlT = wv::read_lane(ctrl, ll);
             const bool hit_lane = OBS ? collided<false>(P, sp.x, sp.y, sp.yaw, obs) : false;
             const bool hitT = OBS ? ((__ballot(hit_lane) >> ll) & 1ull) != 0ull : false;
             const VecT4<R> row = sh_row[min(lane, nc - 1)];
             const R rr[4] = {row.x, row.y, row.z, row.w};
-            R st_c = tracking_cost_row<R, MODEL_DIFF>(P, P.ws, r.wrap_stage(), rr, xT, yT, yawT, R(0));
-            if (hitT) st_c += P.penalty;
-            const R stage = st_c + P.gamma * ctrlT;
-            R term = tracking_cost_row<R, MODEL_DIFF>(P, P.wt, r.wrap_term(), rr, xT, yT, yawT, R(0));
-            if (hitT) term += P.penalty;
-            cost_j = stage + term;
+            const R stage = stage_cost_row<R, MODEL_DIFF>(P, r.wrap_stage(), rr, xT, yT, yawT, R(0), hitT, ctrlT);
+            cost_j = stage + terminal_cost_row<R, MODEL_DIFF>(P, r.wrap_term(), rr, xT, yT, yawT, R(0), hitT);
         }
         if (lane < LB_CAND) sh_cost[wid][lane] = cost_j;
     }
@@ -656,26 +635,9 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
     __syncthreads();
     const size_t slot = (size_t)agent * P.slots + blockIdx.x;  // this workgroup's record
     R *out = partials + slot * record_len(P.T, (int)sizeof(R));
-    for (int i = threadIdx.x; i < 2 * P.T; i += blockDim.x) {  // W_b[t] = sum_k e_k eps[k, t], :132-135
-        R s = 0;
-#pragma unroll
-        for (int w = 0; w < FUSED_WAVES; ++w) s += sh_acc[w][i];
-        out[4 + i] = s;
-    }
+    record_columns(out, sh_acc, P.T);
     if (threadIdx.x == 64 * (FUSED_WAVES - 1)) {  // a lane of the last wave: the first ones carry the column sums
-        // (the head's fourth word: how many of the workgroup's samples carry a collision penalty in their cost -- mppi_stats::n_collided)
-        R eta = 0, eta2 = 0;
-        const R n_hit = (R)n_hit_i;
-#pragma unroll
-        for (int w = 0; w < FUSED_WAVES; ++w) {
-            const R ew = sh_e[w];
-            eta += ew;
-            eta2 += ew * ew;
-        }
-        out[0] = rho;
-        out[1] = eta;
-        out[2] = eta2;
-        *reinterpret_cast<VecT4<R> *>(P.heads + 4 * slot) = VecT4<R>{rho, eta, eta2, n_hit};
+        record_head(P, out, slot, rho, sh_e, (R)n_hit_i);
         if (seq_search) publish_first_mover<FUSED_WAVES>(sh_mover, &(P.st + agent)->first_k);
     }
     STAMP(4);
@@ -685,8 +647,8 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
 // T <= 64: two samples per wave, two steps per lane.  Each 32-lane half of a wave owns one sample and
 // lane l of the half owns steps 2l and 2l+1, so ONE Philox4x32 call feeds both of its steps (words r0,r1
 // and r2,r3 -- the sampler's layout), the scans are 5 DPP steps over lane totals plus one add, and a
-// workgroup leaves one record per 32 samples (half as many for k_finalize to merge).  Same arithmetic per
-// step as Rollout::chunk; only the association of the prefix sums differs.
+// workgroup leaves one record per 32 samples (half as many for k_finalize to merge).  The draw is noise_pair
+// and the per-step costs stage_cost (mppi_device.h); which sites keep their own text: DESIGN section 3, "Per-step formulas".
 // ------------------------------------------------------------------------------------------
 // SPW = samples per wave.  2: the layout above (T <= 64).  1: one sample per wave with two steps per lane, T <= 128 --
 // for 64 < T <= 128 this replaces two 64-step chunks of k_rollout_fused (the second one mostly idle lanes: T = 75 runs
@@ -776,25 +738,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, (sizeof(R) == 4 && MODEL == MODEL_
     // ---- S1: this lane's noise for its two steps ---------------------------------------------------------
     e00 = 0.f; e01 = 0.f; e10 = 0.f; e11 = 0.f;
     STAMP(8);
-    if (valid && a0) {
-        if (use_philox) {
-            unsigned r[4];
-            px::philox4x32_10((unsigned)(k + P.k_offset), (unsigned)l32, iter, (unsigned)(P.noise_stream + agent), P.seed_lo, P.seed_hi, r);
-            px::box_muller(r[0], r[1], P.chol, e00, e01);
-            px::box_muller(r[2], r[3], P.chol, e10, e11);
-            if (!a1) { e10 = 0.f; e11 = 0.f; }
-        } else {
-            const float *pe = eps_tensor(P, iter, agent) + ((size_t)k * T + t0) * 2;
-            const float2 ea = *reinterpret_cast<const float2 *>(pe);
-            e00 = ea.x;
-            e01 = ea.y;
-            if (a1) {
-                const float2 eb = *reinterpret_cast<const float2 *>(pe + 2);
-                e10 = eb.x;
-                e11 = eb.y;
-            }
-        }
-    }
+    if (valid && a0) noise_pair(P, use_philox, iter, agent, k, l32, a1, e00, e01, e10, e11);
     STAMP(9);
     S_k = R(INFINITY);
     if (__ballot(live) != 0ull || lookback) {  // at least one of the wave's two samples still needs its rollout (look-back: every wave takes part)
@@ -903,7 +847,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, (sizeof(R) == 4 && MODEL == MODEL_
                 const R lxs = sub_last ? px1 : px0, lys = sub_last ? py1 : py0, lyaws = sub_last ? yw1 : yw0;
                 const R xT = __shfl(lxs, src), yT = __shfl(lys, src), yawT = __shfl(lyaws, src);
                 const R ua = sub_last ? u10 : u00, ub = sub_last ? u11 : u01, va = sub_last ? v10 : v00, vb = sub_last ? v11 : v01;
-                const R ctrl = (ua * P.sinv[0] + ub * P.sinv[2]) * va + (ua * P.sinv[1] + ub * P.sinv[3]) * vb;  // :124
+                const R ctrl = control_cost<R, MODEL_DIFF>(P, ua, ub, va, vb);
                 const R ctrlT = __shfl(ctrl, src);
                 // the collision test of that one state (:301-313): a lane per circle -- lanes m < 32 of the wave hold circles
                 // 0 .. 31 -- instead of every lane walking all circles for a result only one lane's state needs
@@ -1012,14 +956,9 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, (sizeof(R) == 4 && MODEL == MODEL_
         STAMP(11);
 
         // ---- costs -----------------------------------------------------------------------------------------------
-        auto stage_cost = [&](R x, R y, R yaw, R vel, int idx, R ua, R ub, R va, R vb, bool &hit, bool have_sc = false) {
+        auto step_cost = [&](R x, R y, R yaw, R vel, int idx, R ua, R ub, R va, R vb, bool &hit, bool have_sc = false) {
             hit = collided<MODEL == MODEL_RACE>(P, x, y, yaw, obs, have_sc, sin_w0, cos_w0);
-            R st_c = tracking_cost<R, MODEL>(P, P.ws, wrap_stage, idx, x, y, yaw, vel);
-            if (hit) st_c += P.penalty;
-            R ctrl;
-            if (MODEL == MODEL_DIFF) ctrl = (ua * P.sinv[0] + ub * P.sinv[2]) * va + (ua * P.sinv[1] + ub * P.sinv[3]) * vb;
-            else ctrl = ua * (P.sinv[0] * va + P.sinv[1] * vb) + ub * (P.sinv[2] * va + P.sinv[3] * vb);
-            return st_c + P.gamma * ctrl;
+            return stage_cost<R, MODEL>(P, wrap_stage, idx, x, y, yaw, vel, hit, ua, ub, va, vb);
         };
         // state of the last step as held by lane_last of each half
         const R lx = sub_last ? px1 : px0, ly = sub_last ? py1 : py0, lyaw = sub_last ? yw1 : yw0, lvel = sub_last ? vl1 : vl0;
@@ -1028,9 +967,9 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, (sizeof(R) == 4 && MODEL == MODEL_
             total = lb_total;
         } else if (P.accumulate) {
             bool hit0, hit1;
-            const R st0 = stage_cost(px0, py0, yw0, vl0, idx0, u00, u01, v00, v01, hit0, true);
+            const R st0 = step_cost(px0, py0, yw0, vl0, idx0, u00, u01, v00, v01, hit0, true);
             STAMP(12);
-            const R st1 = stage_cost(px1, py1, yw1, vl1, idx1, u10, u11, v10, v11, hit1);
+            const R st1 = step_cost(px1, py1, yw1, vl1, idx1, u10, u11, v10, v11, hit1);
             STAMP(13);
             const bool hit_l = sub_last ? hit1 : hit0;
             R term = tracking_cost<R, MODEL>(P, P.wt, wrap_term, idx_term, lx, ly, lyaw, lvel);
@@ -1050,7 +989,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, (sizeof(R) == 4 && MODEL == MODEL_
         } else {  // `S[k] =`: only the last step's stage cost survives (:124)
             bool hit_l;
             const int idx_l = sub_last ? idx1 : idx0;
-            const R st_l = stage_cost(lx, ly, lyaw, lvel, idx_l, sub_last ? u10 : u00, sub_last ? u11 : u01,
+            const R st_l = step_cost(lx, ly, lyaw, lvel, idx_l, sub_last ? u10 : u00, sub_last ? u11 : u01,
                                       sub_last ? v10 : v00, sub_last ? v11 : v01, hit_l);
             R term = tracking_cost<R, MODEL>(P, P.wt, wrap_term, idx_term, lx, ly, lyaw, lvel);
             if (hit_l) term += P.penalty;
@@ -1083,8 +1022,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, (sizeof(R) == 4 && MODEL == MODEL_
             if (k_s < P.K) {
                 if (k_s >= k_start) {
                     const float *row = sh_st[lane];
-                    S = 0.f;
-                    for (int t = 0; t <= T; ++t) S += row[t];
+                    S = sum_rows_in_order(row, T);
                     S_[k_s] = (R)S;
                 } else {
                     S = (float)S_[k_s];  // final from an earlier speculation round
@@ -1132,12 +1070,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, (sizeof(R) == 4 && MODEL == MODEL_
     __syncthreads();
     const size_t slot = (size_t)agent * P.slots + blockIdx.x;  // this workgroup's record
     R *out = partials + slot * record_len(T, (int)sizeof(R));
-    for (int i = threadIdx.x; i < 2 * T; i += blockDim.x) {  // W_b[t] = sum_k e_k eps[k, t], :132-135
-        R acc = 0;
-#pragma unroll
-        for (int q = 0; q < ROWS; ++q) acc += sh_acc[q][i];
-        out[4 + i] = acc;
-    }
+    record_columns(out, sh_acc, T);
     if (threadIdx.x == 64 * (DUAL_WAVES - 1)) {
         R eta = 0, eta2 = 0;
         const R n_hit = P.obstacle_model != OBS_NONE ? (R)n_hit_i : R(0);
@@ -1161,7 +1094,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, (sizeof(R) == 4 && MODEL == MODEL_
 // wave (k_rollout_dual<.., 1, ..>) a horizon of 75 steps keeps 38 of 64 lanes busy; here a half-wave owns a sample and lane l
 // of the half the steps 3l, 3l+1, 3l+2 -- 25 of 32 lanes at T = 75.  A lane's three steps straddle two Philox blocks (the
 // sampler's counter is (k, t >> 1): words r0,r1 for even t, r2,r3 for odd t), so it draws two blocks and uses six of
-// their eight words.  Same arithmetic per step as k_rollout_dual (the association of the prefix sums differs); frozen
+// their eight words.  perturb_clamp, record_columns / record_head and sum_rows_in_order of mppi_device.h; frozen
 // waypoint index, `S[k] +=` summed in the reference's order through LDS (a lane per sample), one record per 32 samples.
 // ------------------------------------------------------------------------------------------
 constexpr int TRI_STEPS = 3, TRI_SAMPLES = 2 * DUAL_WAVES;
@@ -1240,12 +1173,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, SHARE ? 8 : 1) void k_rollout_tri(
     for (int i = 0; i < NS; ++i) {
         u[i][0] = a[i] ? P.u[2 * t[i]] : R(0);
         u[i][1] = a[i] ? P.u[2 * t[i] + 1] : R(0);
-        v[i][0] = exploit ? u[i][0] + e[i][0] : e[i][0];
-        v[i][1] = exploit ? u[i][1] + e[i][1] : e[i][1];
-        if (clamp_rollout) {
-            v[i][0] = mf::clamp(v[i][0], P.umax0);
-            v[i][1] = mf::clamp(v[i][1], P.umax1);
-        }
+        perturb_clamp(P, exploit, clamp_rollout, u[i][0], u[i][1], e[i][0], e[i][1], v[i][0], v[i][1]);
         if (!a[i]) { v[i][0] = 0; v[i][1] = 0; }
     }
     auto before = [&](R lane_total, R start) {  // `start` + the totals of the lanes before this one in its half
@@ -1293,7 +1221,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, SHARE ? 8 : 1) void k_rollout_tri(
                             : collided<true>(P, px_[i], py_[i], yw[i], obs);
         R st_c = tracking_cost<R, MODEL_RACE>(P, P.ws, wrap_stage, idx[i], px_[i], py_[i], yw[i], vl[i]);
         if (hit[i]) st_c += P.penalty;
-        const R ctrl = u[i][0] * (P.sinv[0] * v[i][0] + P.sinv[1] * v[i][1]) + u[i][1] * (P.sinv[2] * v[i][0] + P.sinv[3] * v[i][1]);  // mppi_race_car.py:84
+        const R ctrl = control_cost<R, MODEL_RACE>(P, u[i][0], u[i][1], v[i][0], v[i][1]);
         if (valid && a[i]) row[t[i]] = st_c + P.gamma * ctrl;
     }
     {
@@ -1303,9 +1231,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, SHARE ? 8 : 1) void k_rollout_tri(
             const R lyaw = sub_last == 0 ? yw[0] : sub_last == 1 ? yw[1] : yw[2], lvel = sub_last == 0 ? vl[0] : sub_last == 1 ? vl[1] : vl[2];
             const int li = sub_last == 0 ? idx[0] : sub_last == 1 ? idx[1] : idx[2];
             const bool lh = sub_last == 0 ? hit[0] : sub_last == 1 ? hit[1] : hit[2];
-            R term = tracking_cost<R, MODEL_RACE>(P, P.wt, wrap_term, li, lx, ly, lyaw, lvel);
-            if (lh) term += P.penalty;
-            row[T] = term;
+            row[T] = terminal_cost<R, MODEL_RACE>(P, wrap_term, li, lx, ly, lyaw, lvel, lh);
         }
     }
     __syncthreads();
@@ -1314,9 +1240,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, SHARE ? 8 : 1) void k_rollout_tri(
         const int k_s = blockIdx.x * ROWS + lane;
         float S = INFINITY;
         if (k_s < P.K) {
-            const float *rw = sh_st[lane];
-            S = 0.f;
-            for (int tt = 0; tt <= T; ++tt) S += rw[tt];
+            S = sum_rows_in_order(sh_st[lane], T);
             P.S[k_s] = S;
             P.pout[k_s] = c;
         }
@@ -1343,26 +1267,8 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, SHARE ? 8 : 1) void k_rollout_tri(
     __syncthreads();
     const size_t slot = blockIdx.x;
     R *out = partials + slot * record_len(T, (int)sizeof(R));
-    for (int i = threadIdx.x; i < 2 * T; i += blockDim.x) {  // W_b[t] = sum_k e_k eps[k, t]
-        R acc = 0;
-#pragma unroll
-        for (int q = 0; q < ROWS; ++q) acc += sh_acc[q][i];
-        out[4 + i] = acc;
-    }
-    if (threadIdx.x == 64 * (DUAL_WAVES - 1)) {
-        R eta = 0, eta2 = 0;
-#pragma unroll
-        for (int q = 0; q < ROWS; ++q) {
-            const R w = sh_e[q];
-            eta += w;
-            eta2 += w * w;
-        }
-        out[0] = rho;
-        out[1] = eta;
-        out[2] = eta2;
-        *reinterpret_cast<VecT4<R> *>(P.heads + 4 * slot) =
-            VecT4<R>{rho, eta, eta2, P.obstacle_model != OBS_NONE ? (R)n_hit_i : R(0)};
-    }
+    record_columns(out, sh_acc, T);
+    if (threadIdx.x == 64 * (DUAL_WAVES - 1)) record_head(P, out, slot, rho, sh_e, P.obstacle_model != OBS_NONE ? (R)n_hit_i : R(0));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1436,7 +1342,8 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, sizeof(R) == 4 ? 8 : 1) void k_rol
     __syncthreads();
     const R x_0 = (R)sv.x0[0], y_0 = (R)sv.x0[1], yaw_0 = (R)sv.x0[2];
     const int t_last = T - 1, lane_last = t_last >> 1, sub_last = t_last & 1;
-    // the control cost of the last step, u^T Sigma^-1 v (:124), as two wave-uniform coefficients of v
+    // the control cost of the last step, u^T Sigma^-1 v (:124), as two wave-uniform coefficients of v: control_cost<R,
+    // MODEL_DIFF>'s association, (u0 s0 + u1 s2) v0 + (u0 s1 + u1 s3) v1, with the brackets taken once per launch
     const R u_la = sh_u[2 * t_last], u_lb = sh_u[2 * t_last + 1];
     const R ca = wv::read_lane(u_la * P.sinv[0] + u_lb * P.sinv[2], 0), cb = wv::read_lane(u_la * P.sinv[1] + u_lb * P.sinv[3], 0);
     // this half-wave's private record (rho, eta, eta2 uniform within the half; w*: this lane's four columns)
@@ -1453,12 +1360,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, sizeof(R) == 4 ? 8 : 1) void k_rol
             // LDS per batch: eight registers fewer across the arithmetic below, which keeps the kernel at 64 VGPRs)
             float4 e = e_next;
             request(batch + 1, e_next);  // (past the last batch: a clamped re-read, cheaper than a branch around the loads)
-            if (PHILOX) {
-                unsigned r[4];
-                px::philox4x32_10((unsigned)(k + P.k_offset), (unsigned)l32, iter, (unsigned)(P.noise_stream + agent), P.seed_lo, P.seed_hi, r);
-                px::box_muller(r[0], r[1], P.chol, e.x, e.y);
-                px::box_muller(r[2], r[3], P.chol, e.z, e.w);
-            }
+            if (PHILOX) noise_pair(P, true, iter, agent, k, l32, true, e.x, e.y, e.z, e.w);  // (beyond the horizon: masked where it is used)
             *reinterpret_cast<float4 *>(&sh_raw[sidx][4 * l32]) = e;
             const VecT4<R> uu = *reinterpret_cast<const VecT4<R> *>(&sh_u[4 * l32]);  // u<step><channel>
             v00 = exploit ? uu.x + (R)e.x : (R)e.x; v01 = exploit ? uu.y + (R)e.y : (R)e.y;  // :116-119
@@ -1546,15 +1448,7 @@ __global__ __launch_bounds__(64 * DUAL_WAVES, sizeof(R) == 4 ? 8 : 1) void k_rol
         for (int q = 0; q < ROWS; ++q) acc += sh_acc[q][tid];
         out[4 + tid] = acc;
     }
-    if (tid == 64 * (DUAL_WAVES - 1)) {
-        R eta = 0, eta2 = 0, n_hit = 0;
-#pragma unroll
-        for (int q = 0; q < ROWS; ++q) { eta += sh_eta[q][0]; eta2 += sh_eta[q][1]; n_hit += sh_eta[q][2]; }
-        out[0] = rho;
-        out[1] = eta;
-        out[2] = eta2;
-        *reinterpret_cast<VecT4<R> *>(P.heads + 4 * slot) = VecT4<R>{rho, eta, eta2, n_hit};
-    }
+    if (tid == 64 * (DUAL_WAVES - 1)) record_head(P, out, slot, rho, sh_eta);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1612,13 +1506,7 @@ __global__ __launch_bounds__(256) void k_reduce(const KParams<R> P, R *__restric
         if (t < P.T) {
             for (int i = wid; i < nk; i += nw) {
                 float e0, e1;
-                if (P.use_philox) {
-                    px::sample(P.seed_lo, P.seed_hi, iter, (unsigned)(k0 + i + P.k_offset), t, P.chol, e0, e1, (unsigned)P.noise_stream);
-                } else {
-                    const float2 e = *reinterpret_cast<const float2 *>(eps_tensor(P, iter, 0) + ((size_t)(k0 + i) * P.T + t) * 2);
-                    e0 = e.x;
-                    e1 = e.y;
-                }
+                noise_at(P, (bool)P.use_philox, iter, 0, k0 + i, t, e0, e1);
                 const R w = sh_e[i];
                 a0 += w * (R)e0;
                 a1 += w * (R)e1;
@@ -2133,17 +2021,9 @@ __global__ __launch_bounds__(256) void k_viz(const KParams<R> P, const R *__rest
                 v1 = mf::clamp(u_upd[2 * tc + 1], P.umax1);
             } else {
                 float e0, e1;
-                if (P.use_philox) {
-                    px::sample(P.seed_lo, P.seed_hi, iter, (unsigned)(row + P.k_offset), tc, P.chol, e0, e1, (unsigned)P.noise_stream);
-                } else {
-                    const float2 e = *reinterpret_cast<const float2 *>(eps_tensor(P, iter, 0) + ((size_t)row * P.T + tc) * 2);
-                    e0 = e.x;
-                    e1 = e.y;
-                }
-                v0 = exploit ? u_before[2 * tc] + (R)e0 : (R)e0;
-                v1 = exploit ? u_before[2 * tc + 1] + (R)e1 : (R)e1;
-                v0 = mf::clamp(v0, P.umax0);  // the viz loop clamps even where the rollout did not (:158)
-                v1 = mf::clamp(v1, P.umax1);
+                noise_at(P, (bool)P.use_philox, iter, 0, row, tc, e0, e1);
+                // (the viz loop clamps even where the rollout did not, :158)
+                perturb_clamp(P, exploit, true, u_before[2 * tc], u_before[2 * tc + 1], e0, e1, v0, v1);
             }
         }
         R x, y, yaw, vel = 0;
@@ -2241,9 +2121,8 @@ __global__ __launch_bounds__(256) void k_eval(const KParams<R> P, int what, cons
             if (act) out[i] = hit ? R(1) : R(0);
         } else {  // `_compute_cost` / `_c`, `_terminal_cost` / `_phi` at the given waypoint index
             const bool term = what == EVAL_COST_TERMINAL;
-            R c = tracking_cost<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage, act ? idx[i] : 0, s[0], s[1],
-                                          s[2], s[3]);
-            if (hit) c += P.penalty;
+            const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
+                                                 P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit);
             if (act) out[i] = c;
         }
     }

@@ -20,8 +20,6 @@
 
 namespace mppi {
 
-template <typename R> struct alignas(4 * sizeof(R)) VecT4 { R x, y, z, w; };
-
 // Block records (written by k_rollout_fused / k_reduce / k_merge) use the INTERNAL layout
 // {rho, eta, eta2, pad, W[2T] padded to a 16-byte multiple}, so W is read as aligned 16-byte vectors;
 // the per-rank record of the split step uses the ABI layout {rho, eta, eta2, W[2T]} in doubles.

@@ -120,22 +120,10 @@ struct MlpLane {
 __device__ __forceinline__ void mlp_controls(const KParams<float> &P, unsigned iter, int k, int t, bool valid, bool exploit,
                                              float &u0, float &u1, float &v0, float &v1) {
     float e0 = 0.f, e1 = 0.f;
-    if (valid) {
-        if (P.use_philox) px::sample(P.seed_lo, P.seed_hi, iter, (unsigned)(k + P.k_offset), t, P.chol, e0, e1, (unsigned)P.noise_stream);
-        else {
-            const float2 e = *reinterpret_cast<const float2 *>(eps_tensor(P, iter, 0) + ((size_t)k * P.T + t) * 2);
-            e0 = e.x;
-            e1 = e.y;
-        }
-    }
+    if (valid) noise_at(P, (bool)P.use_philox, iter, 0, k, t, e0, e1);
     u0 = P.u[2 * t];
     u1 = P.u[2 * t + 1];
-    v0 = exploit ? u0 + e0 : e0;  // mppi_differential_drive.py:116-119
-    v1 = exploit ? u1 + e1 : e1;
-    if (P.clamp_rollout) {
-        v0 = mf::clamp(v0, P.umax0);
-        v1 = mf::clamp(v1, P.umax1);
-    }
+    perturb_clamp(P, exploit, (bool)P.clamp_rollout, u0, u1, e0, e1, v0, v1);
 }
 
 // Euler step of f + MLP (bullet_differential_drive_dnn.py:79-92)
@@ -173,17 +161,10 @@ __device__ __forceinline__ void mlp_controls_viz(const KParams<float> &P, const 
         v1 = V.u_upd[2 * tc + 1];
     } else if (sample_row) {
         float e0, e1;
-        if (P.use_philox) px::sample(P.seed_lo, P.seed_hi, V.iter, (unsigned)(k + P.k_offset), tc, P.chol, e0, e1, (unsigned)P.noise_stream);
-        else {
-            const float2 e = *reinterpret_cast<const float2 *>(eps_tensor(P, V.iter, 0) + ((size_t)k * P.T + tc) * 2);
-            e0 = e.x;
-            e1 = e.y;
-        }
-        v0 = exploit ? V.u_before[2 * tc] + e0 : e0;
-        v1 = exploit ? V.u_before[2 * tc + 1] + e1 : e1;
+        noise_at(P, (bool)P.use_philox, V.iter, 0, k, tc, e0, e1);
+        perturb(exploit, V.u_before[2 * tc], V.u_before[2 * tc + 1], e0, e1, v0, v1);
     }
-    v0 = mf::clamp(v0, P.umax0);
-    v1 = mf::clamp(v1, P.umax1);
+    clamp_controls(P, v0, v1);  // every row, the nominal one included (:148,:158)
 }
 
 // this call's waypoint index and costs behind the Euler step
@@ -209,10 +190,7 @@ __device__ __forceinline__ void mlp_advance(const KParams<float> &P, const ObsLa
     if (threads) L.p = idx;
     if (P.accumulate || t == P.T - 1) {
         const bool hit = collided<false>(P, L.x, L.y, L.yaw, obs);
-        float st_c = tracking_cost<float, MODEL_DIFF>(P, P.ws, P.wrap_stage, idx, L.x, L.y, L.yaw, 0.f);
-        if (hit) st_c += P.penalty;
-        const float ctrl = (u0 * P.sinv[0] + u1 * P.sinv[2]) * v0 + (u0 * P.sinv[1] + u1 * P.sinv[3]) * v1;
-        const float stage = st_c + P.gamma * ctrl;
+        const float stage = stage_cost<float, MODEL_DIFF>(P, (bool)P.wrap_stage, idx, L.x, L.y, L.yaw, 0.f, hit, u0, u1, v0, v1);
         L.S = P.accumulate ? L.S + stage : stage;
         if (t == P.T - 1) {
             int idx_term = idx;
@@ -220,9 +198,7 @@ __device__ __forceinline__ void mlp_advance(const KParams<float> &P, const ObsLa
                 L.p = nearest(L.p);
                 idx_term = L.p;
             }
-            float term = tracking_cost<float, MODEL_DIFF>(P, P.wt, P.wrap_term, idx_term, L.x, L.y, L.yaw, 0.f);
-            if (hit) term += P.penalty;
-            L.S += term;
+            L.S += terminal_cost<float, MODEL_DIFF>(P, (bool)P.wrap_term, idx_term, L.x, L.y, L.yaw, 0.f, hit);
         }
     }
 }
@@ -251,14 +227,7 @@ __device__ __forceinline__ void mlp_record(const KParams<float> &P, float *__res
     }
     for (int t = 0; t < P.T; ++t) {  // second pass over this tile's noise rows (regenerated / re-read)
         float e0 = 0.f, e1 = 0.f;
-        if (valid) {
-            if (P.use_philox) px::sample(P.seed_lo, P.seed_hi, iter, (unsigned)(k + P.k_offset), t, P.chol, e0, e1, (unsigned)P.noise_stream);
-            else {
-                const float2 ee = *reinterpret_cast<const float2 *>(eps_tensor(P, iter, 0) + ((size_t)k * P.T + t) * 2);
-                e0 = ee.x;
-                e1 = ee.y;
-            }
-        }
+        if (valid) noise_at(P, (bool)P.use_philox, iter, 0, k, t, e0, e1);
         const float w0 = wv::reduce<wv::OpAdd>(e * e0), w1 = wv::reduce<wv::OpAdd>(e * e1);
         if (lane == 0) { out[4 + 2 * t] = w0; out[4 + 2 * t + 1] = w1; }
     }

@@ -306,6 +306,23 @@ __global__ __launch_bounds__(256) void k_sample(unsigned seed_lo, unsigned seed_
 
 constexpr int SAMPLER_MAX = 1 << 20;
 
+// noise_pair against noise_at (one wave): lane l owns steps 2l and 2l+1 of sample k as in k_rollout_dual, idle when 2l >= T.
+// out[l][8] = {noise_pair's four values, noise_at(2l), noise_at(2l+1) -- 0 beyond the horizon}; the pair's second step starts
+// as NaN, so that a 0 there is the helper's
+__global__ __launch_bounds__(64) void k_noise_pair(const KParams<float> P, int philox, unsigned iter, int agent, int k, float *out) {
+    const int l = threadIdx.x;
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (2 * l < P.T) {
+        const bool a1 = 2 * l + 1 < P.T;
+        v[2] = NAN;
+        v[3] = NAN;
+        noise_pair(P, philox != 0, iter, agent, k, l, a1, v[0], v[1], v[2], v[3]);
+        noise_at(P, philox != 0, iter, agent, k, 2 * l, v[4], v[5]);
+        if (a1) noise_at(P, philox != 0, iter, agent, k, 2 * l + 1, v[6], v[7]);
+    }
+    for (int q = 0; q < 8; ++q) out[8 * l + q] = v[q];
+}
+
 // ------------------------------------------------------------------------------------------ look-back pieces
 // lb_scan: thread i owns positions NP i .. NP i + NP - 1 (one past n: idle, x = NaN); every block stages the 32 candidates in
 // sh_c as the rollout kernels do (thread j writes its candidate into its pair).  m[n]; bad[n]: the lane's flag (NP = 2: the OR
@@ -541,6 +558,25 @@ int prims_sample(unsigned seed_lo, unsigned seed_hi, unsigned iter, const unsign
     const Chol ch = {{chol[0], chol[1], chol[2]}};
     if (n) k_sample<<<(n + 255) / 256, 256>>>(seed_lo, seed_hi, iter, dk, dt, stream, ch, dout, n);
     return (int)finish(e, dout, (size_t)n * 2);
+}
+
+// row [T][2]: sample k's row of agent `agent`'s noise tensor [K = k + 1][T][2] (the tensor branch reads nothing else, so
+// only the row exists: P.eps points where the whole tensor would start); out [64][8], see k_noise_pair
+int prims_noise_pair(int philox, unsigned seed_lo, unsigned seed_hi, unsigned iter, int T, int k_offset, int noise_stream,
+                     int agent, int k, const float *chol, const float *row, float *out) {
+    if (T < 1 || T > 128 || k < 0 || agent < 0 || agent > 7) return (int)hipErrorInvalidValue;
+    Scope sc;
+    float *drow, *dout;
+    CK(sc.in(drow, row, (size_t)T * 2));
+    CK(sc.out(dout, 64 * 8));
+    KParams<float> P{};
+    P.K = k + 1; P.T = T; P.k_offset = k_offset; P.noise_stream = noise_stream;
+    P.seed_lo = seed_lo; P.seed_hi = seed_hi; P.n_agents = 8; P.eps_slots = 0;
+    for (int q = 0; q < 3; ++q) P.chol[q] = chol[q];
+    const size_t before = (((size_t)agent * P.K + (size_t)k) * T) * 2 * sizeof(float);  // bytes of the tensors before the row
+    P.eps = reinterpret_cast<const float *>(reinterpret_cast<uintptr_t>(drow) - before);
+    k_noise_pair<<<1, 64>>>(P, philox, iter, agent, k, dout);
+    return (int)finish(out, dout, 64 * 8);
 }
 
 // candidates [32][2], positions [n][2] (n a multiple of np, np 1 or 2: positions per lane) -> m[n], bad[n]

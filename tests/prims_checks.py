@@ -203,6 +203,17 @@ class Prims:
                    C.c_uint(stream), _p(chol), _p(o), C.c_int(k.size))
         return o
 
+    def noise_pair(self, philox_branch, seed, iteration, T, k_offset, noise_stream, agent, k, chol, row):
+        """one wave, lane l = steps 2l, 2l+1 of sample k -> (noise_pair [64][2][2], noise_at [64][2][2]); `row` [T][2] is
+        sample k's row of the agent's noise tensor (what the tensor branch reads)"""
+        chol, row = np.ascontiguousarray(chol, F32), np.ascontiguousarray(row, F32)
+        assert row.shape == (T, 2)
+        o = np.empty((64, 8), F32)
+        self._call("prims_noise_pair", C.c_int(int(philox_branch)), C.c_uint(seed & 0xFFFFFFFF), C.c_uint(seed >> 32),
+                   C.c_uint(iteration), C.c_int(T), C.c_int(k_offset), C.c_int(noise_stream), C.c_int(agent), C.c_int(k),
+                   _p(chol), _p(row), _p(o))
+        return o[:, :4].reshape(64, 2, 2), o[:, 4:].reshape(64, 2, 2)
+
 
 # ------------------------------------------------------------------------------------------ mathfn
     # ---- mppi_merge.h

@@ -410,3 +410,24 @@ def test_sample_at_the_counter_edges(P):
         got = P.sample(seed, it, np.full(ts.size, k, np.uint64).astype(U32), ts, stream, pc.chol_f32())
         want = philox.sample_epsilon(pc.SIGMA, seed, it, 1, 100, k_offset=k, stream=stream)[0, ts]
         np.testing.assert_allclose(got, want, rtol=0, atol=4e-6)
+
+
+@pytest.mark.parametrize("T", (1, 2, 7, 64))
+def test_noise_pair_equals_noise_at_bitwise(P, T):
+    """A lane's two steps from one Philox block, or two loads: the values noise_at gives at steps 2l and 2l+1, bit for bit, on
+    both branches; an odd horizon leaves the last lane's second step beyond it, where the pair comes back 0."""
+    seed, it = 0x1234567890ABCDEF, 5
+    row = np.random.default_rng(71).standard_normal((T, 2)).astype(F32)
+    steps = np.zeros((64, 2, 2), F32)  # the row as the lanes own it: [l][step][channel], 0 beyond the horizon
+    steps.reshape(128, 2)[:T] = row
+    for k in (0, 1, 2 ** 20 + 3):
+        for k_offset in (0, 5):
+            for agent in (0, 3):
+                for philox_branch in (True, False):
+                    pair, single = P.noise_pair(philox_branch, seed, it, T, k_offset, 0, agent, k, pc.chol_f32(), row)
+                    tag = (k, k_offset, agent, philox_branch)
+                    assert np.array_equal(pc.bits(pair), pc.bits(single)), tag
+                    assert not pair.reshape(128, 2)[T:].any(), tag
+                    assert pair.reshape(128, 2)[:T].all(), tag  # (a draw is never exactly 0, nor is the row)
+                    if not philox_branch:
+                        assert np.array_equal(pc.bits(pair), pc.bits(steps)), tag
