@@ -48,7 +48,10 @@ class _ControllerBase:
     _idx_name = "prev_way_point_idx"
     _ref_dtype = np.float64
 
-    def _finish_init(self, cfg, ref_path, obstacle_circles, precision, device, seed, process_group):
+    def _finish_init(self, cfg, ref_path, obstacle_circles, precision, device, seed, process_group, obstacle_velocities=None):
+        if obstacle_velocities is not None and obstacle_circles is None:
+            raise ValueError("obstacle_velocities needs obstacle_circles")
+        cfg.update(obstacle_motion=int(obstacle_velocities is not None))  # a create-time switch (mppi_config.obstacle_motion)
         cfg.update(precision=capi.PREC_F64 if precision in ("f64", "float64") else capi.PREC_F32,
                    device=int(device), seed=int(seed), collision_penalty=1.0e10, filter_window=10)
         self._pg = process_group
@@ -65,7 +68,11 @@ class _ControllerBase:
         self._ref_path = None
         self.ref_path = ref_path
         self._obstacles = None
-        if obstacle_circles is not None:
+        self._obstacle_vel = None
+        if obstacle_circles is not None and obstacle_velocities is not None:
+            self._obstacles = _arr(obstacle_circles).reshape(-1, 3)
+            self.obstacle_velocities = obstacle_velocities
+        elif obstacle_circles is not None:
             self.obstacle_circles = obstacle_circles
         self._u_host = np.zeros((self.T, self.dim_u))  # `u_prev`, mppi_differential_drive.py:82
         self._u_dev_copy = self._u_host.copy()
@@ -181,7 +188,23 @@ class _ControllerBase:
     @obstacle_circles.setter
     def obstacle_circles(self, value):
         self._obstacles = _arr(value).reshape(-1, 3)
+        self._obstacle_vel = None  # (circles assigned alone stand still)
         self._engine.set_obstacles(self._obstacles)
+
+    @property
+    def obstacle_velocities(self):
+        """[m, 2] = vx, vy of ``obstacle_circles`` in metres per second, or None while they stand still.  Assigning uploads
+        the circles as they stand now together with these velocities; the controller must have been built with
+        ``obstacle_velocities`` (else the library refuses: the switch is a create-time one)."""
+        return self._obstacle_vel
+
+    @obstacle_velocities.setter
+    def obstacle_velocities(self, value):
+        if self._obstacles is None:
+            raise ValueError("obstacle_velocities needs obstacle_circles")
+        vel = _arr(value).reshape(-1, 2)
+        self._engine.set_obstacles(self._obstacles, velocities=vel)
+        self._obstacle_vel = vel
 
     @property
     def u_prev(self):
@@ -433,7 +456,8 @@ class MPPIAlgorithms(_ControllerBase):
                  param_lambda, param_alpha, sigma, stage_cost_weight, terminal_cost_weight, obstacle_circles=None,
                  safety_margin_rate=None, visualize_optimal_traj=True, visualze_sampled_trajs=True,
                  visualize_sampled_traj=None, *, variant="numpy", precision="f32", device=0, seed=0,
-                 process_group=None, waypoint_mode=None, learned_dynamics=None, learned_scalers=None):
+                 process_group=None, waypoint_mode=None, learned_dynamics=None, learned_scalers=None,
+                 obstacle_velocities=None):
         if visualize_sampled_traj is not None:  # the torch variant's spelling (:63-64)
             visualze_sampled_trajs = visualize_sampled_traj
         self.delta_t = _num(delta_t)
@@ -484,7 +508,7 @@ class MPPIAlgorithms(_ControllerBase):
             safety_margin=0.0 if safety_margin_rate is None else self.safefy_margin_rate,
             vehicle_w=0.0, vehicle_l=0.0,
         )
-        self._finish_init(cfg, ref_path, obstacle_circles, precision, device, seed, process_group)
+        self._finish_init(cfg, ref_path, obstacle_circles, precision, device, seed, process_group, obstacle_velocities)
         self._learned = learned_dynamics is not None
         if self._learned:
             self._engine.set_mlp(learned_dynamics, learned_scalers)
@@ -532,7 +556,8 @@ class MPPIRacecarController(_ControllerBase):
                  param_exploration=0.01, param_lambda=50.0, param_alpha=1.0, sigma=((0.5, 0.0), (0.0, 0.1)),
                  stage_cost_weight=(50.0, 50.0, 1.0, 20.0), terminal_cost_weight=(50.0, 50.0, 1.0, 20.0),
                  obstacle_circles=None, collision_safety_margin_rat=1.5, visualize_optimal_traj=True,
-                 visualze_sampled_trajs=True, *, variant="numpy", precision="f32", device=0, seed=0, process_group=None):
+                 visualze_sampled_trajs=True, *, variant="numpy", precision="f32", device=0, seed=0, process_group=None,
+                 obstacle_velocities=None):
         if variant not in ("numpy", "cupy", "torch"):
             raise ValueError("variant must be 'numpy', 'cupy' or 'torch'")
         # mppi_race_car_cupy.py is the NumPy file with cp. for np.; mppi_race_car_torch.py differs in its moving
@@ -574,7 +599,7 @@ class MPPIRacecarController(_ControllerBase):
             raise_at_path_end=0 if self._has_obstacles else 1,  # mppi_race_car.py:63-65 vs _obstacle.py:73-74
             safety_margin=self.collision_safety_margin_rate, vehicle_w=self.vehicle_w, vehicle_l=self.vehicle_l,
         )
-        self._finish_init(cfg, ref_path, obstacle_circles, precision, device, seed, process_group)
+        self._finish_init(cfg, ref_path, obstacle_circles, precision, device, seed, process_group, obstacle_velocities)
 
     prev_waypoints_idx = property(_ControllerBase._get_idx, _ControllerBase._set_idx)
 

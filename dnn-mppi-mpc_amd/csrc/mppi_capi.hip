@@ -125,9 +125,11 @@ struct mppi_handle {
         DevBuf<void> d_ref, d_obs;
         int n_ref = 0, n_obs = 0;
         bool has_obs = false;  // (an own set of m = 0 circles has no buffer)
+        long long obs_iter0 = 0;  // moving obstacles: the agent's iteration counter when its own set was uploaded
     };
     std::vector<OwnScene> own;
     DevBuf<AgentScene> d_scenes;
+    long long obs_iter0 = 0;  // moving obstacles (mppi_config.obstacle_motion): the iteration counter when d_obs was uploaded
     DevBuf<int> d_pout;
     DevBuf<void> d_partials;        // block records in the handle's precision
     DevBuf<double> d_w, d_trace;
@@ -205,11 +207,11 @@ static double softmin_beta(const mppi_config &c) {
 static bool at_path_end(const mppi_handle *h, int idx) { return idx >= h->n_ref - 1; }  // (sequential index: one agent)
 // Agent a's scene: what it was given for itself, else the shared one.  n_obs counts only where the handle tests collisions.
 static AgentScene scene_of(const mppi_handle *h, int a) {
-    AgentScene sc = {h->d_ref, h->d_obs, h->n_ref, h->n_obs, {0, 0}};
+    AgentScene sc = {h->d_ref, h->d_obs, h->n_ref, h->n_obs, h->obs_iter0};
     if (a < (int)h->own.size()) {
         const mppi_handle::OwnScene &o = h->own[a];
         if (o.d_ref) sc.ref = o.d_ref, sc.n_ref = o.n_ref;
-        if (o.has_obs) sc.obs = o.d_obs, sc.n_obs = o.n_obs;
+        if (o.has_obs) sc.obs = o.d_obs, sc.n_obs = o.n_obs, sc.iter0 = o.obs_iter0;
     }
     if (h->cfg.obstacle_model == MPPI_OBSTACLE_NONE) sc.n_obs = 0;
     return sc;
@@ -231,7 +233,8 @@ static bool lookback_serves(const mppi_handle *h, int records) {
     const bool lb_layout = (h->layout & LAYOUT_KIND) == LAYOUT_FUSED || h->layout == LAYOUT_DUAL;  // (one pass per workgroup)
     return h->fused && lb_layout && c.T <= 64 && c.model == MPPI_MODEL_DIFFDRIVE && c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL &&
            !c.accumulate_stage_cost && (c.search_window == HYP_WINDOW || c.search_window == HYP_WINDOW_CUDA) && c.n_agents == 1 &&
-           records <= HYP_MAX_BLOCKS && !h->sw.no_hyp;
+           records <= HYP_MAX_BLOCKS && !h->sw.no_hyp &&
+           !c.obstacle_motion;  // (the look-back prices the last state with a collision test of its own: static circles only)
 }
 static bool index_can_move(const mppi_handle *h) { return h->hyp && !(h->idx_valid && h->n_ref > 0 && at_path_end(h, h->idx)); }
 template <typename R> static KParams<R> make_params(const mppi_handle *h, const float *eps);
@@ -280,6 +283,13 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         CREATE_FAIL(MPPI_ERR_UNSUPPORTED,
              "MPPI_WAYPOINT_PER_ROLLOUT restates the diff-drive files' index bookkeeping (mppi_differential_drive.py:228,:244); "
              "the race-car files search from the x0 call's index (MPPI_WAYPOINT_FROZEN)");
+    if (c.obstacle_motion != 0 && c.obstacle_motion != 1)
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: obstacle_motion %d is neither 0 (static) nor 1 (constant velocity)", c.obstacle_motion);
+    if (c.obstacle_motion && c.obstacle_model == MPPI_OBSTACLE_NONE)
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: obstacle_motion = 1 needs an obstacle model (MPPI_OBSTACLE_CIRCLE or _OUTLINE), got MPPI_OBSTACLE_NONE");
+    if (c.obstacle_motion && c.model == MPPI_MODEL_DIFFDRIVE_MLP)
+        CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "moving obstacles (obstacle_motion = 1) are served by the analytic models only: the "
+                                          "learned-dynamics rollout (MPPI_MODEL_DIFFDRIVE_MLP) tests static circles");
     if (c.filter_window < 1) c.filter_window = 10;
     if (c.search_window < 1) CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: search_window must be >= 1");
     // the reference's filters fail on short horizons (np.convolve 'same' returns max(M, N) samples)
@@ -303,7 +313,7 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
                      "several agents per learned-dynamics handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, at most 512 rollout "
                      "workgroups of 64 samples per agent (K <= 32768) and no sharding (got K = %d, K_global = %d)", c.K, c.K_global);
         } else if (c.waypoint_mode == MPPI_WAYPOINT_SEQUENTIAL || c.K_global != c.K || !fused_supported(c.T) ||
-                   merge_tree(fused_blocks(c.K, c.T, rollout_layout(sw, c.K, c.T, c.n_agents, kernel_model(c), c.precision == MPPI_PREC_F64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT)), true).group) {
+                   merge_tree(fused_blocks(c.K, c.T, rollout_layout(sw, c.K, c.T, c.n_agents, kernel_model(c), c.precision == MPPI_PREC_F64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT, false, c.obstacle_motion != 0)), true).group) {
             CREATE_FAIL(MPPI_ERR_UNSUPPORTED,
                  "several agents per handle need MPPI_WAYPOINT_FROZEN or _PER_ROLLOUT, T <= 128, at most 512 rollout workgroups "
                  "(K <= 8192) and no sharding");
@@ -345,7 +355,7 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     // (k_rollout_tri: the race car as the reference runs it -- frozen index, `S[k] +=` -- one agent, f32)
     const bool tri_ok = c.model == MPPI_MODEL_RACECAR && !h->f64 && c.n_agents == 1 && c.waypoint_mode == MPPI_WAYPOINT_FROZEN &&
                         c.accumulate_stage_cost;
-    h->layout = rollout_layout(sw, c.K, c.T, c.n_agents, kernel_model(c), h->f64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT, tri_ok);
+    h->layout = rollout_layout(sw, c.K, c.T, c.n_agents, kernel_model(c), h->f64, c.waypoint_mode == MPPI_WAYPOINT_PER_ROLLOUT, tri_ok, c.obstacle_motion != 0);
     h->B = c.n_agents;
     // records per agent of this handle's own rollout launch: its plan's count (every learned-dynamics kernel leaves the same)
     const int n_part = with_real(h, [&](auto r) { return front_plan<decltype(r)>(h, make_params<decltype(r)>(h, nullptr)).records; });
@@ -456,16 +466,30 @@ static int set_path(mppi_handle *h, const char *who, const double *path, int32_t
     return upload_real(h, *d_ref, packed.data(), packed.size());
 }
 
-// `self.obstacle_circles` into *d_obs / *n_obs, likewise
-static int set_circles(mppi_handle *h, const char *who, const double *xyr, int32_t m, DevBuf<void> *d_obs, int *n_obs) {
+// `self.obstacle_circles` into *d_obs / *n_obs, likewise.  A handle with obstacle_motion: the velocity rows {vx, vy, 0, 0}
+// follow the m circle rows (vel null: zeros) and *iter0 receives agent `clock_agent`'s iteration counter as of now.
+// Everything that can refuse the arguments stands before the first change.
+static int set_circles(mppi_handle *h, const char *who, const double *xyr, const double *vel, int32_t m, DevBuf<void> *d_obs,
+                       int *n_obs, long long *iter0, int clock_agent) {
     if (m > 0 && !xyr) FAIL(h, MPPI_ERR_BAD_ARG, "%s: null argument", who);
     if (m < 0) FAIL(h, MPPI_ERR_SHAPE, "%s: m < 0", who);
+    const bool moving = h->cfg.obstacle_motion != 0;
+    for (int i = 0; vel && i < 2 * m; ++i)
+        if (!std::isfinite(vel[i]))
+            FAIL(h, MPPI_ERR_BAD_ARG, "%s: the velocity of circle %d is not finite (a moving circle needs finite vx, vy)", who, i / 2);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
+    long long now = 0;
+    if (moving) HIPCHECK(h, hipMemcpy(&now, &h->d_st[clock_agent].iter, sizeof(now), hipMemcpyDeviceToHost));
     HIPCHECK(h, d_obs->reset());
     *n_obs = m;
+    *iter0 = now;
     if (m == 0) return MPPI_OK;
-    std::vector<double> packed((size_t)m * 4, 0.0);
+    std::vector<double> packed((size_t)m * (moving ? 8 : 4), 0.0);
+    for (int i = 0; moving && vel && i < m; ++i) {
+        packed[4 * (size_t)(m + i)] = vel[2 * i];
+        packed[4 * (size_t)(m + i) + 1] = vel[2 * i + 1];
+    }
     for (int i = 0; i < m; ++i) {
         const double r = xyr[3 * i + 2];
         // mppi_differential_drive_obs.py:304-311: (0.5*margin + r)^2 ; mppi_race_car_obstacle.py:272: r^2
@@ -474,7 +498,7 @@ static int set_circles(mppi_handle *h, const char *who, const double *xyr, int32
         packed[4 * i + 1] = xyr[3 * i + 1];
         packed[4 * i + 2] = thr * thr;
     }
-    HIPCHECK(h, d_obs->alloc(rsz(h) * 4 * m));
+    HIPCHECK(h, d_obs->alloc(rsz(h) * packed.size()));
     return upload_real(h, *d_obs, packed.data(), packed.size());
 }
 
@@ -488,15 +512,39 @@ extern "C" int mppi_set_ref_path(mppi_handle *h, const double *path, int32_t n, 
     return upload_scenes(h);
 }
 
-extern "C" int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m) {
-    if (!h) return MPPI_ERR_BAD_ARG;
-    if (int rc = set_circles(h, "mppi_set_obstacles", xyr, m, &h->d_obs, &h->n_obs)) return rc;
+static int set_shared_circles(mppi_handle *h, const char *who, const double *xyr, const double *vel, int32_t m) {
+    if (int rc = set_circles(h, who, xyr, vel, m, &h->d_obs, &h->n_obs, &h->obs_iter0, 0)) return rc;
     for (mppi_handle::OwnScene &o : h->own) {
         o.n_obs = 0;
         o.has_obs = false;
         HIPCHECK(h, o.d_obs.reset());
     }
     return upload_scenes(h);
+}
+static int set_agent_circles(mppi_handle *h, const char *who, int32_t agent, const double *xyr, const double *vel, int32_t m) {
+    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "%s: agent %d not in [0, %d)", who, agent, h->B);
+    if (h->B == 1) return set_shared_circles(h, who, xyr, vel, m);
+    mppi_handle::OwnScene &o = h->own[agent];
+    h->dev_loop_primed = false;
+    const int rc = set_circles(h, who, xyr, vel, m, &o.d_obs, &o.n_obs, &o.obs_iter0, agent);
+    if (rc == MPPI_OK || rc == MPPI_ERR_HIP) o.has_obs = rc == MPPI_OK;  // (refused arguments change nothing)
+    if (int rc2 = upload_scenes(h)) return rc ? rc : rc2;
+    return rc;
+}
+#define NEEDS_MOTION(h, who)                                                                                            \
+    if (!(h)->cfg.obstacle_motion)                                                                                      \
+        FAIL(h, MPPI_ERR_STATE, "%s: the handle was created with obstacle_motion = 0 (static circles: mppi_set_obstacles); " \
+                                "moving circles need mppi_config.obstacle_motion = 1 at mppi_create", who)
+
+extern "C" int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    return set_shared_circles(h, "mppi_set_obstacles", xyr, nullptr, m);
+}
+extern "C" int mppi_set_obstacles_moving(mppi_handle *h, const double *xyr, const double *vel, int32_t m) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    NEEDS_MOTION(h, "mppi_set_obstacles_moving");
+    if (m > 0 && !vel) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_obstacles_moving: null argument");
+    return set_shared_circles(h, "mppi_set_obstacles_moving", xyr, vel, m);
 }
 
 extern "C" int mppi_set_agent_ref_path(mppi_handle *h, int32_t agent, const double *path, int32_t n, int32_t ncols) {
@@ -513,14 +561,13 @@ extern "C" int mppi_set_agent_ref_path(mppi_handle *h, int32_t agent, const doub
 
 extern "C" int mppi_set_agent_obstacles(mppi_handle *h, int32_t agent, const double *xyr, int32_t m) {
     if (!h) return MPPI_ERR_BAD_ARG;
-    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_agent_obstacles: agent %d not in [0, %d)", agent, h->B);
-    if (h->B == 1) return mppi_set_obstacles(h, xyr, m);
-    mppi_handle::OwnScene &o = h->own[agent];
-    h->dev_loop_primed = false;
-    const int rc = set_circles(h, "mppi_set_agent_obstacles", xyr, m, &o.d_obs, &o.n_obs);
-    if (rc == MPPI_OK || rc == MPPI_ERR_HIP) o.has_obs = rc == MPPI_OK;  // (refused arguments change nothing)
-    if (int rc2 = upload_scenes(h)) return rc ? rc : rc2;
-    return rc;
+    return set_agent_circles(h, "mppi_set_agent_obstacles", agent, xyr, nullptr, m);
+}
+extern "C" int mppi_set_agent_obstacles_moving(mppi_handle *h, int32_t agent, const double *xyr, const double *vel, int32_t m) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    NEEDS_MOTION(h, "mppi_set_agent_obstacles_moving");
+    if (m > 0 && !vel) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_agent_obstacles_moving: null argument");
+    return set_agent_circles(h, "mppi_set_agent_obstacles_moving", agent, xyr, vel, m);
 }
 
 extern "C" int mppi_get_agent_status(mppi_handle *h, int32_t *idx_out, int32_t *path_end_out) {
@@ -828,9 +875,20 @@ extern "C" int mppi_set_iteration(mppi_handle *h, int64_t iteration) {
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
     long long it = iteration;
-    for (int a = 0; a < h->B; ++a)
+    for (int a = 0; a < h->B; ++a) {
+        if (h->cfg.obstacle_motion) {  // the counter replays noise, it does not move obstacles: their clocks' origins follow it
+            long long old = 0;
+            HIPCHECK(h, hipMemcpy(&old, &h->d_st[a].iter, sizeof(old), hipMemcpyDeviceToHost));
+            if (a == 0) h->obs_iter0 += it - old;
+            if (a < (int)h->own.size()) h->own[a].obs_iter0 += it - old;
+        }
         HIPCHECK(h, hipMemcpy(&h->d_st[a].iter, &it, sizeof(it), hipMemcpyHostToDevice));
+    }
     h->iter = it;
+    if (h->cfg.obstacle_motion) {
+        h->dev_loop_primed = false;
+        return upload_scenes(h);
+    }
     return MPPI_OK;
 }
 
@@ -924,6 +982,8 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.chol[2] = (float)l11;
     P.ref = (const R *)sc0.ref;
     P.obs = (const R *)sc0.obs;
+    P.obs_motion = c.obstacle_motion;
+    P.iter0 = sc0.iter0;
     P.scenes = h->d_scenes;
     P.u = (const R *)h->d_u.get();
     P.eps = noise;
@@ -2032,14 +2092,20 @@ static void eval_transition_mlp(mppi_handle *, const KParams<double> &, const vo
 
 template <typename R>
 static int eval_impl(mppi_handle *h, int what, const double *x, const double *v, int n, int32_t *prev_idx, int update,
-                     double *out, int32_t *idx_out) {
+                     double *out, int32_t *idx_out, const int32_t *steps = nullptr) {
     const KParams<R> P = make_params<R>(h, nullptr);
     const int nx = h->nx;
     const bool need_x = what != EVAL_CLAMP, need_v = what == EVAL_TRANSITION || what == EVAL_CLAMP;
     const bool need_idx = what == EVAL_COST_STAGE || what == EVAL_COST_TERMINAL || what < 0;  // what < 0: index only
     const int n_out = what == EVAL_TRANSITION ? nx : what == EVAL_CLAMP ? 2 : 1;
     DevBuf<R> dx, dv, dout;
-    DevBuf<int> di, dp;
+    DevBuf<int> di, dp, ds;
+    // moving obstacles: the collision test (alone or inside a cost) takes the kernel that knows the clock; steps null: "now"
+    const bool at = h->cfg.obstacle_motion && (what == EVAL_COLLIDED || what == EVAL_COST_STAGE || what == EVAL_COST_TERMINAL);
+    if (at && steps) {
+        HIPCHECK(h, ds.alloc(sizeof(int) * (size_t)n));
+        HIPCHECK(h, hipMemcpy(ds, steps, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    }
     if (need_x) {
         HIPCHECK(h, dx.alloc(sizeof(R) * (size_t)n * nx));
         if (int rc = upload_real(h, dx, x, (size_t)n * nx)) return rc;
@@ -2059,6 +2125,8 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
         HIPCHECK(h, dout.alloc(sizeof(R) * (size_t)n * n_out));
         if (what == EVAL_TRANSITION && h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP)  // x + dt (f + MLP([x, v])), fp32 handles only
             eval_transition_mlp(h, P, dx, dv, n, dout);
+        else if (at)
+            launch_eval_at<R>(P, what, dx, di, ds, n, dout, nullptr);
         else
             launch_eval<R>(P, what, dx, dv, di, n, dout, nullptr);
     }
@@ -2076,14 +2144,14 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
 }
 
 static int eval_entry(mppi_handle *h, const char *who, int what, const double *x, const double *v, int n, int32_t *prev_idx,
-                      int update, double *out, int32_t *idx_out) {
+                      int update, double *out, int32_t *idx_out, const int32_t *steps = nullptr) {
     int rc = check_ready(h, who);
     if (rc) return rc;
     if (n < 1 || (what >= 0 && !out)) FAIL(h, MPPI_ERR_BAD_ARG, "%s: bad argument", who);
     if ((what != EVAL_CLAMP && !x) || ((what == EVAL_TRANSITION || what == EVAL_CLAMP) && !v))
         FAIL(h, MPPI_ERR_BAD_ARG, "%s: null input", who);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
-    return with_real(h, [&](auto r) { return eval_impl<decltype(r)>(h, what, x, v, n, prev_idx, update, out, idx_out); });
+    return with_real(h, [&](auto r) { return eval_impl<decltype(r)>(h, what, x, v, n, prev_idx, update, out, idx_out, steps); });
 }
 
 extern "C" int mppi_eval_state_transition(mppi_handle *h, const double *x, const double *v, int32_t n, double *x_next) {
@@ -2094,6 +2162,12 @@ extern "C" int mppi_eval_clamp(mppi_handle *h, const double *v, int32_t n, doubl
 }
 extern "C" int mppi_eval_is_collided(mppi_handle *h, const double *x, int32_t n, double *out) {
     return eval_entry(h, "mppi_eval_is_collided", EVAL_COLLIDED, x, nullptr, n, nullptr, 0, out, nullptr);
+}
+extern "C" int mppi_eval_is_collided_at(mppi_handle *h, const double *x, int32_t n, const int32_t *steps, double *out) {
+    if (h && !steps) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_is_collided_at: steps is null");
+    for (int i = 0; h && steps && i < n; ++i)
+        if (steps[i] < 0) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_is_collided_at: steps[%d] = %d is negative (steps count ahead of the clock)", i, steps[i]);
+    return eval_entry(h, "mppi_eval_is_collided_at", EVAL_COLLIDED, x, nullptr, n, nullptr, 0, out, nullptr, steps);
 }
 extern "C" int mppi_eval_nearest_waypoint(mppi_handle *h, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
                                           int32_t *idx_out) {

@@ -166,22 +166,50 @@ template <typename R> __device__ __forceinline__ ObsLanes<R> load_obstacles(cons
     return o;
 }
 
+// Moving obstacles (mppi_config.obstacle_motion, KParams::obs_motion): the table's twin with circle m's velocity on lane m as
+// well.  The velocity rows {vx, vy, 0, 0} stand behind the n_obs circle rows of the same buffer.
+template <typename R> struct ObsLanesMoving { R x, y, r2, vx, vy; };
+
+template <typename R> __device__ __forceinline__ ObsLanesMoving<R> load_obstacles_moving(const KParams<R> &P, int lane) {
+    ObsLanesMoving<R> o{R(0), R(0), R(0), R(0), R(0)};
+    if (P.obstacle_model != OBS_NONE && lane < P.n_obs) {
+        const R *q = P.obs + 4 * lane, *w = P.obs + 4 * (P.n_obs + lane);
+        o.x = q[0]; o.y = q[1]; o.r2 = q[2];
+        o.vx = w[0]; o.vy = w[1];
+    }
+    return o;
+}
+__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// The obstacle clock: control steps since the set was uploaded (n = DevState::iter - iter0) plus the j rollout steps ahead a
+// state lies, as the time tau = dt (n + j) in the handle's precision -- the integer converted exactly, one product.  A circle's
+// centre at that state is then one fma per coordinate: c + v tau (zero velocities give c back exactly).
+__device__ __forceinline__ int obstacle_clock(long long iter, long long iter0) { return (int)(iter - iter0); }
+template <typename R> __device__ __forceinline__ R obstacle_time(const KParams<R> &P, int n_plus_j) { return P.dt * (R)n_plus_j; }
+
 // WIDE: the 8 outline points stay in registers and each circle is read once (the race-car kernels); otherwise the
 // points are visited one after the other, which keeps the diff-drive kernels at their register count
 // (`have_sc`: the caller already holds sin/cos of this yaw)
-template <bool WIDE, typename R>
-__device__ __forceinline__ bool collided(const KParams<R> &P, R x, R y, R yaw, const ObsLanes<R> &tab, bool have_sc = false,
-                                         R sn_in = R(0), R cs_in = R(1)) {
+// MOVING: `tab` carries velocities and every centre is taken at this lane's time `tau` (obstacle_time); false compiles to the
+// static test.
+template <bool WIDE, bool MOVING = false, typename R, typename TAB>
+__device__ __forceinline__ bool collided(const KParams<R> &P, R x, R y, R yaw, const TAB &tab, bool have_sc = false,
+                                         R sn_in = R(0), R cs_in = R(1), R tau = R(0)) {
     if (P.obstacle_model == OBS_NONE) return false;
     bool hit = false;
     const int n_reg = P.n_obs < 64 ? P.n_obs : 64;
+    // circle m's centre: from lane m of the table (m < 64) or from its rows in memory
+    auto lane_x = [&](int m) { R c = wv::read_lane(tab.x, m); if constexpr (MOVING) c = fma_(wv::read_lane(tab.vx, m), tau, c); return c; };
+    auto lane_y = [&](int m) { R c = wv::read_lane(tab.y, m); if constexpr (MOVING) c = fma_(wv::read_lane(tab.vy, m), tau, c); return c; };
+    auto mem_x = [&](int m) { R c = P.obs[4 * m]; if constexpr (MOVING) c = fma_(P.obs[4 * (P.n_obs + m)], tau, c); return c; };
+    auto mem_y = [&](int m) { R c = P.obs[4 * m + 1]; if constexpr (MOVING) c = fma_(P.obs[4 * (P.n_obs + m) + 1], tau, c); return c; };
     if (P.obstacle_model == OBS_CIRCLE) {
         for (int m = 0; m < n_reg; ++m) {
-            const R dx = x - wv::read_lane(tab.x, m), dy = y - wv::read_lane(tab.y, m);
+            const R dx = x - lane_x(m), dy = y - lane_y(m);
             hit |= dx * dx + dy * dy < wv::read_lane(tab.r2, m);
         }
         for (int m = 64; m < P.n_obs; ++m) {
-            const R dx = x - P.obs[4 * m], dy = y - P.obs[4 * m + 1];
+            const R dx = x - mem_x(m), dy = y - mem_y(m);
             hit |= dx * dx + dy * dy < P.obs[4 * m + 2];
         }
         return hit;
@@ -204,18 +232,18 @@ __device__ __forceinline__ bool collided(const KParams<R> &P, R x, R y, R yaw, c
             const R ex2 = ex * ex, ey2 = ey * ey;
             hit |= fmin(fmin(ex2 + by * by, ex2 + ey2), bx * bx + ey2) < r2;
         };
-        for (int m = 0; m < n_reg; ++m) circle(wv::read_lane(tab.x, m), wv::read_lane(tab.y, m), wv::read_lane(tab.r2, m));
-        for (int m = 64; m < P.n_obs; ++m) circle(P.obs[4 * m], P.obs[4 * m + 1], P.obs[4 * m + 2]);
+        for (int m = 0; m < n_reg; ++m) circle(lane_x(m), lane_y(m), wv::read_lane(tab.r2, m));
+        for (int m = 64; m < P.n_obs; ++m) circle(mem_x(m), mem_y(m), P.obs[4 * m + 2]);
     } else {
         for (int q = 0; q < 8; ++q) {
             const R px = P.shape_x[q] * cs - P.shape_y[q] * sn + x;
             const R py = P.shape_x[q] * sn + P.shape_y[q] * cs + y;
             for (int m = 0; m < n_reg; ++m) {
-                const R dx = px - wv::read_lane(tab.x, m), dy = py - wv::read_lane(tab.y, m);
+                const R dx = px - lane_x(m), dy = py - lane_y(m);
                 hit |= dx * dx + dy * dy < wv::read_lane(tab.r2, m);
             }
             for (int m = 64; m < P.n_obs; ++m) {
-                const R dx = px - P.obs[4 * m], dy = py - P.obs[4 * m + 1];
+                const R dx = px - mem_x(m), dy = py - mem_y(m);
                 hit |= dx * dx + dy * dy < P.obs[4 * m + 2];
             }
         }

@@ -117,9 +117,9 @@ inline MergeTree merge_tree(int n, bool finalize_reads) {
 struct alignas(32) AgentScene {
     const void *ref, *obs;  // [n_ref][4], [n_obs][4] as KParams::ref / obs
     int n_ref, n_obs;       // (n_obs: 0 for a handle without an obstacle model)
-    int pad[2];
+    long long iter0;        // moving obstacles: DevState::iter when this agent's set was uploaded (KParams::iter0)
 };
-static_assert(sizeof(AgentScene) == 32, "AgentScene layout");
+static_assert(sizeof(AgentScene) == 32 && offsetof(AgentScene, iter0) == 24, "AgentScene layout");
 
 template <typename R> struct KParams {
     int K, T, k_offset, noise_stream;  // noise_stream: fourth Philox counter word (of agent 0) -- kept in the first
@@ -135,11 +135,12 @@ template <typename R> struct KParams {
     R shape_x[9], shape_y[9];
     float chol[3];
     const R *ref;      // [n_ref][4]  x, y, yaw, v
-    const R *obs;      // [n_obs][4]  x, y, threshold^2, 0
+    const R *obs;      // [n_obs][4]  x, y, threshold^2, 0; obs_motion: followed by [n_obs][4]  vx, vy, 0, 0 (row n_obs + m: circle m)
     const R *u;        // [T][2] nominal controls
     const float *eps;  // [K][T][2] or nullptr (Philox); with eps_slots > 0: a ring [eps_slots][n_agents][K][T][2]
     int eps_slots;     // 0: `eps` is this call's tensor; 2^n: iteration i reads slot i mod eps_slots (mppi_set_noise_ring)
-    int pad_eps;
+    int obs_motion;    // mppi_config.obstacle_motion: the circles carry velocities and the moving instantiations serve (this
+                       // word was padding: the layout stays)
     R *S;              // [K]
     int *pout;         // [K] waypoint index after sample k (sequential mode)
     DevState *st;
@@ -165,12 +166,16 @@ template <typename R> struct KParams {
     // Last, so that the first kernel-argument fetch keeps its layout; padded to 32 bytes, so that the arguments behind the
     // struct keep their alignment and the compiler merges their loads as it did (the single-agent kernels' code is unchanged).
     const AgentScene *scenes;
-    long long pad_scenes[3];
+    // moving obstacles: the value of DevState::iter when the set (agent 0's here, every agent's in the table) was uploaded.  A
+    // rollout step j steps ahead tests against c + v dt (iter - iter0 + j).  (It took a padding word: the layout stays.)
+    long long iter0;
+    long long pad_scenes[2];
 };
 // (lb_timeout took the place of a padding word: the layout the kernels' argument loads were tuned for stays as it was)
 static_assert(sizeof(KParams<float>) == 424 && sizeof(KParams<double>) == 576, "KParams layout");
 static_assert(offsetof(KParams<float>, hyp) == 376 && offsetof(KParams<double>, hyp) == 528, "KParams layout");
 static_assert(offsetof(KParams<float>, scenes) == 392 && offsetof(KParams<double>, scenes) == 544, "KParams layout");
+static_assert(offsetof(KParams<float>, iter0) == 400 && offsetof(KParams<double>, iter0) == 552, "KParams layout");
 
 struct FinalizeParams {
     int T, K, n_part, pad2;
@@ -340,7 +345,9 @@ inline void launch_plan(const KernelLaunch &p, void **args, hipStream_t s) {
 enum { LAYOUT_FUSED = 0, LAYOUT_DUAL = 1, LAYOUT_PAIR = 2, LAYOUT_TRI = 3, LAYOUT_KIND = 3, LAYOUT_TWICE = 4 };  // (KIND: mask)
 // n_agents: problems batched in one launch; tri_ok: the handle is what k_rollout_tri serves (race car, f32, frozen index,
 // `S[k] +=`, one agent) -- it takes horizons of 65 .. 96 steps then
-int rollout_layout(const Switches &sw, int K, int T, int n_agents, int model, bool f64, bool per_rollout = false, bool tri_ok = false);
+// moving: mppi_config.obstacle_motion -- the one-sample-per-wave layout for every K (the only one with moving instantiations)
+int rollout_layout(const Switches &sw, int K, int T, int n_agents, int model, bool f64, bool per_rollout = false, bool tri_ok = false,
+                   bool moving = false);
 int fused_blocks(int K, int T, int layout);  // workgroups = block records of a launch of the layout's own kernels
 // the most records per agent any fused launch of this layout can leave (the streaming kernel, which serves the two-samples-
 // per-wave layout where it can, leaves up to one per batch): what a handle sizes its record buffers by
@@ -364,6 +371,10 @@ void launch_eval_index(const KParams<R> &P, const R *xy, int stride, int n, int 
                        hipStream_t s);
 template <typename R>
 void launch_eval(const KParams<R> &P, int what, const R *x, const R *v, const int *idx, int n, R *out, hipStream_t s);
+// the same for a handle with moving obstacles: pose i is tested against the circles steps[i] rollout steps ahead of the current
+// clock (steps null: 0).  what: EVAL_COST_STAGE, EVAL_COST_TERMINAL or EVAL_COLLIDED
+template <typename R>
+void launch_eval_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s);
 void launch_eval_weights(const double *S, int n, double beta, double *w, hipStream_t s);
 template <typename R> void launch_set_state_dev(const KParams<R> &P, const double *x_dev, int nx, hipStream_t s);

@@ -87,7 +87,24 @@ __global__ __launch_bounds__(64) void k_set_state(const R *ref, int n_ref, int w
 // PLAIN: in addition the noise is drawn in the kernel, the rollout clamps its controls and no cost wraps the yaw -- the
 // reference's diff-drive NumPy controller as bench.py runs it; the four run-time switches become constants (0.19 us per
 // iteration at config 2, A/B on one box).  Anything else takes the general instantiation.
-template <typename R, int MODEL, bool OBS = true, bool PLAIN = false> struct Rollout {
+// MOVING (mppi_config.obstacle_motion): the obstacle table carries velocities and a state j rollout steps ahead is tested
+// against the circles at time dt (clock + j) -- lane l of chunk ch owns step j = 64 ch + l + 1 (obstacle_time, mppi_device.h).
+// What a MOVING rollout carries beside the static table: circle m's velocity on lane m and the obstacle clock (control steps
+// since the set was uploaded).  The static form is empty, so that the static instantiations keep their code.
+template <typename R, bool MOVING> struct RolloutMotion {
+    RolloutMotion() = default;
+    __device__ __forceinline__ RolloutMotion(const KParams<R> &, const DevState &, int) {}
+};
+template <typename R> struct RolloutMotion<R, true> {
+    R vx, vy;
+    int clock;
+    __device__ __forceinline__ RolloutMotion(const KParams<R> &P, const DevState &sv, int lane) {
+        const ObsLanesMoving<R> t = load_obstacles_moving(P, lane);
+        vx = t.vx; vy = t.vy;
+        clock = obstacle_clock(sv.iter, P.iter0);
+    }
+};
+template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVING = false> struct Rollout : RolloutMotion<R, MOVING> {
     __device__ __forceinline__ bool use_philox() const { return PLAIN || P.use_philox; }
     __device__ __forceinline__ bool clamp_rollout() const { return PLAIN || P.clamp_rollout; }
     __device__ __forceinline__ bool wrap_stage() const { return !PLAIN && P.wrap_stage; }
@@ -114,6 +131,24 @@ template <typename R, int MODEL, bool OBS = true, bool PLAIN = false> struct Rol
           exploit((k_ + P_.k_offset) < P_.n_exploit), cx((R)sv.x0[0]), cy((R)sv.x0[1]), cyaw((R)sv.x0[2]),
           cvel(MODEL == MODEL_RACE ? (R)sv.x0[3] : R(0)), p(sv.c), slow(false), s_acc(0), s_last(0),
           n_chunk((P_.T + 63) >> 6), lane_last((P_.T - 1) & 63), win(win_), obs(obs_), agent(agent_) {}
+    // the same for a MOVING rollout
+    __device__ __forceinline__ Rollout(const KParams<R> &P_, const DevState &sv, int k_, int lane_, const RefPair<R> *win_,
+                                       const ObsLanes<R> &obs_, int agent_, const RolloutMotion<R, MOVING> &mv)
+        : RolloutMotion<R, MOVING>(mv), P(P_), k(k_), lane(lane_), c(sv.c), iter((unsigned)sv.iter),
+          exploit((k_ + P_.k_offset) < P_.n_exploit), cx((R)sv.x0[0]), cy((R)sv.x0[1]), cyaw((R)sv.x0[2]),
+          cvel(MODEL == MODEL_RACE ? (R)sv.x0[3] : R(0)), p(sv.c), slow(false), s_acc(0), s_last(0),
+          n_chunk((P_.T + 63) >> 6), lane_last((P_.T - 1) & 63), win(win_), obs(obs_), agent(agent_) {}
+
+    // collision test of this lane's state after step 64 ch + lane.  MOVING: that state lies j = 64 ch + lane + 1 steps ahead;
+    // the terminal call prices the same state, and only lane_last's terminal value is read: j = T there
+    __device__ __forceinline__ bool collided_at(int ch, R x, R y, R yaw) const {
+        if constexpr (MOVING) {
+            const ObsLanesMoving<R> tab{obs.x, obs.y, obs.r2, this->vx, this->vy};
+            return collided<MODEL == MODEL_RACE, true>(P, x, y, yaw, tab, false, R(0), R(1), obstacle_time(P, this->clock + 64 * ch + lane + 1));
+        } else {
+            return collided<MODEL == MODEL_RACE>(P, x, y, yaw, obs);
+        }
+    }
 
     // this lane's noise for step t of sample k (S1, or the caller's tensor)
     __device__ __forceinline__ void load_eps(int ch, float &e0, float &e1) const {
@@ -272,7 +307,7 @@ template <typename R, int MODEL, bool OBS = true, bool PLAIN = false> struct Rol
         // ---- stage cost of every call (only the last one survives when !accumulate) ------
         const bool last_chunk = ch == n_chunk - 1;
         if (P.accumulate || last_chunk) {
-            const bool hit = OBS ? collided<MODEL == MODEL_RACE>(P, x, y, yaw, obs) : false;
+            const bool hit = OBS ? collided_at(ch, x, y, yaw) : false;
             const R stage = stage_cost<R, MODEL>(P, wrap_stage(), my_idx, x, y, yaw, vel, hit, u0, u1, v0, v1);
             if (P.accumulate) {
                 if (sizeof(R) == 4) {
@@ -336,6 +371,28 @@ __global__ __launch_bounds__(256) void k_rollout(const DevState *st_pre, const K
     __syncthreads();
     if (k >= P.K || k < sv.k_start) return;
     Rollout<R, MODEL> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs);
+    for (int ch = 0; ch < r.n_chunk; ++ch) {
+        float e0, e1;
+        r.chunk(ch, e0, e1);
+    }
+    r.finish();
+}
+// The same with moving obstacles (mppi_config.obstacle_motion) -- a kernel of its own name and text, so that k_rollout's
+// symbols and code stay what they were.  Chunk ch's lanes continue at step 64 ch + 1 (Rollout::collided_at).
+template <typename R, int MODEL>
+__global__ __launch_bounds__(256) void k_rollout_moving(const DevState *st_pre, const KParams<R> P) {
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // wave-uniform
+    const DevState sv = load_state(P, st_pre);
+    __shared__ RefPair<R> sh_win[WINDOW_LDS_MAX / 2];
+    const ObsLanes<R> obs = load_obstacles(P, lane);
+    const RolloutMotion<R, true> mv(P, sv, lane);
+    const int wlen0 = window_len<R>(P.window, P.n_ref, sv.c);
+    const bool use_win = wlen0 <= WINDOW_LDS_MAX;
+    if (use_win) stage_window(sh_win, P.ref, sv.c, wlen0, (int)threadIdx.x, (int)blockDim.x);
+    __syncthreads();
+    if (k >= P.K || k < sv.k_start) return;
+    Rollout<R, MODEL, true, false, true> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, 0, mv);
     for (int ch = 0; ch < r.n_chunk; ++ch) {
         float e0, e1;
         r.chunk(ch, e0, e1);
@@ -525,16 +582,18 @@ __device__ __forceinline__ void per_rollout_thread(const KParams<R> &P, int c, c
 
 // MULTI: several agents per launch, one row of workgroups (blockIdx.y) each; a single agent compiles to the
 // offset-free code (the offsets cost config 2 half a microsecond per iteration when they were unconditional)
-// SPEC: 0 general, 1 no obstacles, 2 no obstacles + the PLAIN switches (see Rollout)
+// SPEC: 0 general, 1 no obstacles, 2 no obstacles + the PLAIN switches (see Rollout), 3 general with moving obstacles
 // HYPK: the instantiation that can resolve the sequential index in one launch (fused_lookback).  A separate instantiation,
 // picked by the host while the waypoint index can still move (KParams::hyp): carrying that code costs the lean kernel
 // 0.17 us per launch in registers and LDS (A/B on one box), and at the end of the path nothing moves any more.
 template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK = false>
 __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevState *st_pre, KParams<R> P,
                                                                     R *__restrict__ partials) {
-    constexpr bool OBS = SPEC == 0, PLAIN = SPEC == 2;
+    constexpr bool OBS = SPEC == 0 || SPEC == 3, PLAIN = SPEC == 2, MOVING = SPEC == 3;
+    static_assert(!(HYPK && MOVING), "the look-back prices the last state with a collision test of its own: static obstacles only");
     const int agent = MULTI ? (int)blockIdx.y : 0;
     if constexpr (MULTI) agent_scene(P, P.scenes, agent);  // (the agent's view of P: its own path and obstacles, see AgentScene)
+    if constexpr (MULTI && MOVING) P.iter0 = P.scenes[agent].iter0;  // (and the clock its own set was uploaded at)
     __shared__ R sh_S[FUSED_WAVES];
     __shared__ R sh_e[FUSED_WAVES];
     __shared__ R sh_acc[FUSED_WAVES][128 * NCH];
@@ -552,6 +611,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
     const bool lookback = HYPK && sv.round == 0 && wlen0 > 1;
     __shared__ RefPair<R> sh_win[WINDOW_LDS_MAX / 2];
     const ObsLanes<R> obs = OBS ? load_obstacles(P, lane) : ObsLanes<R>{R(0), R(0), R(0)};
+    const RolloutMotion<R, MOVING> mv(P, sv, lane);  // (MOVING: the velocities and the clock; else empty)
     // Both waypoint modes search the window at c first.  A window of ONE candidate (the robot holds the end of the
     // path) leaves nothing to search or to move: no staging and no barrier behind its loads then (0.7 us per launch
     // at config 2).
@@ -572,7 +632,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
     const bool pr_fast = !PLAIN && NCH == 1 && P.per_rollout && wlen0 > 1 && P.n_ref < 32768;
     R S_all = R(INFINITY);  // (look-back: every wave holds all sixteen costs, sample l & 15 on lane l)
     if (lookback) {
-        if constexpr (HYPK && MODEL == MODEL_DIFF && NCH == 1) S_all = fused_lookback<R, OBS, PLAIN>(P, sv, k, valid, e0[0], e1[0]);
+        if constexpr (HYPK && MODEL == MODEL_DIFF && NCH == 1 && !MOVING) S_all = fused_lookback<R, OBS, PLAIN>(P, sv, k, valid, e0[0], e1[0]);
         S_k = wv::read_lane(S_all, wid);
     } else if (pr_fast) {
         __shared__ R sh_px[FUSED_WAVES][64], sh_py[FUSED_WAVES][64];
@@ -581,8 +641,8 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
         const bool ref_lds = P.n_ref <= PR_REF_LDS;
         if (ref_lds)
             for (int i = threadIdx.x; i < P.n_ref; i += blockDim.x) { sh_pref[2 * i] = P.ref[4 * i]; sh_pref[2 * i + 1] = P.ref[4 * i + 1]; }
-        Rollout<R, MODEL, OBS, PLAIN> r(P, sv, k, lane, nullptr, obs, agent);
-        typename Rollout<R, MODEL, OBS, PLAIN>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
+        Rollout<R, MODEL, OBS, PLAIN, MOVING> r(P, sv, k, lane, nullptr, obs, agent, mv);
+        typename Rollout<R, MODEL, OBS, PLAIN, MOVING>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
         if (valid) sp = r.dynamics(0, e0[0], e1[0]);
         sh_px[wid][lane] = sp.x;
         sh_py[wid][lane] = sp.y;
@@ -594,7 +654,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
             S_k = r.finish(false);
         }
     } else if (valid) {
-        Rollout<R, MODEL, OBS, PLAIN> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent);
+        Rollout<R, MODEL, OBS, PLAIN, MOVING> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
         r.sh_first = seq_search ? &sh_first : nullptr;
         if (k >= k_start) {
 #pragma unroll
@@ -2128,6 +2188,31 @@ __global__ __launch_bounds__(256) void k_eval(const KParams<R> P, int what, cons
     }
 }
 
+// `_is_collided` and the costs of a handle with moving obstacles: pose i against the circles steps[i] rollout steps ahead of the
+// current clock (steps null: 0 -- "now"); the clock is read from the device state as the rollout kernels read it
+template <typename R, int MODEL>
+__global__ __launch_bounds__(256) void k_eval_at(const KParams<R> P, int what, const R *__restrict__ x, const int *__restrict__ idx,
+                                                 const int *__restrict__ steps, int n, R *__restrict__ out) {
+    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
+    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
+    const bool act = i < n;
+    R s[4] = {R(0), R(0), R(0), R(0)};
+    if (act)
+        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
+    const int j = act && steps ? steps[i] : 0;
+    const R tau = obstacle_time(P, obstacle_clock(P.st->iter, P.iter0) + j);
+    const bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
+    if (what == EVAL_COLLIDED) {
+        if (act) out[i] = hit ? R(1) : R(0);
+    } else {
+        const bool term = what == EVAL_COST_TERMINAL;
+        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
+                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit);
+        if (act) out[i] = c;
+    }
+}
+
 // `_moving_average_filter` of a [T,2] signal in the handle's filter mode (one workgroup)
 template <typename A>
 __global__ __launch_bounds__(256) void k_eval_filter(const A *__restrict__ xx, A *__restrict__ out, int T, int W, int f_filter) {
@@ -2177,6 +2262,10 @@ template <typename R> static const char *type_name() { return sizeof(R) == 8 ? "
 template <typename R, int MODEL> static KernelLaunch rollout_entry() {
     static KernelEntry e("k_rollout<%s, %d>", type_name<R>(), MODEL);
     return plan_entry(reinterpret_cast<const void *>(k_rollout<R, MODEL>), e, 256);
+}
+template <typename R, int MODEL> static KernelLaunch rollout_moving_entry() {
+    static KernelEntry e("k_rollout_moving<%s, %d>", type_name<R>(), MODEL);
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_moving<R, MODEL>), e, 256);
 }
 template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK> static KernelLaunch fused_entry() {
     static KernelEntry e("k_rollout_fused<%s, %d, %d, %s, %d, %s>", type_name<R>(), MODEL, NCH, KernelEntry::of(MULTI), SPEC,
@@ -2232,7 +2321,8 @@ static bool tri_layout(const Switches &sw, int T, bool tri_ok) {
     if (sw.tri >= 0) return sw.tri != 0;
     return true;
 }
-int rollout_layout(const Switches &sw, int K, int T, int n_agents, int model, bool f64, bool per_rollout, bool tri_ok) {
+int rollout_layout(const Switches &sw, int K, int T, int n_agents, int model, bool f64, bool per_rollout, bool tri_ok, bool moving) {
+    if (moving) return LAYOUT_FUSED;  // (the moving collision test lives in the one-sample-per-wave kernels: Rollout::costs)
     if (!per_rollout && model == MODEL_RACE && !f64 && n_agents <= 1 && tri_layout(sw, T, tri_ok)) return LAYOUT_TRI;
     // (per-rollout index threading lives in the one-sample-per-wave kernels: Rollout::chunk)
     const int kind = per_rollout ? LAYOUT_FUSED : dual_layout(sw, K, T, n_agents) ? LAYOUT_DUAL : pair_layout(sw, T) ? LAYOUT_PAIR : LAYOUT_FUSED;
@@ -2286,8 +2376,11 @@ template <typename R, int MODEL, bool MULTI, int SPW> static KernelLaunch dual_p
         if (plain && !twice) return dual_entry<R, MODEL, 2, true, 1, true>();
     return twice ? dual_entry<R, MODEL, SPW, MULTI, 2, false>() : dual_entry<R, MODEL, SPW, MULTI, 1, false>();
 }
-// k_rollout_fused<R, MODEL, NCH, MULTI, SPEC, HYPK>: SPEC 2 the plain form, 1 no obstacles, 0 everything
+// k_rollout_fused<R, MODEL, NCH, MULTI, SPEC, HYPK>: SPEC 2 the plain form, 1 no obstacles, 0 everything, 3 everything with
+// moving obstacles (never with the look-back: lookback_serves, mppi_capi.hip)
 template <typename R, int MODEL, int NCH, bool MULTI, bool HYPK> static KernelLaunch fused_plan(int spec) {
+    if constexpr (!HYPK)
+        if (spec == 3) return fused_entry<R, MODEL, NCH, MULTI, 3, false>();
     return spec == 2   ? fused_entry<R, MODEL, NCH, MULTI, 2, HYPK>()
            : spec == 1 ? fused_entry<R, MODEL, NCH, MULTI, 1, HYPK>()
                        : fused_entry<R, MODEL, NCH, MULTI, 0, HYPK>();
@@ -2324,8 +2417,11 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
         {
             const bool plain = P.obstacle_model == OBS_NONE && P.use_philox && P.clamp_rollout && !P.wrap_stage && !P.wrap_term &&
                                !P.per_rollout;
-            const int spec = plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
-            p.lookback = !MULTI && MODEL == MODEL_DIFF && P.hyp && P.T <= 64;  // (the HYPK form: one agent, diff-drive, one chunk)
+            // (a handle with obstacle motion takes the moving form whatever its set holds at the moment -- none yet, or m = 0:
+            // an agent of a batch with no circles of its own then computes what its single-agent handle computes, bit for
+            // bit; the forms contract their cost arithmetic differently in the last place)
+            const int spec = P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
+            p.lookback = !MULTI && MODEL == MODEL_DIFF && P.hyp && P.T <= 64 && !P.obs_motion;  // (the HYPK form: one agent, diff-drive, one chunk)
             p.k = p.lookback  ? fused_plan<R, MODEL_DIFF, 1, false, true>(spec)
                   : P.T <= 64 ? fused_plan<R, MODEL, 1, MULTI, false>(spec)
                               : fused_plan<R, MODEL, 2, MULTI, false>(spec);
@@ -2343,7 +2439,8 @@ template <typename R> RolloutPlan plan_rollout(const KParams<R> &P, bool fused, 
         return diff ? plan_fused<R, MODEL_DIFF, false>(P, sw) : plan_fused<R, MODEL_RACE, false>(P, sw);
     }
     RolloutPlan p;
-    p.k = diff ? rollout_entry<R, MODEL_DIFF>() : rollout_entry<R, MODEL_RACE>();
+    if (P.obs_motion) p.k = diff ? rollout_moving_entry<R, MODEL_DIFF>() : rollout_moving_entry<R, MODEL_RACE>();
+    else p.k = diff ? rollout_entry<R, MODEL_DIFF>() : rollout_entry<R, MODEL_RACE>();
     p.k.grid = dim3((P.K + 3) / 4);  // four waves per workgroup, a sample each
     p.records = reduce_blocks(P.K, P.traj_per_block);
     return p;
@@ -2429,6 +2526,12 @@ void launch_eval(const KParams<R> &P, int what, const R *x, const R *v, const in
     if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, v, idx, n, out);
     else hipLaunchKernelGGL((k_eval<R, MODEL_RACE>), grid, block, 0, s, P, what, x, v, idx, n, out);
 }
+template <typename R>
+void launch_eval_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
+    const dim3 grid((n + 255) / 256), block(256);
+    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+    else hipLaunchKernelGGL((k_eval_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+}
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s) {
     hipLaunchKernelGGL(k_eval_filter<R>, dim3(1), dim3(256), sizeof(R) * 2 * (size_t)(T + W + 2), s, xx, out, T, W, mode);
 }
@@ -2479,6 +2582,7 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
     template void launch_weights<R>(const KParams<R> &, double, double, double *, hipStream_t);           \
     template void launch_eval_index<R>(const KParams<R> &, const R *, int, int, int, int, int *, int *, hipStream_t); \
     template void launch_eval<R>(const KParams<R> &, int, const R *, const R *, const int *, int, R *, hipStream_t);   \
+    template void launch_eval_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_filter<R>(const R *, R *, int, int, int, hipStream_t);                                 \
     template void launch_set_state_dev<R>(const KParams<R> &, const double *, int, hipStream_t);                     \
     template void launch_viz<R>(const KParams<R> &, const R *, const R *, long long, float *, float *, hipStream_t);

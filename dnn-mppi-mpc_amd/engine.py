@@ -33,7 +33,7 @@ class Engine:
     def __init__(self, **cfg):
         self.lib = capi.load_library()
         c = capi.MppiConfig()
-        c.struct_size = C.sizeof(capi.MppiConfig)
+        c.struct_size = capi.config_size(self.lib)
         for k, v in cfg.items():
             if k in ("u_max", "sigma", "stage_cost_weight", "terminal_cost_weight"):
                 arr = np.asarray(v, dtype=np.float64).reshape(-1)
@@ -42,6 +42,8 @@ class Engine:
                     field[i] = float(arr[i]) if i < arr.size else 0.0
             else:
                 setattr(c, k, v)
+        if c.obstacle_motion and c.struct_size != C.sizeof(capi.MppiConfig):
+            raise capi.MppiError(capi.ERR_UNSUPPORTED, "obstacle_motion needs a library of ABI version 7 or later")
         self.cfg = c
         self.K, self.T = int(c.K), int(c.T)
         self.nx = 4 if c.model == capi.MODEL_RACECAR else 3
@@ -81,10 +83,20 @@ class Engine:
         else:
             self._ck(self.lib.mppi_set_agent_ref_path(self._h, int(agent), _dp(p), p.shape[0], p.shape[1]))
 
-    def set_obstacles(self, circles, agent=None):
-        """``agent``: as in `set_ref_path`; an agent given no circles collides with nothing."""
+    def set_obstacles(self, circles, agent=None, velocities=None):
+        """``agent``: as in `set_ref_path`; an agent given no circles collides with nothing.  ``velocities``: [m, 2] = vx, vy
+        in metres per second, for a handle created with ``obstacle_motion=1`` (the circles then stand where given at this
+        call and move with the handle's iteration counter, see mppi_config.obstacle_motion); None: they stand still."""
         c = np.ascontiguousarray(circles, dtype=np.float64).reshape(-1, 3)
-        if agent is None:
+        if velocities is not None:
+            v = np.ascontiguousarray(velocities, dtype=np.float64).reshape(-1, 2)
+            if v.shape[0] != c.shape[0]:
+                raise ValueError("one velocity per circle")
+            if agent is None:
+                self._ck(self.lib.mppi_set_obstacles_moving(self._h, _dp(c), _dp(v), c.shape[0]))
+            else:
+                self._ck(self.lib.mppi_set_agent_obstacles_moving(self._h, int(agent), _dp(c), _dp(v), c.shape[0]))
+        elif agent is None:
             self._ck(self.lib.mppi_set_obstacles(self._h, _dp(c), c.shape[0]))
         else:
             self._ck(self.lib.mppi_set_agent_obstacles(self._h, int(agent), _dp(c), c.shape[0]))
@@ -360,10 +372,18 @@ class Engine:
         self._ck(self.lib.mppi_eval_clamp(self._h, _dp(v), v.shape[0], _dp(out)))
         return out
 
-    def eval_is_collided(self, x):
+    def eval_is_collided(self, x, steps=None):
+        """``steps``: int [n], pose i is tested against the circles ``steps[i]`` rollout steps ahead of the current obstacle
+        clock (moving obstacles); None: now."""
         x = self._rows(x, self.nx)
         out = np.empty(x.shape[0])
-        self._ck(self.lib.mppi_eval_is_collided(self._h, _dp(x), x.shape[0], _dp(out)))
+        if steps is None:
+            self._ck(self.lib.mppi_eval_is_collided(self._h, _dp(x), x.shape[0], _dp(out)))
+            return out
+        st = np.ascontiguousarray(steps, dtype=np.int32).reshape(-1)
+        if st.shape[0] != x.shape[0]:
+            raise ValueError("one step per pose")
+        self._ck(self.lib.mppi_eval_is_collided_at(self._h, _dp(x), x.shape[0], st.ctypes.data_as(C.POINTER(C.c_int32)), _dp(out)))
         return out
 
     def eval_nearest_waypoint(self, x, prev_idx, update_prev_idx=False):

@@ -37,6 +37,25 @@ int main(void) {
     c.sigma[1] = c.sigma[2] = 1.0; /* not positive definite */
     EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG);
     c.sigma[1] = c.sigma[2] = 0.0;
+    /* moving obstacles: the create-time refusals come before any device work, each with its reason as text */
+    c.obstacle_motion = 1; /* (obstacle_model is MPPI_OBSTACLE_NONE) */
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG && strstr(mppi_last_error(NULL), "MPPI_OBSTACLE_NONE") != NULL);
+    c.obstacle_model = MPPI_OBSTACLE_CIRCLE;
+    c.model = MPPI_MODEL_DIFFDRIVE_MLP;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_UNSUPPORTED && strstr(mppi_last_error(NULL), "MPPI_MODEL_DIFFDRIVE_MLP") != NULL);
+    c.obstacle_motion = 2;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG);
+    c.model = MPPI_MODEL_DIFFDRIVE;
+    c.obstacle_model = MPPI_OBSTACLE_NONE;
+    c.obstacle_motion = 0;
+    {   /* and the setters refuse a NULL handle before anything is read */
+        double circle[3] = {0.5, 0.5, 0.1}, vel[2] = {0.1, 0.0};
+        int32_t step = 0;
+        double out = 0.0;
+        EXPECT(mppi_set_obstacles_moving(NULL, circle, vel, 1) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_agent_obstacles_moving(NULL, 0, circle, vel, 1) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_eval_is_collided_at(NULL, circle, 1, &step, &out) == MPPI_ERR_BAD_ARG);
+    }
     const int rc = mppi_create(&c, &h); /* a box without an MI355X: MPPI_ERR_NO_DEVICE, with the reason as text */
     if (rc == MPPI_OK) {
         double path[6] = {0, 0, 0, 1, 1, 0};

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MPPI_ABI_VERSION 6
+#define MPPI_ABI_VERSION 7
 
 typedef enum {
     MPPI_OK = 0,
@@ -140,6 +140,24 @@ typedef struct {
     /* fourth word of the sampler's Philox counter (agent a of a batched handle draws with noise_stream + a, so a
      * single-agent handle with noise_stream = a reproduces its noise) */
     int32_t noise_stream;
+    /* Moving obstacles.  0: every circle stands still (zero-initialised configs: as before).  1: a circle is {x, y, r, vx, vy},
+     * constant velocity in world coordinates, metres per second (mppi_set_obstacles_moving, mppi_set_agent_obstacles_moving).
+     * A create-time field: the rollout layout and the record buffers are decided here -- such a handle runs the one-sample-
+     * per-wave kernels for every K (several agents: T <= 128 and K <= 8192, as documented above).
+     * THE OBSTACLE CLOCK IS THE HANDLE'S ITERATION COUNTER, the one the sampler reads (mppi_stats.iteration): with iter0 its
+     * value when the set was uploaded, n = iteration - iter0 control steps have passed since, and the state a rollout reaches
+     * after j steps is tested against the centres c + v * (delta_t * (n + j)): j = 1 .. T for the stage calls, j = T for the
+     * terminal call (it prices the same state as the last stage call), j = 0 for whatever prices "now" (mppi_eval_is_collided,
+     * mppi_eval_cost).  delta_t * (n + j) is evaluated in the handle's precision with the integer n + j converted exactly,
+     * then one fused multiply-add per coordinate; zero velocities give the static centres exactly.  An f32 handle loses centre
+     * precision as |v| * delta_t * n grows (half an ulp of that product): a caller to whom that matters uploads fresh
+     * positions, which re-bases iter0.
+     * One iteration is one tick: all speculation rounds of an iteration see the same clock, mppi_run_closed_loop advances
+     * the obstacles with the plant without the host, and a replayed graph (MPPI_GRAPH=1) reads the clock afresh from the
+     * device.  mppi_set_iteration replays noise and must not move obstacles: it shifts iter0 by the same amount.
+     * Needs an obstacle model (MPPI_OBSTACLE_NONE: MPPI_ERR_BAD_ARG); MPPI_MODEL_DIFFDRIVE_MLP: MPPI_ERR_UNSUPPORTED. */
+    int32_t obstacle_motion;
+    int32_t reserved0;
 } mppi_config;
 
 /* per-iteration diagnostics (the reference only prints) */
@@ -187,6 +205,14 @@ int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m);
  * (MPPI_ERR_STATE).  On a single-agent handle agent = 0 is the plain setter. */
 int mppi_set_agent_ref_path(mppi_handle *h, int32_t agent, const double *path, int32_t n, int32_t ncols);
 int mppi_set_agent_obstacles(mppi_handle *h, int32_t agent, const double *xyr, int32_t m);
+/* The two obstacle setters for a handle with mppi_config.obstacle_motion = 1 (on any other handle: MPPI_ERR_STATE): xyr as
+ * above and vel (host, [m,2] = vx,vy; metres per second) as the circles stand and move AT THIS CALL -- it sets iter0 to the
+ * current iteration counter (see mppi_config.obstacle_motion).  Otherwise the semantics of mppi_set_obstacles /
+ * mppi_set_agent_obstacles: the shared set or one agent's own, m = 0 collides with nothing.  Non-finite velocities are
+ * MPPI_ERR_BAD_ARG, and a refused call leaves the scene as it was.  On such a handle the static setters above stay valid
+ * and mean velocity 0. */
+int mppi_set_obstacles_moving(mppi_handle *h, const double *xyr, const double *vel, int32_t m);
+int mppi_set_agent_obstacles_moving(mppi_handle *h, int32_t agent, const double *xyr, const double *vel, int32_t m);
 /* Per agent: `prev_way_point_idx` / `prev_waypoints_idx` (mppi_differential_drive.py:85) and whether its last x0 call found
  * the last waypoint of ITS path (:97-99, mppi_race_car.py:62-65) -- with paths of different lengths, which agent stopped a
  * call that returned MPPI_ERR_PATH_END.  Host int32_t[n_agents] each, either may be NULL. */
@@ -338,7 +364,8 @@ int mppi_sample_epsilon(mppi_handle *h, int64_t iteration, float *eps_out, void 
  * iterations bit for bit.
  */
 int mppi_set_noise_ring(mppi_handle *h, const float *eps_ring, int32_t n_slots);
-/* iteration counter that keys the sampler (checkpoint / resume) */
+/* iteration counter that keys the sampler (checkpoint / resume).  Moving obstacles stay where they are: the clock's origin
+ * moves with the counter (see mppi_config.obstacle_motion). */
 int mppi_set_iteration(mppi_handle *h, int64_t iteration);
 
 /*
@@ -382,6 +409,10 @@ int mppi_run_closed_loop(mppi_handle *h, int32_t n_iters, double *u0_trace /* ho
 int mppi_eval_state_transition(mppi_handle *h, const double *x, const double *v, int32_t n, double *x_next);
 int mppi_eval_clamp(mppi_handle *h, const double *v, int32_t n, double *out);
 int mppi_eval_is_collided(mppi_handle *h, const double *x, int32_t n, double *out);
+/* `_is_collided` of pose i against the circles steps[i] >= 0 rollout steps ahead of the current obstacle clock (host
+ * int32_t[n]; see mppi_config.obstacle_motion: steps[i] = j of the rollout).  mppi_eval_is_collided and mppi_eval_cost price
+ * at step 0 of the current clock.  On a handle without obstacle motion the steps change nothing. */
+int mppi_eval_is_collided_at(mppi_handle *h, const double *x, int32_t n, const int32_t *steps, double *out);
 int mppi_eval_nearest_waypoint(mppi_handle *h, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
                                int32_t *idx_out);
 int mppi_eval_cost(mppi_handle *h, int32_t terminal, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
