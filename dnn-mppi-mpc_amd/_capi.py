@@ -9,9 +9,9 @@ import ctypes as C
 import os
 
 PKG = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 7  # MPPI_ABI_VERSION of include/mppi_hip.h this mirror was written against
+ABI_VERSION = 8  # MPPI_ABI_VERSION of include/mppi_hip.h this mirror was written against
 MIN_AB_ABI_VERSION = 3  # oldest library an MPPI_LIB override may point at: the mppi_config layout of today up to the fields
-                        # version 7 appended (config_size) (an ABI-3 library fills the first fields of mppi_stats only: the
+                        # versions 7 and 8 appended (config_size) (an ABI-3 library fills the first fields of mppi_stats only: the
                         # struct grew at its end in version 4)
 LIB_PATH = os.environ.get("MPPI_LIB") or os.path.join(PKG, "lib", "libmppi_hip.so")  # MPPI_LIB: A/B a diagnostic build
 
@@ -40,14 +40,16 @@ class MppiConfig(C.Structure):
         ("filter_window", C.c_int32), ("obstacle_model", C.c_int32), ("raise_at_path_end", C.c_int32),
         ("safety_margin", C.c_double), ("vehicle_w", C.c_double), ("vehicle_l", C.c_double),
         ("collision_penalty", C.c_double), ("seed", C.c_uint64), ("n_agents", C.c_int32), ("noise_stream", C.c_int32),
-        ("obstacle_motion", C.c_int32), ("reserved0", C.c_int32),
+        ("obstacle_motion", C.c_int32), ("reserved0", C.c_int32), ("fleet_radius", C.c_double),
     ]
 
 
 def config_size(lib):
     """sizeof(mppi_config) as `lib` compares it in mppi_create: version 7 appended obstacle_motion (8 bytes with its
-    padding), so an older diagnostic build under MPPI_LIB takes the struct without them."""
-    return C.sizeof(MppiConfig) - (8 if lib.mppi_abi_version() < 7 else 0)
+    padding) and version 8 fleet_radius (8 bytes), so an older diagnostic build under MPPI_LIB takes the struct without them:
+    16 bytes less below version 7, 8 less below 8."""
+    v = lib.mppi_abi_version()
+    return C.sizeof(MppiConfig) - (16 if v < 7 else 8 if v < 8 else 0)
 
 
 class MppiStats(C.Structure):
@@ -134,6 +136,8 @@ PROTOTYPES = {
     "mppi_eval_clamp": (C.c_int, [_H, _D, C.c_int32, _D]),
     "mppi_eval_is_collided": (C.c_int, [_H, _D, C.c_int32, _D]),
     "mppi_eval_is_collided_at": (C.c_int, [_H, _D, C.c_int32, C.POINTER(C.c_int32), _D]),
+    "mppi_get_agent_circles": (C.c_int, [_H, C.c_int32, _D, _D, C.c_int32, C.POINTER(C.c_int32)]),
+    "mppi_get_fleet_clearance": (C.c_int, [_H, _D, C.POINTER(C.c_int64), C.c_int32]),
     "mppi_eval_nearest_waypoint": (C.c_int, [_H, _D, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "mppi_eval_cost": (C.c_int, [_H, C.c_int32, _D, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _D, C.POINTER(C.c_int32)]),
     "mppi_eval_moving_average": (C.c_int, [_H, _D, _D]),

@@ -126,10 +126,19 @@ struct mppi_handle {
         int n_ref = 0, n_obs = 0;
         bool has_obs = false;  // (an own set of m = 0 circles has no buffer)
         long long obs_iter0 = 0;  // moving obstacles: the agent's iteration counter when its own set was uploaded
+        std::vector<double> obs_host;  // fleet handles: the packed rows of d_obs as uploaded ([n_obs] circles, [n_obs] velocities)
     };
     std::vector<OwnScene> own;
     DevBuf<AgentScene> d_scenes;
     long long obs_iter0 = 0;  // moving obstacles (mppi_config.obstacle_motion): the iteration counter when d_obs was uploaded
+    // Fleet avoidance (mppi_config.fleet_radius > 0): every agent b owns a table of m_b + B - 1 circle rows and as many velocity
+    // rows -- its own circles (the shared set's or its own: written by the host at every setter, build_fleet_tables) followed by its
+    // mates' rows, which k_fleet_rows writes at the front of every slot.  scene_of hands these tables to the kernels; d_obs and
+    // own[a].d_obs keep what the setters uploaded and are not read by a launch.  d_clear: the agents' clearance records.
+    bool fleet = false;
+    std::vector<double> obs_host;  // the shared set's packed rows, as OwnScene::obs_host
+    std::vector<DevBuf<void>> fleet_tab;
+    DevBuf<FleetClear> d_clear;
     DevBuf<int> d_pout;
     DevBuf<void> d_partials;        // block records in the handle's precision
     DevBuf<double> d_w, d_trace;
@@ -214,6 +223,7 @@ static AgentScene scene_of(const mppi_handle *h, int a) {
         if (o.has_obs) sc.obs = o.d_obs, sc.n_obs = o.n_obs, sc.iter0 = o.obs_iter0;
     }
     if (h->cfg.obstacle_model == MPPI_OBSTACLE_NONE) sc.n_obs = 0;
+    if (h->fleet) sc.obs = h->fleet_tab[a], sc.n_obs += h->B - 1;  // (its own rows first, then one per mate: build_fleet_tables)
     return sc;
 }
 // some agent has obstacles: the obstacle instantiations serve and the records carry collision counts
@@ -239,6 +249,8 @@ static bool lookback_serves(const mppi_handle *h, int records) {
 static bool index_can_move(const mppi_handle *h) { return h->hyp && !(h->idx_valid && h->n_ref > 0 && at_path_end(h, h->idx)); }
 template <typename R> static KParams<R> make_params(const mppi_handle *h, const float *eps);
 template <typename R> static RolloutPlan front_plan(const mppi_handle *h, const KParams<R> &P);
+static int upload_scenes(mppi_handle *h);
+static int build_fleet_tables(mppi_handle *h, int only);
 
 // host double[] -> device array in the kernel precision
 static int upload_real(mppi_handle *h, void *dst, const double *src, size_t n) {
@@ -290,6 +302,14 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
     if (c.obstacle_motion && c.model == MPPI_MODEL_DIFFDRIVE_MLP)
         CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "moving obstacles (obstacle_motion = 1) are served by the analytic models only: the "
                                           "learned-dynamics rollout (MPPI_MODEL_DIFFDRIVE_MLP) tests static circles");
+    if (!(c.fleet_radius >= 0) || !std::isfinite(c.fleet_radius))
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: fleet_radius %g is not a finite radius >= 0 (0: fleet avoidance off)", c.fleet_radius);
+    if (c.fleet_radius > 0 && c.n_agents < 2)
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: fleet_radius > 0 needs n_agents >= 2 (an agent's mates are the other agents of its handle), got %d", c.n_agents);
+    if (c.fleet_radius > 0 && !c.obstacle_motion)
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: fleet_radius > 0 needs obstacle_motion = 1 (the mates are moving circles)");
+    if (c.fleet_radius > 0 && c.n_agents > 256)
+        CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "fleet avoidance serves at most 256 agents per handle (n_agents = %d): every agent tests every other", c.n_agents);
     if (c.filter_window < 1) c.filter_window = 10;
     if (c.search_window < 1) CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: search_window must be >= 1");
     // the reference's filters fail on short horizons (np.convolve 'same' returns max(M, N) samples)
@@ -407,6 +427,18 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
             if (int rc = zeroed(h->d_models, B * sizeof(MlpParams), "hipMalloc(agent models)")) return rc;
         }
     }
+    if (c.fleet_radius > 0) {
+        h->fleet = true;
+        h->fleet_tab.resize(B);
+        if ((e = h->d_clear.alloc(B * sizeof(FleetClear))) != hipSuccess) return fail(e, "hipMalloc(fleet clearance)");
+        const std::vector<FleetClear> none(B, FleetClear{INFINITY, 0});
+        if ((e = hipMemcpy(h->d_clear, none.data(), B * sizeof(FleetClear), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+        if (build_fleet_tables(h, -1) != MPPI_OK || upload_scenes(h) != MPPI_OK) {  // (no own circles yet: the mates' rows alone)
+            g_create_error = h->err;
+            mppi_destroy(h);
+            return MPPI_ERR_HIP;
+        }
+    }
     DevState st0;
     memset(&st0, 0, sizeof(st0));  // prev_way_point_idx = 0 (:85)
     st0.first_k = NO_TRIGGER;
@@ -429,6 +461,28 @@ extern "C" int mppi_destroy(mppi_handle *h) {
     return MPPI_OK;
 }
 
+// Fleet handles: agent `only`'s table (-1: every agent's) made again from the host's copy of its own rows -- m_b circle rows,
+// B - 1 mate rows, the same of velocities -- with the mate rows zero (a threshold of 0 collides with nothing) until
+// k_fleet_rows writes them.  The caller has synchronised the device and uploads the scenes afterwards.
+static int build_fleet_tables(mppi_handle *h, int only) {
+    for (int a = 0; h->fleet && a < h->B; ++a) {
+        if (only >= 0 && a != only) continue;
+        const mppi_handle::OwnScene &o = h->own[a];
+        const int m = o.has_obs ? o.n_obs : h->n_obs, n = m + h->B - 1;
+        const std::vector<double> &src = o.has_obs ? o.obs_host : h->obs_host;
+        std::vector<double> rows((size_t)8 * n, 0.0);
+        if (src.size() == (size_t)8 * m) {
+            std::copy(src.begin(), src.begin() + 4 * (size_t)m, rows.begin());
+            std::copy(src.begin() + 4 * (size_t)m, src.end(), rows.begin() + 4 * (size_t)n);
+        } else if (m > 0) {
+            FAIL(h, MPPI_ERR_STATE, "fleet table of agent %d: the host copy of its %d circles is missing", a, m);
+        }
+        HIPCHECK(h, h->fleet_tab[a].reset());
+        HIPCHECK(h, h->fleet_tab[a].alloc(rsz(h) * rows.size()));
+        if (int rc = upload_real(h, h->fleet_tab[a], rows.data(), rows.size())) return rc;
+    }
+    return MPPI_OK;
+}
 // The batched kernels' table (AgentScene[n_agents]), rewritten from the host's view of every agent (the caller has synchronised
 // the device).  The table is read at run time, so a cached graph (ensure_graph) replays the new scenes; what a launch carries
 // by value -- agent 0's scene and the "any agent has obstacles" decisions in KParams / FinalizeParams -- is part of the graph's key.
@@ -470,7 +524,7 @@ static int set_path(mppi_handle *h, const char *who, const double *path, int32_t
 // follow the m circle rows (vel null: zeros) and *iter0 receives agent `clock_agent`'s iteration counter as of now.
 // Everything that can refuse the arguments stands before the first change.
 static int set_circles(mppi_handle *h, const char *who, const double *xyr, const double *vel, int32_t m, DevBuf<void> *d_obs,
-                       int *n_obs, long long *iter0, int clock_agent) {
+                       int *n_obs, long long *iter0, int clock_agent, std::vector<double> *host_copy) {
     if (m > 0 && !xyr) FAIL(h, MPPI_ERR_BAD_ARG, "%s: null argument", who);
     if (m < 0) FAIL(h, MPPI_ERR_SHAPE, "%s: m < 0", who);
     const bool moving = h->cfg.obstacle_motion != 0;
@@ -484,6 +538,7 @@ static int set_circles(mppi_handle *h, const char *who, const double *xyr, const
     HIPCHECK(h, d_obs->reset());
     *n_obs = m;
     *iter0 = now;
+    host_copy->clear();
     if (m == 0) return MPPI_OK;
     std::vector<double> packed((size_t)m * (moving ? 8 : 4), 0.0);
     for (int i = 0; moving && vel && i < m; ++i) {
@@ -499,6 +554,7 @@ static int set_circles(mppi_handle *h, const char *who, const double *xyr, const
         packed[4 * i + 2] = thr * thr;
     }
     HIPCHECK(h, d_obs->alloc(rsz(h) * packed.size()));
+    if (h->fleet) *host_copy = packed;  // (what build_fleet_tables copies into the agents' tables)
     return upload_real(h, *d_obs, packed.data(), packed.size());
 }
 
@@ -513,12 +569,14 @@ extern "C" int mppi_set_ref_path(mppi_handle *h, const double *path, int32_t n, 
 }
 
 static int set_shared_circles(mppi_handle *h, const char *who, const double *xyr, const double *vel, int32_t m) {
-    if (int rc = set_circles(h, who, xyr, vel, m, &h->d_obs, &h->n_obs, &h->obs_iter0, 0)) return rc;
+    if (int rc = set_circles(h, who, xyr, vel, m, &h->d_obs, &h->n_obs, &h->obs_iter0, 0, &h->obs_host)) return rc;
     for (mppi_handle::OwnScene &o : h->own) {
         o.n_obs = 0;
         o.has_obs = false;
+        o.obs_host.clear();
         HIPCHECK(h, o.d_obs.reset());
     }
+    if (int rc = build_fleet_tables(h, -1)) return rc;
     return upload_scenes(h);
 }
 static int set_agent_circles(mppi_handle *h, const char *who, int32_t agent, const double *xyr, const double *vel, int32_t m) {
@@ -526,8 +584,10 @@ static int set_agent_circles(mppi_handle *h, const char *who, int32_t agent, con
     if (h->B == 1) return set_shared_circles(h, who, xyr, vel, m);
     mppi_handle::OwnScene &o = h->own[agent];
     h->dev_loop_primed = false;
-    const int rc = set_circles(h, who, xyr, vel, m, &o.d_obs, &o.n_obs, &o.obs_iter0, agent);
+    const int rc = set_circles(h, who, xyr, vel, m, &o.d_obs, &o.n_obs, &o.obs_iter0, agent, &o.obs_host);
     if (rc == MPPI_OK || rc == MPPI_ERR_HIP) o.has_obs = rc == MPPI_OK;  // (refused arguments change nothing)
+    if (rc == MPPI_OK || rc == MPPI_ERR_HIP)
+        if (int rc2 = build_fleet_tables(h, agent)) return rc ? rc : rc2;
     if (int rc2 = upload_scenes(h)) return rc ? rc : rc2;
     return rc;
 }
@@ -1003,6 +1063,29 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     return P;
 }
 
+// Fleet handles: the arguments of the k_fleet_rows launch at the front of a slot (count = 1) or of the refresh in front of a
+// getter or an mppi_eval_* call (count = 0: the clearance records stay).  A mate's threshold is packed as set_circles packs a
+// circle of radius fleet_radius; dt is rounded as KParams::dt is.
+static FleetParams make_fleet(const mppi_handle *h, int count) {
+    const mppi_config &c = h->cfg;
+    FleetParams F;
+    memset(&F, 0, sizeof(F));
+    F.scenes = h->d_scenes;
+    F.st = h->d_st;
+    F.u = h->d_u;
+    F.clear = h->d_clear;
+    F.n_agents = h->B;
+    F.T = c.T;
+    F.model = kernel_model(c);
+    F.count = count;
+    F.dt = h->f64 ? c.delta_t : (double)(float)c.delta_t;
+    F.umax0 = c.u_max[0];
+    const double thr = c.obstacle_model == MPPI_OBSTACLE_CIRCLE ? 0.5 * c.safety_margin + c.fleet_radius : c.fleet_radius;
+    F.thr2 = thr * thr;
+    F.contact = 2.0 * c.fleet_radius;
+    return F;
+}
+
 // the softmin rate as the records carry it
 static double record_beta(const mppi_handle *h) {
     const double beta = softmin_beta(h->cfg);
@@ -1128,9 +1211,11 @@ static SlotPlan plan_slot(const mppi_handle *h, const KParams<R> &P, FinalizePar
     return sp;
 }
 
-// the plan's launches up to its reader: [rollout] [reduce / merge]
+// the plan's launches up to its reader: [rollout] [reduce / merge].  A fleet handle: k_fleet_rows leads the slot, inside the
+// rollout's event pair (mppi_last_kernel_ms out[0]) and outside the launch counters (mppi_get_counters)
 template <typename R> static void launch_records(mppi_handle *h, const SlotPlan &sp, const KParams<R> &P, hipStream_t s, bool tm) {
     if (tm) hipEventRecord(next_event(h), s);
+    if (h->fleet) launch_fleet_rows<R>(make_fleet(h, 1), s);
     h->n_rollout_launches += h->rollout_repeats;
     for (int rep = 0; rep < h->rollout_repeats; ++rep) {
         if constexpr (sizeof(R) == 4)
@@ -1865,13 +1950,15 @@ static bool ensure_graph(mppi_handle *h, const SlotPlan &sp, const KParams<R> &P
     // (the learned model's parameters too: its launches carry MlpParams -- weight pointers, shape, output bias -- by value,
     // agent 0's; a batched launch carries the address of the agents' table instead, whose entries a replay reads afresh)
     const MlpParams *const models = h->d_models;  // (the raw address: that is what a launch carries)
-    std::vector<char> key(sizeof(P) + sizeof(F) + 2 * sizeof(int) + sizeof(MlpParams) + sizeof(models));
+    const FleetParams fleet = h->fleet ? make_fleet(h, 1) : FleetParams{};  // (the k_fleet_rows launch of a slot)
+    std::vector<char> key(sizeof(P) + sizeof(F) + 2 * sizeof(int) + sizeof(MlpParams) + sizeof(models) + sizeof(fleet));
     memcpy(key.data(), &P, sizeof(P));
     memcpy(key.data() + sizeof(P), &F, sizeof(F));
     const int tail[2] = {h->rollout_repeats, (int)sizeof(R)};
     memcpy(key.data() + sizeof(P) + sizeof(F), tail, sizeof(tail));
     memcpy(key.data() + sizeof(P) + sizeof(F) + sizeof(tail), &h->mlp, sizeof(MlpParams));
     memcpy(key.data() + sizeof(P) + sizeof(F) + sizeof(tail) + sizeof(MlpParams), &models, sizeof(models));
+    memcpy(key.data() + sizeof(P) + sizeof(F) + sizeof(tail) + sizeof(MlpParams) + sizeof(models), &fleet, sizeof(fleet));
     if (h->graph_exec[0] && key == h->graph_key) return true;
     if (h->sw.graph_verbose) fprintf(stderr, "[mppi] capturing a graph of %d iterations\n", GRAPH_SLOTS);
     drop_graph(h);
@@ -2125,8 +2212,10 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
         HIPCHECK(h, dout.alloc(sizeof(R) * (size_t)n * n_out));
         if (what == EVAL_TRANSITION && h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP)  // x + dt (f + MLP([x, v])), fp32 handles only
             eval_transition_mlp(h, P, dx, dv, n, dout);
-        else if (at)
+        else if (at) {
+            if (h->fleet) launch_fleet_rows<R>(make_fleet(h, 0), nullptr);  // agent 0's mates as of the current states
             launch_eval_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+        }
         else
             launch_eval<R>(P, what, dx, dv, di, n, dout, nullptr);
     }
@@ -2169,6 +2258,68 @@ extern "C" int mppi_eval_is_collided_at(mppi_handle *h, const double *x, int32_t
         if (steps[i] < 0) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_is_collided_at: steps[%d] = %d is negative (steps count ahead of the clock)", i, steps[i]);
     return eval_entry(h, "mppi_eval_is_collided_at", EVAL_COLLIDED, x, nullptr, n, nullptr, 0, out, nullptr, steps);
 }
+
+// The circles agent `agent`'s next iteration tests, read back from its table (a fleet handle: the mates' rows made afresh first)
+template <typename R>
+static int agent_circles_impl(mppi_handle *h, int agent, double *xyr_out, double *vel_out, int cap, int32_t *m_out) {
+    const AgentScene sc = scene_of(h, agent);
+    const int m = sc.n_obs;
+    *m_out = m;
+    if (cap < m) FAIL(h, MPPI_ERR_SHAPE, "mppi_get_agent_circles: agent %d has %d circles, cap = %d", agent, m, cap);
+    if (m == 0) return MPPI_OK;
+    if (!sc.obs) FAIL(h, MPPI_ERR_STATE, "mppi_get_agent_circles: obstacles not uploaded");
+    const bool moving = h->cfg.obstacle_motion != 0;
+    HIPCHECK(h, hipDeviceSynchronize());
+    if (h->fleet) {
+        launch_fleet_rows<R>(make_fleet(h, 0), nullptr);
+        HIPCHECK(h, hipDeviceSynchronize());
+    }
+    std::vector<R> rows((size_t)(moving ? 8 : 4) * m, R(0));
+    long long now = 0;
+    HIPCHECK(h, hipMemcpy(rows.data(), sc.obs, sizeof(R) * rows.size(), hipMemcpyDeviceToHost));
+    if (moving) HIPCHECK(h, hipMemcpy(&now, &h->d_st[agent].iter, sizeof(now), hipMemcpyDeviceToHost));
+    const R tau = (R)h->cfg.delta_t * (R)(int)(now - sc.iter0);  // (obstacle_time at j = 0)
+    for (int i = 0; i < m; ++i) {
+        const R vx = moving ? rows[4 * (size_t)(m + i)] : R(0), vy = moving ? rows[4 * (size_t)(m + i) + 1] : R(0);
+        const double thr = sqrt((double)rows[4 * (size_t)i + 2]);
+        xyr_out[3 * i] = (double)std::fma(vx, tau, rows[4 * (size_t)i]);
+        xyr_out[3 * i + 1] = (double)std::fma(vy, tau, rows[4 * (size_t)i + 1]);
+        xyr_out[3 * i + 2] = h->cfg.obstacle_model == MPPI_OBSTACLE_CIRCLE ? thr - 0.5 * h->cfg.safety_margin : thr;
+        vel_out[2 * i] = (double)vx;
+        vel_out[2 * i + 1] = (double)vy;
+    }
+    return MPPI_OK;
+}
+
+extern "C" int mppi_get_agent_circles(mppi_handle *h, int32_t agent, double *xyr_out, double *vel_out, int32_t cap, int32_t *m_out) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (!m_out || cap < 0 || (cap > 0 && (!xyr_out || !vel_out))) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_get_agent_circles: bad argument");
+    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_get_agent_circles: agent %d not in [0, %d)", agent, h->B);
+    if (h->cfg.obstacle_model == MPPI_OBSTACLE_NONE)
+        FAIL(h, MPPI_ERR_STATE, "mppi_get_agent_circles: the handle has no obstacle model (MPPI_OBSTACLE_NONE)");
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    return with_real(h, [&](auto r) { return agent_circles_impl<decltype(r)>(h, agent, xyr_out, vel_out, cap, m_out); });
+}
+
+extern "C" int mppi_get_fleet_clearance(mppi_handle *h, double *min_dist, int64_t *contact_iters, int32_t reset) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (!h->fleet)
+        FAIL(h, MPPI_ERR_STATE, "mppi_get_fleet_clearance: the handle was created with fleet_radius = 0 (no fleet avoidance)");
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    std::vector<FleetClear> rec(h->B);
+    HIPCHECK(h, hipMemcpy(rec.data(), h->d_clear, sizeof(FleetClear) * rec.size(), hipMemcpyDeviceToHost));
+    for (int a = 0; a < h->B; ++a) {
+        if (min_dist) min_dist[a] = rec[a].min_dist;
+        if (contact_iters) contact_iters[a] = rec[a].contact_iters;
+    }
+    if (reset) {
+        std::fill(rec.begin(), rec.end(), FleetClear{INFINITY, 0});
+        HIPCHECK(h, hipMemcpy(h->d_clear, rec.data(), sizeof(FleetClear) * rec.size(), hipMemcpyHostToDevice));
+    }
+    return MPPI_OK;
+}
+
 extern "C" int mppi_eval_nearest_waypoint(mppi_handle *h, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
                                           int32_t *idx_out) {
     if (h && !idx_out) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_nearest_waypoint: idx_out is null");

@@ -375,6 +375,24 @@ void launch_eval(const KParams<R> &P, int what, const R *x, const R *v, const in
 // clock (steps null: 0).  what: EVAL_COST_STAGE, EVAL_COST_TERMINAL or EVAL_COLLIDED
 template <typename R>
 void launch_eval_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
+// Fleet avoidance (mppi_config.fleet_radius): what k_fleet_rows takes.  Agent b's table (AgentScene::obs, n_obs rows of circles
+// then n_obs rows of velocities) ends in n_agents - 1 mate rows; FleetClear is agent b's persistent clearance record.
+struct FleetClear {
+    double min_dist;          // smallest centre distance to a mate over the counted launches (+inf: none)
+    long long contact_iters;  // counted launches that found it below `contact`
+};
+struct FleetParams {
+    const AgentScene *scenes;  // [n_agents]
+    const DevState *st;        // [n_agents]
+    const void *u;             // [n_agents][T][2] nominal controls in the handle's precision
+    FleetClear *clear;         // [n_agents]
+    int n_agents, T, model;
+    int count;                 // 1: an iteration starts here (the clearance records it); 0: a refresh for a getter / mppi_eval_*
+    double dt, umax0;          // dt: as KParams::dt (already rounded to the handle's precision)
+    double thr2;               // a mate's packed threshold, as set_circles packs a circle of radius fleet_radius
+    double contact;            // 2 * fleet_radius
+};
+template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s);
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s);
 void launch_eval_weights(const double *S, int n, double beta, double *w, hipStream_t s);
 template <typename R> void launch_set_state_dev(const KParams<R> &P, const double *x_dev, int nx, hipStream_t s);

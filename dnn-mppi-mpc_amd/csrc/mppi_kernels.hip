@@ -2253,6 +2253,51 @@ __global__ __launch_bounds__(64) void k_set_state_dev(const R *ref, int n_ref, i
     x0_call<R>(st, ref, n_ref, window, sequential, lane, x0, x1, st->p);
 }
 
+// Fleet avoidance (mppi_config.fleet_radius): the mates of agent b as moving circles, written behind b's own circles at the
+// start of an iteration.  One workgroup per target agent b, lanes over the mates a != b (ascending; n_agents <= 256: up to
+// four passes).  Mate a: centre p_a = (x, y) of its state, velocity s_a (cos yaw_a, sin yaw_a) in f64, rounded to R; the row
+// holds the centre back-dated by b's clock, fma(-v, dt n, p), so that the rollout's fma(v, dt (n + j), c) lands on p + v dt j.
+// Every write stays inside rows [m_own, n_obs) of b's circle rows and velocity rows: the host sizes each table for n_obs =
+// m_own + n_agents - 1 rows of each (build_fleet_tables); a table that does not have them is left alone.
+// The same lanes hold the squared centre distances: their minimum updates b's clearance record where F.count says that an
+// iteration starts here (one workgroup per agent and stream order: a plain read-modify-write).
+template <typename R> struct alignas(16) FleetRow { R a, b, c, d; };
+template <typename R>
+__global__ __launch_bounds__(64) void k_fleet_rows(const FleetParams F) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const AgentScene sc = F.scenes[b];
+    const int n_obs = sc.n_obs, m_own = n_obs - (F.n_agents - 1);
+    FleetRow<R> *tab = reinterpret_cast<FleetRow<R> *>(const_cast<void *>(sc.obs));
+    const bool sized = tab != nullptr && m_own >= 0;
+    const R tau = (R)F.dt * (R)obstacle_clock(F.st[b].iter, sc.iter0);
+    const double bx = F.st[b].x0[0], by = F.st[b].x0[1];
+    const R *u = static_cast<const R *>(F.u);
+    double d2 = INFINITY;
+    for (int a = lane; a < F.n_agents; a += 64) {
+        if (a == b) continue;
+        const double *x = F.st[a].x0;
+        const double px = x[0], py = x[1];
+        double sn, cs;
+        mf::sincos_(x[2], sn, cs);
+        const double sp = F.model == MODEL_RACE ? x[3] : mf::clamp((double)u[(size_t)a * 2 * F.T], F.umax0);
+        const R vx = (R)(sp * cs), vy = (R)(sp * sn);
+        const int row = m_own + (a < b ? a : a - 1);
+        if (sized) {
+            tab[row] = FleetRow<R>{fma_(-vx, tau, (R)px), fma_(-vy, tau, (R)py), (R)F.thr2, R(0)};
+            tab[n_obs + row] = FleetRow<R>{vx, vy, R(0), R(0)};
+        }
+        const double dx = px - bx, dy = py - by;
+        d2 = fmin(d2, dx * dx + dy * dy);
+    }
+    d2 = wv::reduce<wv::OpMin>(d2);
+    if (F.count && lane == 0) {
+        FleetClear *q = F.clear + b;
+        const double d = sqrt(d2);
+        q->min_dist = fmin(q->min_dist, d);
+        if (d < F.contact) q->contact_iters += 1;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
@@ -2532,6 +2577,9 @@ void launch_eval_at(const KParams<R> &P, int what, const R *x, const int *idx, c
     if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
     else hipLaunchKernelGGL((k_eval_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
 }
+template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s) {
+    hipLaunchKernelGGL(k_fleet_rows<R>, dim3(F.n_agents), dim3(64), 0, s, F);
+}
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s) {
     hipLaunchKernelGGL(k_eval_filter<R>, dim3(1), dim3(256), sizeof(R) * 2 * (size_t)(T + W + 2), s, xx, out, T, W, mode);
 }
@@ -2583,6 +2631,7 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
     template void launch_eval_index<R>(const KParams<R> &, const R *, int, int, int, int, int *, int *, hipStream_t); \
     template void launch_eval<R>(const KParams<R> &, int, const R *, const R *, const int *, int, R *, hipStream_t);   \
     template void launch_eval_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
+    template void launch_fleet_rows<R>(const FleetParams &, hipStream_t);                                            \
     template void launch_eval_filter<R>(const R *, R *, int, int, int, hipStream_t);                                 \
     template void launch_set_state_dev<R>(const KParams<R> &, const double *, int, hipStream_t);                     \
     template void launch_viz<R>(const KParams<R> &, const R *, const R *, long long, float *, float *, hipStream_t);

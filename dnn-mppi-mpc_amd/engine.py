@@ -42,8 +42,11 @@ class Engine:
                     field[i] = float(arr[i]) if i < arr.size else 0.0
             else:
                 setattr(c, k, v)
-        if c.obstacle_motion and c.struct_size != C.sizeof(capi.MppiConfig):
+        abi = self.lib.mppi_abi_version()
+        if c.obstacle_motion and abi < 7:
             raise capi.MppiError(capi.ERR_UNSUPPORTED, "obstacle_motion needs a library of ABI version 7 or later")
+        if c.fleet_radius != 0 and abi < 8:
+            raise capi.MppiError(capi.ERR_UNSUPPORTED, "fleet_radius needs a library of ABI version 8 or later")
         self.cfg = c
         self.K, self.T = int(c.K), int(c.T)
         self.nx = 4 if c.model == capi.MODEL_RACECAR else 3
@@ -100,6 +103,27 @@ class Engine:
             self._ck(self.lib.mppi_set_obstacles(self._h, _dp(c), c.shape[0]))
         else:
             self._ck(self.lib.mppi_set_agent_obstacles(self._h, int(agent), _dp(c), c.shape[0]))
+
+    def agent_circles(self, agent=0):
+        """(circles[m, 3], velocities[m, 2]) that ``agent``'s next iteration tests: its own set, then -- on a handle created
+        with ``fleet_radius > 0`` -- one circle per mate in ascending agent order; centres as of rollout step 0 of the current
+        obstacle clock, r the radius (mppi_get_agent_circles)."""
+        m = C.c_int32()
+        rc = self.lib.mppi_get_agent_circles(self._h, int(agent), None, None, 0, C.byref(m))
+        if rc != capi.ERR_SHAPE:  # (cap = 0 holds no circle: MPPI_ERR_SHAPE with m written, or m = 0)
+            self._ck(rc)
+        c, v = np.empty((m.value, 3)), np.empty((m.value, 2))
+        if m.value:
+            self._ck(self.lib.mppi_get_agent_circles(self._h, int(agent), _dp(c), _dp(v), m.value, C.byref(m)))
+        return c, v
+
+    def fleet_clearance(self, reset=False):
+        """(min_dist[n_agents], contact_iters[n_agents]) over the iterations run since the handle was made or the last call
+        with ``reset=True``: the smallest centre distance of every agent to any mate at the start of an iteration (inf: none
+        ran), and how many iterations started closer than ``2 * fleet_radius`` (mppi_get_fleet_clearance)."""
+        d, n = np.empty(self.n_agents), np.zeros(self.n_agents, dtype=np.int64)
+        self._ck(self.lib.mppi_get_fleet_clearance(self._h, _dp(d), n.ctypes.data_as(C.POINTER(C.c_int64)), int(bool(reset))))
+        return d, n
 
     def agent_status(self):
         """(idx[n_agents], path_end[n_agents]): every agent's waypoint index and whether its last x0 call found the end of

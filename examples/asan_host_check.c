@@ -1,6 +1,7 @@
 /* Host-side check of libmppi_hip.so under AddressSanitizer (make -C dnn-mppi-mpc_amd/csrc asan_check; no GPU needed):
  * the entry points that run on the host before any device work -- argument validation, error strings, create on a box
  * without a device -- are driven with good and bad arguments; ASan reports any out-of-bounds access or leak. */
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -46,6 +47,35 @@ int main(void) {
     c.obstacle_motion = 2;
     EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG);
     c.model = MPPI_MODEL_DIFFDRIVE;
+    /* fleet avoidance: likewise refused before any device work (obstacle_model is MPPI_OBSTACLE_CIRCLE here) */
+    c.obstacle_motion = 1;
+    c.waypoint_mode = MPPI_WAYPOINT_FROZEN;
+    c.n_agents = 3;
+    c.fleet_radius = -0.5;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG && strstr(mppi_last_error(NULL), "fleet_radius") != NULL);
+    c.fleet_radius = NAN;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG);
+    c.fleet_radius = INFINITY;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG);
+    c.fleet_radius = 0.4;
+    c.n_agents = 1;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG && strstr(mppi_last_error(NULL), "n_agents >= 2") != NULL);
+    c.n_agents = 3;
+    c.obstacle_motion = 0;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG && strstr(mppi_last_error(NULL), "obstacle_motion = 1") != NULL);
+    c.obstacle_motion = 1;
+    c.n_agents = 257;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_UNSUPPORTED && strstr(mppi_last_error(NULL), "256") != NULL);
+    c.n_agents = 0;
+    c.fleet_radius = 0.0;
+    c.waypoint_mode = MPPI_WAYPOINT_SEQUENTIAL;
+    {   /* the two entry points that came with it refuse a NULL handle before anything is read or written */
+        int32_t m = -7;
+        double d = -1.0;
+        int64_t n = -1;
+        EXPECT(mppi_get_agent_circles(NULL, 0, &d, &d, 1, &m) == MPPI_ERR_BAD_ARG && m == -7);
+        EXPECT(mppi_get_fleet_clearance(NULL, &d, &n, 1) == MPPI_ERR_BAD_ARG && n == -1);
+    }
     c.obstacle_model = MPPI_OBSTACLE_NONE;
     c.obstacle_motion = 0;
     {   /* and the setters refuse a NULL handle before anything is read */

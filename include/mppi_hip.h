@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MPPI_ABI_VERSION 7
+#define MPPI_ABI_VERSION 8
 
 typedef enum {
     MPPI_OK = 0,
@@ -158,6 +158,36 @@ typedef struct {
      * Needs an obstacle model (MPPI_OBSTACLE_NONE: MPPI_ERR_BAD_ARG); MPPI_MODEL_DIFFDRIVE_MLP: MPPI_ERR_UNSUPPORTED. */
     int32_t obstacle_motion;
     int32_t reserved0;
+    /* Fleet avoidance.  0: off (zero-initialised configs: as before).  > 0: every agent of the handle sees every other agent
+     * (its "mates") as a moving circle of this radius, written on the device at the start of every iteration -- no host round
+     * trip, no re-upload.  Needs n_agents >= 2 and obstacle_motion = 1 (else MPPI_ERR_BAD_ARG), and with obstacle_motion an
+     * obstacle model, an analytic dynamics model, T <= 128 and K <= 8192; n_agents <= 256 (more: MPPI_ERR_UNSUPPORTED);
+     * negative or non-finite: MPPI_ERR_BAD_ARG.  All of it is refused before the device is looked for.
+     * THE MATE ROWS.  At the start of every iteration mppi_run_closed_loop runs, before that iteration's rollout launch, agent
+     * b's obstacle table is its own circles (mppi_set_obstacles[_moving] / mppi_set_agent_obstacles[_moving], unchanged, in
+     * their order) followed by one circle per mate a = 0 .. n_agents - 1, a != b, ascending: n_obs = m_b + n_agents - 1.  Mate a:
+     *   centre     p_a = (x, y) of a's state at the start of the iteration;
+     *   threshold  packed as a circle of radius fleet_radius is: (0.5 safety_margin + fleet_radius)^2 for MPPI_OBSTACLE_CIRCLE,
+     *              fleet_radius^2 for MPPI_OBSTACLE_OUTLINE;
+     *   velocity   v_a = s_a (cos yaw_a, sin yaw_a); diff-drive: s_a = component 0 of row 0 of a's nominal sequence as it
+     *              stands at the start of the iteration (what mppi_get_u_prev returns for a), clamped to +-u_max[0]; race car:
+     *              s_a = the state's v (x[3]);
+     *   prediction the state b reaches after j rollout steps is tested against p_a + v_a (delta_t j), j as for obstacle_motion
+     *              (1 .. T stage calls, T terminal call): constant velocity from NOW, not from an upload time.
+     * p_a, s_a, cos and sin are evaluated in f64 (the state is stored as doubles, u in the handle's precision) and the results
+     * rounded to the handle's precision.  A table has one clock -- iter0, the upload time of b's own set -- so the mate row is
+     * stored back-dated: with n = iteration_b - iter0_b it holds c = fma(-v, delta_t n, p), and the test's
+     * fma(v, delta_t (n + j), c) lands on p + v delta_t j up to the rounding documented for moving circles above (an f32 handle:
+     * half an ulp of |v| delta_t n twice; fresh own circles, even an empty set, re-base iter0).
+     * b's own circles are priced exactly as on a handle without fleet_radius: own rows, iter0 and the rollout kernel are the
+     * same.  Every agent of a fleet handle owns its table (m_b + n_agents - 1 circle rows and as many velocity rows), also
+     * where the shared setters gave all agents the same circles: the host writes the own part at a setter, the device the mate
+     * part every iteration (k_fleet_rows: one launch in front of the rollout launch, inside a captured graph and inside the
+     * first timing bracket of mppi_last_kernel_ms; counted by mppi_get_counters under neither launch class).
+     * mppi_eval_is_collided[_at] and mppi_eval_cost see agent 0's scene, its mate rows as of the current states included: the
+     * library refreshes the rows before such a call.  mppi_set_state, mppi_set_u_prev and mppi_set_iteration need nothing
+     * special: the rows are a pure function of states, nominal controls and clocks, made afresh at the start of an iteration. */
+    double fleet_radius;
 } mppi_config;
 
 /* per-iteration diagnostics (the reference only prints) */
@@ -413,6 +443,18 @@ int mppi_eval_is_collided(mppi_handle *h, const double *x, int32_t n, double *ou
  * int32_t[n]; see mppi_config.obstacle_motion: steps[i] = j of the rollout).  mppi_eval_is_collided and mppi_eval_cost price
  * at step 0 of the current clock.  On a handle without obstacle motion the steps change nothing. */
 int mppi_eval_is_collided_at(mppi_handle *h, const double *x, int32_t n, const int32_t *steps, double *out);
+/* The circles agent `agent`'s next iteration will test, own set first, then its mates: host xyr_out [cap][3] = centre as of
+ * rollout step 0 of the current clock and the RADIUS r (threshold unpacked), vel_out [cap][2]; *m_out = the number the agent
+ * has (written even when cap is too small: MPPI_ERR_SHAPE then).  Any handle with an obstacle model (none: MPPI_ERR_STATE;
+ * agent outside [0, n_agents): MPPI_ERR_BAD_ARG); what a planner's visualisation draws, and what the tests read.  The values
+ * are the table's own, in the handle's precision: centre = fma(v, delta_t n, c) as the kernels form it at j = 0. */
+int mppi_get_agent_circles(mppi_handle *h, int32_t agent, double *xyr_out, double *vel_out, int32_t cap, int32_t *m_out);
+/* Fleet handles (else MPPI_ERR_STATE): per agent, over the iterations run since mppi_create or the last call with reset != 0,
+ * min_dist[a] = the smallest centre distance to any mate among the states those iterations started from (f64; +inf: none ran),
+ * contact_iters[a] = how many of them started with that distance < 2 * fleet_radius.  Host arrays [n_agents], either nullable.
+ * (A closed-loop call of many iterations returns only the last state: this says whether two robots touched in between.  The
+ * refreshes in front of mppi_eval_* and mppi_get_agent_circles are not counted.) */
+int mppi_get_fleet_clearance(mppi_handle *h, double *min_dist, int64_t *contact_iters, int32_t reset);
 int mppi_eval_nearest_waypoint(mppi_handle *h, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
                                int32_t *idx_out);
 int mppi_eval_cost(mppi_handle *h, int32_t terminal, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
@@ -423,7 +465,7 @@ int mppi_eval_weights(mppi_handle *h, const double *S, int32_t n, double *w);
 /* Kernel durations by HIP events on the launch stream.  While enabled, every launch group of every
  * iteration is bracketed by an event pair, plus one empty pair that calibrates the cost of the
  * bracketing itself.  mppi_last_kernel_ms: averages (ms) over the window since timing was enabled,
- * calibration subtracted: out[0] rollout+cost(+fused softmin partial), out[1] separate reduce / merge
+ * calibration subtracted: out[0] rollout+cost(+fused softmin partial; a fleet handle: + its k_fleet_rows launch), out[1] separate reduce / merge
  * launches (0 when fused), out[2] finalise, out[3] the empty-pair calibration itself. */
 int mppi_last_kernel_ms(mppi_handle *h, float *out4);
 int mppi_enable_timing(mppi_handle *h, int32_t on);
