@@ -24,6 +24,7 @@ FILTER_DIFFDRIVE, FILTER_RACECAR, FILTER_NONE, FILTER_TORCH = 0, 1, 2, 3
 OBSTACLE_NONE, OBSTACLE_CIRCLE, OBSTACLE_OUTLINE = 0, 1, 2
 OK, ERR_BAD_ARG, ERR_SHAPE, ERR_NO_DEVICE, ERR_HIP, ERR_PATH_END, ERR_UNSUPPORTED, ERR_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 ERR_COMM = -8
+FLEET_VELOCITY, FLEET_PLAN = 0, 1  # mppi_set_fleet_prediction
 LAYOUT_FUSED, LAYOUT_DUAL, LAYOUT_PAIR, LAYOUT_TRI, LAYOUT_KIND, LAYOUT_TWICE = 0, 1, 2, 3, 3, 4  # mppi_get_rollout_layout (KIND: mask)
 
 
@@ -138,6 +139,8 @@ PROTOTYPES = {
     "mppi_eval_is_collided_at": (C.c_int, [_H, _D, C.c_int32, C.POINTER(C.c_int32), _D]),
     "mppi_get_agent_circles": (C.c_int, [_H, C.c_int32, _D, _D, C.c_int32, C.POINTER(C.c_int32)]),
     "mppi_get_fleet_clearance": (C.c_int, [_H, _D, C.POINTER(C.c_int64), C.c_int32]),
+    "mppi_set_fleet_prediction": (C.c_int, [_H, C.c_int32]),
+    "mppi_get_fleet_plans": (C.c_int, [_H, _D]),
     "mppi_eval_nearest_waypoint": (C.c_int, [_H, _D, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "mppi_eval_cost": (C.c_int, [_H, C.c_int32, _D, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _D, C.POINTER(C.c_int32)]),
     "mppi_eval_moving_average": (C.c_int, [_H, _D, _D]),

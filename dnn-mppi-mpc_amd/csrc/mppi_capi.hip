@@ -139,6 +139,10 @@ struct mppi_handle {
     std::vector<double> obs_host;  // the shared set's packed rows, as OwnScene::obs_host
     std::vector<DevBuf<void>> fleet_tab;
     DevBuf<FleetClear> d_clear;
+    // MPPI_FLEET_PLAN (mppi_set_fleet_prediction): the tables hold the own rows alone, k_fleet_plan leads the slots in
+    // k_fleet_rows' place and writes d_plans, [B][T + 1][2] in the handle's precision, which the plan rollout forms read
+    bool fleet_plan = false;
+    DevBuf<void> d_plans;
     DevBuf<int> d_pout;
     DevBuf<void> d_partials;        // block records in the handle's precision
     DevBuf<double> d_w, d_trace;
@@ -223,11 +227,13 @@ static AgentScene scene_of(const mppi_handle *h, int a) {
         if (o.has_obs) sc.obs = o.d_obs, sc.n_obs = o.n_obs, sc.iter0 = o.obs_iter0;
     }
     if (h->cfg.obstacle_model == MPPI_OBSTACLE_NONE) sc.n_obs = 0;
-    if (h->fleet) sc.obs = h->fleet_tab[a], sc.n_obs += h->B - 1;  // (its own rows first, then one per mate: build_fleet_tables)
+    // (its own rows first, then one per mate: build_fleet_tables; plan mode: the own rows alone, the mates come from d_plans)
+    if (h->fleet) sc.obs = h->fleet_tab[a], sc.n_obs += h->fleet_plan ? 0 : h->B - 1;
     return sc;
 }
 // some agent has obstacles: the obstacle instantiations serve and the records carry collision counts
 static bool any_obstacles(const mppi_handle *h) {
+    if (h->fleet) return true;  // (the mates: rows of every table, or -- plan mode, where an agent may have n_obs = 0 -- their plans)
     for (int a = 0; a < h->B; ++a)
         if (scene_of(h, a).n_obs > 0) return true;
     return false;
@@ -468,7 +474,7 @@ static int build_fleet_tables(mppi_handle *h, int only) {
     for (int a = 0; h->fleet && a < h->B; ++a) {
         if (only >= 0 && a != only) continue;
         const mppi_handle::OwnScene &o = h->own[a];
-        const int m = o.has_obs ? o.n_obs : h->n_obs, n = m + h->B - 1;
+        const int m = o.has_obs ? o.n_obs : h->n_obs, n = m + (h->fleet_plan ? 0 : h->B - 1);
         const std::vector<double> &src = o.has_obs ? o.obs_host : h->obs_host;
         std::vector<double> rows((size_t)8 * n, 0.0);
         if (src.size() == (size_t)8 * m) {
@@ -478,6 +484,7 @@ static int build_fleet_tables(mppi_handle *h, int only) {
             FAIL(h, MPPI_ERR_STATE, "fleet table of agent %d: the host copy of its %d circles is missing", a, m);
         }
         HIPCHECK(h, h->fleet_tab[a].reset());
+        if (n == 0) continue;  // (plan mode, no own circles: no table, n_obs = 0)
         HIPCHECK(h, h->fleet_tab[a].alloc(rsz(h) * rows.size()));
         if (int rc = upload_real(h, h->fleet_tab[a], rows.data(), rows.size())) return rc;
     }
@@ -1060,6 +1067,10 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.hyp = index_can_move(h);
     P.lb_seq = 0;
     P.hyp_slots = h->d_hyp_slots;
+    if (h->fleet_plan) {  // (the threshold as make_fleet packs it for a mate row)
+        const double thr = c.obstacle_model == MPPI_OBSTACLE_CIRCLE ? 0.5 * c.safety_margin + c.fleet_radius : c.fleet_radius;
+        set_fleet_plan<R>(P, h->d_plans, (R)(thr * thr));
+    }
     return P;
 }
 
@@ -1083,6 +1094,12 @@ static FleetParams make_fleet(const mppi_handle *h, int count) {
     const double thr = c.obstacle_model == MPPI_OBSTACLE_CIRCLE ? 0.5 * c.safety_margin + c.fleet_radius : c.fleet_radius;
     F.thr2 = thr * thr;
     F.contact = 2.0 * c.fleet_radius;
+    if (h->fleet_plan) {
+        F.plans = h->d_plans;
+        F.clamp_rollout = c.clamp_rollout;
+        F.umax1 = c.u_max[1];
+        F.wheel_base = c.wheel_base;
+    }
     return F;
 }
 
@@ -1112,7 +1129,7 @@ static FinalizeParams make_finalize(const mppi_handle *h, int plant, const void 
     F.n_ref = sc0.n_ref;
     F.window = c.search_window;
     F.is_f64 = h->f64;
-    F.count_hits = any_obstacles(h);
+    F.count_hits = h->fleet_plan ? 2 : any_obstacles(h);  // (2: every agent counts, also one without rows of its own -- its mates' plans)
     F.beta = record_beta(h);
     F.dt = c.delta_t;
     F.wheel_base = c.wheel_base;
@@ -1211,7 +1228,7 @@ static SlotPlan plan_slot(const mppi_handle *h, const KParams<R> &P, FinalizePar
     return sp;
 }
 
-// the plan's launches up to its reader: [rollout] [reduce / merge].  A fleet handle: k_fleet_rows leads the slot, inside the
+// the plan's launches up to its reader: [rollout] [reduce / merge].  A fleet handle: k_fleet_rows (plan mode: k_fleet_plan) leads the slot, inside the
 // rollout's event pair (mppi_last_kernel_ms out[0]) and outside the launch counters (mppi_get_counters)
 template <typename R> static void launch_records(mppi_handle *h, const SlotPlan &sp, const KParams<R> &P, hipStream_t s, bool tm) {
     if (tm) hipEventRecord(next_event(h), s);
@@ -2214,7 +2231,8 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
             eval_transition_mlp(h, P, dx, dv, n, dout);
         else if (at) {
             if (h->fleet) launch_fleet_rows<R>(make_fleet(h, 0), nullptr);  // agent 0's mates as of the current states
-            launch_eval_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+            if (h->fleet_plan) launch_eval_plan_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+            else launch_eval_at<R>(P, what, dx, di, ds, n, dout, nullptr);
         }
         else
             launch_eval<R>(P, what, dx, dv, di, n, dout, nullptr);
@@ -2256,6 +2274,8 @@ extern "C" int mppi_eval_is_collided_at(mppi_handle *h, const double *x, int32_t
     if (h && !steps) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_is_collided_at: steps is null");
     for (int i = 0; h && steps && i < n; ++i)
         if (steps[i] < 0) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_is_collided_at: steps[%d] = %d is negative (steps count ahead of the clock)", i, steps[i]);
+    for (int i = 0; h && h->fleet_plan && steps && i < n; ++i)
+        if (steps[i] > h->cfg.T) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_is_collided_at: steps[%d] = %d lies beyond the mates' plans (T = %d points ahead)", i, steps[i], h->cfg.T);
     return eval_entry(h, "mppi_eval_is_collided_at", EVAL_COLLIDED, x, nullptr, n, nullptr, 0, out, nullptr, steps);
 }
 
@@ -2270,7 +2290,7 @@ static int agent_circles_impl(mppi_handle *h, int agent, double *xyr_out, double
     if (!sc.obs) FAIL(h, MPPI_ERR_STATE, "mppi_get_agent_circles: obstacles not uploaded");
     const bool moving = h->cfg.obstacle_motion != 0;
     HIPCHECK(h, hipDeviceSynchronize());
-    if (h->fleet) {
+    if (h->fleet && !h->fleet_plan) {  // (plan mode: the table holds the own rows alone)
         launch_fleet_rows<R>(make_fleet(h, 0), nullptr);
         HIPCHECK(h, hipDeviceSynchronize());
     }
@@ -2318,6 +2338,39 @@ extern "C" int mppi_get_fleet_clearance(mppi_handle *h, double *min_dist, int64_
         HIPCHECK(h, hipMemcpy(h->d_clear, rec.data(), sizeof(FleetClear) * rec.size(), hipMemcpyHostToDevice));
     }
     return MPPI_OK;
+}
+
+extern "C" int mppi_set_fleet_prediction(mppi_handle *h, int32_t mode) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (mode != MPPI_FLEET_VELOCITY && mode != MPPI_FLEET_PLAN)
+        FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_fleet_prediction: mode %d is neither MPPI_FLEET_VELOCITY nor MPPI_FLEET_PLAN", mode);
+    if (!h->fleet)
+        FAIL(h, MPPI_ERR_STATE, "mppi_set_fleet_prediction: the handle was created with fleet_radius = 0 (no fleet avoidance)");
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    if (mode == MPPI_FLEET_PLAN && !h->d_plans) {
+        const size_t bytes = rsz(h) * 2 * (size_t)(h->cfg.T + 1) * (size_t)h->B;
+        HIPCHECK(h, h->d_plans.alloc(bytes));
+        HIPCHECK(h, hipMemset(h->d_plans, 0, bytes));
+    }
+    h->fleet_plan = mode == MPPI_FLEET_PLAN;
+    h->dev_loop_primed = false;
+    drop_graph(h);
+    if (int rc = build_fleet_tables(h, -1)) return rc;  // (the mate rows come or go; iter0 and the own rows stay)
+    return upload_scenes(h);
+}
+
+extern "C" int mppi_get_fleet_plans(mppi_handle *h, double *xy) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (!xy) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_get_fleet_plans: xy is null");
+    if (!h->fleet_plan)
+        FAIL(h, MPPI_ERR_STATE, "mppi_get_fleet_plans: the handle predicts its mates at constant velocity (mppi_set_fleet_prediction: MPPI_FLEET_PLAN)");
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    with_real(h, [&](auto r) { launch_fleet_rows<decltype(r)>(make_fleet(h, 0), nullptr); return 0; });
+    HIPCHECK(h, hipGetLastError());
+    HIPCHECK(h, hipDeviceSynchronize());
+    return download_real(h, xy, h->d_plans, 2 * (size_t)(h->cfg.T + 1) * (size_t)h->B);
 }
 
 extern "C" int mppi_eval_nearest_waypoint(mppi_handle *h, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,

@@ -251,6 +251,42 @@ __device__ __forceinline__ bool collided(const KParams<R> &P, R x, R y, R yaw, c
     return hit;
 }
 
+// Fleet plans (MPPI_FLEET_PLAN): the mates of agent `self` at point j of their plans (j in [0, P.T]: the caller's business)
+// against this lane's state.  The centres differ per lane -- lane l of a rollout owns its own step -- so they cannot come out
+// of a lane table by v_readlane: every lane reads point j of mate a, one 8-byte (f32) element, consecutive lanes consecutive
+// addresses -- from `table`, the handle's table in memory or the workgroup's copy of it in LDS (conflict-free `ds_read_b64`; the
+// caller makes one call per address space, so that each compiles to its own load).  OBS_CIRCLE: the circle test of collided(); OBS_OUTLINE: its folded outline form, for both models.  A function of
+// its own beside collided(), whose text and callers stay as they are.
+template <typename R>
+__device__ __forceinline__ bool mates_collided(const KParams<R> &P, const PlanPoint<R> *table, R x, R y, R yaw, int self, int j) {
+    const PlanPoint<R> *pt = table + j;
+    const R thr2 = fleet_plan_thr2(P);
+    const size_t stride = (size_t)P.T + 1;
+    bool hit = false;
+    if (P.obstacle_model == OBS_CIRCLE) {
+        for (int a = 0; a < P.n_agents; ++a) {
+            if (a == self) continue;
+            const PlanPoint<R> c = pt[a * stride];
+            const R dx = x - c.x, dy = y - c.y;
+            hit |= dx * dx + dy * dy < thr2;
+        }
+        return hit;
+    }
+    R sn, cs;
+    mf::sincos_(yaw, sn, cs);
+    const R ha = P.shape_x[3], hb = P.shape_y[3];
+    for (int a = 0; a < P.n_agents; ++a) {
+        if (a == self) continue;
+        const PlanPoint<R> c = pt[a * stride];
+        const R dx = c.x - x, dy = c.y - y;
+        const R bx = fabs(dx * cs + dy * sn), by = fabs(dy * cs - dx * sn);
+        const R ex = bx - ha, ey = by - hb;
+        const R ex2 = ex * ex, ey2 = ey * ey;
+        hit |= fmin(fmin(ex2 + by * by, ex2 + ey2), bx * bx + ey2) < thr2;
+    }
+    return hit;
+}
+
 // weighted squared tracking error against waypoint i (`_compute_cost` :222-236, `_c` mppi_race_car.py:137-146)
 template <typename R, int MODEL>
 __device__ __forceinline__ R tracking_cost_row(const KParams<R> &P, const R (&w)[4], bool wrap, const R *r, R x, R y, R yaw,

@@ -169,8 +169,35 @@ template <typename R> struct KParams {
     // moving obstacles: the value of DevState::iter when the set (agent 0's here, every agent's in the table) was uploaded.  A
     // rollout step j steps ahead tests against c + v dt (iter - iter0 + j).  (It took a padding word: the layout stays.)
     long long iter0;
+    // Fleet plans (mppi_set_fleet_prediction, MPPI_FLEET_PLAN): word 0 the address of the plan table R[n_agents][T + 1][2], word 1
+    // the mates' squared threshold as an R in its low bytes (fleet_plan_table / fleet_plan_thr2 below); both 0 otherwise.  (The
+    // two words were padding: the layout stays.)
     long long pad_scenes[2];
 };
+// One point of a plan: agent a's position after j rollout steps of its nominal controls is row a (T + 1) + j of the table
+template <typename R> struct alignas(2 * sizeof(R)) PlanPoint { R x, y; };
+template <typename R> __host__ __device__ inline const PlanPoint<R> *fleet_plan_table(const KParams<R> &P) {
+    return reinterpret_cast<const PlanPoint<R> *>(P.pad_scenes[0]);
+}
+template <typename R> __host__ __device__ inline R fleet_plan_thr2(const KParams<R> &P) {
+    R v;
+    __builtin_memcpy(&v, &P.pad_scenes[1], sizeof(R));
+    return v;
+}
+// The plan forms stage the whole table into dynamic LDS where it fits beside their own LDS within the 64 KB a workgroup gets
+// without raising a limit: up to 40000 bytes beside the f32 forms' 18.6 / 24.8 KB, 16384 beside the f64 forms' 37.2 / 47.5 KB.
+// (Every form runs ONE workgroup of 16 waves per CU -- occupancy 4 - 7 waves per SIMD -- so no size lowers that; staging
+// costs the forms no register, scratch or occupancy: DESIGN 3.10.)  Larger tables are read from memory.  One function for the
+// planner, which sizes the launch's dynamic LDS by it, and the kernel, which decides by it where it reads.
+template <typename R> __host__ __device__ inline int fleet_plan_lds_bytes(int n_agents, int T) {
+    const long long bytes = (long long)n_agents * (T + 1) * 2 * (long long)sizeof(R);
+    return bytes <= (sizeof(R) == 4 ? 40000 : 16384) ? (int)bytes : 0;
+}
+template <typename R> inline void set_fleet_plan(KParams<R> &P, const void *table, R thr2) {
+    P.pad_scenes[0] = (long long)reinterpret_cast<uintptr_t>(table);
+    P.pad_scenes[1] = 0;
+    __builtin_memcpy(&P.pad_scenes[1], &thr2, sizeof(R));
+}
 // (lb_timeout took the place of a padding word: the layout the kernels' argument loads were tuned for stays as it was)
 static_assert(sizeof(KParams<float>) == 424 && sizeof(KParams<double>) == 576, "KParams layout");
 static_assert(offsetof(KParams<float>, hyp) == 376 && offsetof(KParams<double>, hyp) == 528, "KParams layout");
@@ -181,7 +208,8 @@ struct FinalizeParams {
     int T, K, n_part, pad2;
     int filter_mode, filter_window, clamp_u, raise_at_path_end;
     int model, sequential, plant, n_ref;
-    int window, is_f64, count_hits, pad1;  // count_hits: the block records' heads carry collision counts (a handle with obstacles)
+    int window, is_f64, count_hits, pad1;  // count_hits: the block records' heads carry collision counts (a handle with obstacles;
+                                           // batched: an agent with n_obs > 0, or -- 2, fleet plans -- every agent)
     double beta, dt, wheel_base, umax0, umax1;
     const void *partials;    // [n_part] records: the slot plan's, or the caller's ABI records [n_part][partial_len], n_part <= 256
     const void *heads;       // compact heads of `partials` (KParams::heads); unused for the ABI layout
@@ -391,8 +419,18 @@ struct FleetParams {
     double dt, umax0;          // dt: as KParams::dt (already rounded to the handle's precision)
     double thr2;               // a mate's packed threshold, as set_circles packs a circle of radius fleet_radius
     double contact;            // 2 * fleet_radius
+    // MPPI_FLEET_PLAN (appended: k_fleet_rows reads none of it).  plans != null: k_fleet_plan takes the launch's place and writes
+    // every agent's plan -- its nominal controls rolled out from its state, clamped where the rollout clamps -- instead of rows
+    void *plans;               // [n_agents][T + 1][2] in the handle's precision, or null (MPPI_FLEET_VELOCITY)
+    int clamp_rollout, pad_plan;
+    double umax1, wheel_base;
 };
+// the launch at the front of a fleet handle's slot: k_fleet_rows, or k_fleet_plan where F.plans is set
 template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s);
+// launch_eval_at for a handle in plan mode: agent 0's own circles at steps[i] of the clock and its mates at point steps[i] of
+// their plans (P carries the table: set_fleet_plan; steps inside [0, T])
+template <typename R>
+void launch_eval_plan_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s);
 void launch_eval_weights(const double *S, int n, double beta, double *w, hipStream_t s);
 template <typename R> void launch_set_state_dev(const KParams<R> &P, const double *x_dev, int nx, hipStream_t s);

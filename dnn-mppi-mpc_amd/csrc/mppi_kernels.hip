@@ -104,7 +104,9 @@ template <typename R> struct RolloutMotion<R, true> {
         clock = obstacle_clock(sv.iter, P.iter0);
     }
 };
-template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVING = false> struct Rollout : RolloutMotion<R, MOVING> {
+// PLANS (MPPI_FLEET_PLAN, with MOVING): beside its own moving circles the agent tests its mates at the point of their plans
+// that its step owns (mates_collided, mppi_device.h); the table and the threshold travel in KParams.
+template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVING = false, bool PLANS = false> struct Rollout : RolloutMotion<R, MOVING> {
     __device__ __forceinline__ bool use_philox() const { return PLAIN || P.use_philox; }
     __device__ __forceinline__ bool clamp_rollout() const { return PLAIN || P.clamp_rollout; }
     __device__ __forceinline__ bool wrap_stage() const { return !PLAIN && P.wrap_stage; }
@@ -142,7 +144,18 @@ template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVIN
     // collision test of this lane's state after step 64 ch + lane.  MOVING: that state lies j = 64 ch + lane + 1 steps ahead;
     // the terminal call prices the same state, and only lane_last's terminal value is read: j = T there
     __device__ __forceinline__ bool collided_at(int ch, R x, R y, R yaw) const {
-        if constexpr (MOVING) {
+        if constexpr (PLANS) {  // (a lane beyond the horizon reads point T: its cost is never read)
+            static_assert(MOVING, "the plan forms extend the moving ones");
+            const ObsLanesMoving<R> tab{obs.x, obs.y, obs.r2, this->vx, this->vy};
+            const int j = 64 * ch + lane + 1;
+            bool hit = collided<MODEL == MODEL_RACE, true>(P, x, y, yaw, tab, false, R(0), R(1), obstacle_time(P, this->clock + j));
+            const int jp = j < P.T ? j : P.T;
+            // (the workgroup's copy in dynamic LDS where the launch was sized for it -- k_rollout_fused staged it --, else memory)
+            extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
+            if (fleet_plan_lds_bytes<R>(P.n_agents, P.T) > 0) hit |= mates_collided(P, reinterpret_cast<const PlanPoint<R> *>(dyn_lds), x, y, yaw, agent, jp);
+            else hit |= mates_collided(P, fleet_plan_table(P), x, y, yaw, agent, jp);
+            return hit;
+        } else if constexpr (MOVING) {
             const ObsLanesMoving<R> tab{obs.x, obs.y, obs.r2, this->vx, this->vy};
             return collided<MODEL == MODEL_RACE, true>(P, x, y, yaw, tab, false, R(0), R(1), obstacle_time(P, this->clock + 64 * ch + lane + 1));
         } else {
@@ -582,14 +595,16 @@ __device__ __forceinline__ void per_rollout_thread(const KParams<R> &P, int c, c
 
 // MULTI: several agents per launch, one row of workgroups (blockIdx.y) each; a single agent compiles to the
 // offset-free code (the offsets cost config 2 half a microsecond per iteration when they were unconditional)
-// SPEC: 0 general, 1 no obstacles, 2 no obstacles + the PLAIN switches (see Rollout), 3 general with moving obstacles
+// SPEC: 0 general, 1 no obstacles, 2 no obstacles + the PLAIN switches (see Rollout), 3 general with moving obstacles, 4 the
+// same with the mates' plans (MULTI only: a mate is another agent of the launch)
 // HYPK: the instantiation that can resolve the sequential index in one launch (fused_lookback).  A separate instantiation,
 // picked by the host while the waypoint index can still move (KParams::hyp): carrying that code costs the lean kernel
 // 0.17 us per launch in registers and LDS (A/B on one box), and at the end of the path nothing moves any more.
 template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK = false>
 __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevState *st_pre, KParams<R> P,
                                                                     R *__restrict__ partials) {
-    constexpr bool OBS = SPEC == 0 || SPEC == 3, PLAIN = SPEC == 2, MOVING = SPEC == 3;
+    constexpr bool OBS = SPEC == 0 || SPEC == 3 || SPEC == 4, PLAIN = SPEC == 2, MOVING = SPEC == 3 || SPEC == 4, PLANS = SPEC == 4;
+    static_assert(!PLANS || MULTI, "the mates are the other agents of a batched launch");
     static_assert(!(HYPK && MOVING), "the look-back prices the last state with a collision test of its own: static obstacles only");
     const int agent = MULTI ? (int)blockIdx.y : 0;
     if constexpr (MULTI) agent_scene(P, P.scenes, agent);  // (the agent's view of P: its own path and obstacles, see AgentScene)
@@ -621,6 +636,19 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
     __shared__ int sh_first;
     if (use_win) stage_window(sh_win, P.ref, sv.c, wlen0, (int)threadIdx.x, (int)blockDim.x);
     if (seq_search && threadIdx.x == 0) sh_first = NO_TRIGGER;
+    // PLANS: the plan table into dynamic LDS where the planner sized the launch for it (fleet_plan_lds_bytes: the same decision
+    // on both sides); every point of every agent, so that the index stays that of the table in memory
+    // (Rollout::collided_at reads it; a block of its own, so that the other forms keep their text)
+    if constexpr (PLANS) {
+        extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
+        if (fleet_plan_lds_bytes<R>(P.n_agents, P.T) > 0) {
+            PlanPoint<R> *dst = reinterpret_cast<PlanPoint<R> *>(dyn_lds);
+            const PlanPoint<R> *src = fleet_plan_table(P);
+            const int n_pts = P.n_agents * (P.T + 1);
+            for (int i = threadIdx.x; i < n_pts; i += blockDim.x) dst[i] = src[i];
+            if (!(use_win || seq_search)) __syncthreads();  // (else the barrier below serves)
+        }
+    }
     if (use_win || seq_search) __syncthreads();
     float e0[NCH], e1[NCH];
     R S_k = R(INFINITY);
@@ -641,8 +669,8 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
         const bool ref_lds = P.n_ref <= PR_REF_LDS;
         if (ref_lds)
             for (int i = threadIdx.x; i < P.n_ref; i += blockDim.x) { sh_pref[2 * i] = P.ref[4 * i]; sh_pref[2 * i + 1] = P.ref[4 * i + 1]; }
-        Rollout<R, MODEL, OBS, PLAIN, MOVING> r(P, sv, k, lane, nullptr, obs, agent, mv);
-        typename Rollout<R, MODEL, OBS, PLAIN, MOVING>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
+        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS> r(P, sv, k, lane, nullptr, obs, agent, mv);
+        typename Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
         if (valid) sp = r.dynamics(0, e0[0], e1[0]);
         sh_px[wid][lane] = sp.x;
         sh_py[wid][lane] = sp.y;
@@ -654,7 +682,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
             S_k = r.finish(false);
         }
     } else if (valid) {
-        Rollout<R, MODEL, OBS, PLAIN, MOVING> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
+        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
         r.sh_first = seq_search ? &sh_first : nullptr;
         if (k >= k_start) {
 #pragma unroll
@@ -2028,7 +2056,8 @@ __global__ __launch_bounds__(MERGE_THREADS) void k_finalize(const void *partials
         FinalizeParams Fa = F;
         Fa.ref = sc.ref;
         Fa.n_ref = sc.n_ref;
-        Fa.count_hits = F.count_hits && sc.n_obs > 0;
+        // (count_hits 2 -- fleet plans: the mates are obstacles that stand in no table, so an agent with n_obs = 0 counts too)
+        Fa.count_hits = F.count_hits == 2 || (F.count_hits && sc.n_obs > 0);
         const size_t rec = (size_t)a * F.slots * record_len(T_pre, (int)sizeof(A));
         finalize_body<A, MODE, MERGE_THREADS, NWIN>(reinterpret_cast<const A *>(partials_pre) + rec,
                                                     reinterpret_cast<const A *>(heads_pre) + (size_t)a * F.slots * 4,
@@ -2298,6 +2327,97 @@ __global__ __launch_bounds__(64) void k_fleet_rows(const FleetParams F) {
     }
 }
 
+// Fleet plans (MPPI_FLEET_PLAN): agent a's plan, the positions its nominal controls reach from its state -- point 0 the state's
+// (x, y), point j the position after rows 0 .. j - 1 -- in the rollout's own arithmetic at zero noise for an exploiting sample
+// (Rollout::dynamics / k_viz: the state rounded to R, the rows clamped where the rollout clamps, the wave scans in R).  One
+// workgroup of one wave per agent, lanes over the horizon, the state carried from chunk to chunk of 64 steps.  Every write
+// lands in rows [a (T + 1), (a + 1) (T + 1)) of the table, which the host sizes for n_agents (T + 1) points.
+// The clearance record is k_fleet_rows': lanes over the mates, their squared centre distances, one minimum.
+template <typename R, int MODEL>
+__global__ __launch_bounds__(64) void k_fleet_plan(const FleetParams F) {
+    const int a = blockIdx.x, lane = threadIdx.x;
+    const double *x0 = F.st[a].x0;
+    const R *u = static_cast<const R *>(F.u) + (size_t)a * 2 * F.T;
+    PlanPoint<R> *out = static_cast<PlanPoint<R> *>(F.plans) + (size_t)a * (F.T + 1);
+    const R dt = (R)F.dt, umax0 = (R)F.umax0, umax1 = (R)F.umax1, wheel_base = (R)F.wheel_base;
+    R cx = (R)x0[0], cy = (R)x0[1], cyaw = (R)x0[2], cvel = MODEL == MODEL_RACE ? (R)x0[3] : R(0);
+    if (lane == 0) out[0] = PlanPoint<R>{cx, cy};
+    const int n_chunk = (F.T + 63) >> 6;
+    for (int ch = 0; ch < n_chunk; ++ch) {
+        const int t = ch * 64 + lane;
+        const bool act = t < F.T;
+        R v0 = 0, v1 = 0;
+        if (act) {
+            v0 = u[2 * t];
+            v1 = u[2 * t + 1];
+            if (F.clamp_rollout) {
+                v0 = mf::clamp(v0, umax0);
+                v1 = mf::clamp(v1, umax1);
+            }
+        }
+        R x, y, yaw, vel = 0;
+        if (MODEL == MODEL_DIFF) {
+            yaw = cyaw + wv::scan_incl<wv::OpAdd>(v1 * dt);
+            const R yaw_b = wv::shift_up1(yaw, cyaw);
+            R sn, cs;
+            mf::sincos_(yaw_b, sn, cs);
+            x = cx + wv::scan_incl<wv::OpAdd>(v0 * cs * dt);
+            y = cy + wv::scan_incl<wv::OpAdd>(v0 * sn * dt);
+        } else {
+            vel = cvel + wv::scan_incl<wv::OpAdd>(act ? v1 * dt : R(0));
+            const R vel_b = wv::shift_up1(vel, cvel);
+            yaw = cyaw + wv::scan_incl<wv::OpAdd>(act ? vel_b / wheel_base * mf::tan_(v0) * dt : R(0));
+            const R yaw_b = wv::shift_up1(yaw, cyaw);
+            R sn, cs;
+            mf::sincos_(yaw_b, sn, cs);
+            x = cx + wv::scan_incl<wv::OpAdd>(act ? vel_b * cs * dt : R(0));
+            y = cy + wv::scan_incl<wv::OpAdd>(act ? vel_b * sn * dt : R(0));
+        }
+        cx = wv::read_lane(x, 63); cy = wv::read_lane(y, 63); cyaw = wv::read_lane(yaw, 63);
+        if (MODEL == MODEL_RACE) cvel = wv::read_lane(vel, 63);
+        if (act) out[t + 1] = PlanPoint<R>{x, y};
+    }
+    double d2 = INFINITY;
+    for (int m = lane; m < F.n_agents; m += 64) {
+        if (m == a) continue;
+        const double dx = F.st[m].x0[0] - x0[0], dy = F.st[m].x0[1] - x0[1];
+        d2 = fmin(d2, dx * dx + dy * dy);
+    }
+    d2 = wv::reduce<wv::OpMin>(d2);
+    if (F.count && lane == 0) {
+        FleetClear *q = F.clear + a;
+        const double d = sqrt(d2);
+        q->min_dist = fmin(q->min_dist, d);
+        if (d < F.contact) q->contact_iters += 1;
+    }
+}
+
+// k_eval_at for a handle in plan mode: agent 0's own circles steps[i] rollout steps ahead of its clock, and its mates at point
+// steps[i] of their plans (kept inside [0, T]: the host refuses anything else)
+template <typename R, int MODEL>
+__global__ __launch_bounds__(256) void k_eval_plan_at(const KParams<R> P, int what, const R *__restrict__ x, const int *__restrict__ idx,
+                                                      const int *__restrict__ steps, int n, R *__restrict__ out) {
+    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
+    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
+    const bool act = i < n;
+    R s[4] = {R(0), R(0), R(0), R(0)};
+    if (act)
+        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
+    const int j = act && steps ? steps[i] : 0;
+    const R tau = obstacle_time(P, obstacle_clock(P.st->iter, P.iter0) + j);
+    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
+    hit |= mates_collided(P, fleet_plan_table(P), s[0], s[1], s[2], 0, j < 0 ? 0 : j < P.T ? j : P.T);
+    if (what == EVAL_COLLIDED) {
+        if (act) out[i] = hit ? R(1) : R(0);
+    } else {
+        const bool term = what == EVAL_COST_TERMINAL;
+        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
+                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit);
+        if (act) out[i] = c;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
@@ -2422,8 +2542,11 @@ template <typename R, int MODEL, bool MULTI, int SPW> static KernelLaunch dual_p
     return twice ? dual_entry<R, MODEL, SPW, MULTI, 2, false>() : dual_entry<R, MODEL, SPW, MULTI, 1, false>();
 }
 // k_rollout_fused<R, MODEL, NCH, MULTI, SPEC, HYPK>: SPEC 2 the plain form, 1 no obstacles, 0 everything, 3 everything with
-// moving obstacles (never with the look-back: lookback_serves, mppi_capi.hip)
+// moving obstacles (never with the look-back: lookback_serves, mppi_capi.hip), 4 the same with the mates' plans (batched
+// launches of a handle that carries a plan table)
 template <typename R, int MODEL, int NCH, bool MULTI, bool HYPK> static KernelLaunch fused_plan(int spec) {
+    if constexpr (!HYPK && MULTI)
+        if (spec == 4) return fused_entry<R, MODEL, NCH, true, 4, false>();
     if constexpr (!HYPK)
         if (spec == 3) return fused_entry<R, MODEL, NCH, MULTI, 3, false>();
     return spec == 2   ? fused_entry<R, MODEL, NCH, MULTI, 2, HYPK>()
@@ -2465,7 +2588,8 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
             // (a handle with obstacle motion takes the moving form whatever its set holds at the moment -- none yet, or m = 0:
             // an agent of a batch with no circles of its own then computes what its single-agent handle computes, bit for
             // bit; the forms contract their cost arithmetic differently in the last place)
-            const int spec = P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
+            const bool plans = MULTI && P.obs_motion && fleet_plan_table(P) != nullptr;
+            const int spec = plans ? 4 : P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
             p.lookback = !MULTI && MODEL == MODEL_DIFF && P.hyp && P.T <= 64 && !P.obs_motion;  // (the HYPK form: one agent, diff-drive, one chunk)
             p.k = p.lookback  ? fused_plan<R, MODEL_DIFF, 1, false, true>(spec)
                   : P.T <= 64 ? fused_plan<R, MODEL, 1, MULTI, false>(spec)
@@ -2474,6 +2598,9 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
     }
     p.records = blocks;
     p.k.grid = dim3(blocks, MULTI ? P.n_agents : 1);
+    // (the plan forms: the staged table, or 0 -- the memory path)
+    if (MULTI && P.obs_motion && fleet_plan_table(P) != nullptr && (P.layout & LAYOUT_KIND) == LAYOUT_FUSED)
+        p.k.lds = (size_t)fleet_plan_lds_bytes<R>(P.n_agents, P.T);
     return p;
 }
 
@@ -2577,8 +2704,16 @@ void launch_eval_at(const KParams<R> &P, int what, const R *x, const int *idx, c
     if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
     else hipLaunchKernelGGL((k_eval_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
 }
+template <typename R>
+void launch_eval_plan_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
+    const dim3 grid((n + 255) / 256), block(256);
+    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_plan_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+    else hipLaunchKernelGGL((k_eval_plan_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+}
 template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s) {
-    hipLaunchKernelGGL(k_fleet_rows<R>, dim3(F.n_agents), dim3(64), 0, s, F);
+    if (!F.plans) hipLaunchKernelGGL(k_fleet_rows<R>, dim3(F.n_agents), dim3(64), 0, s, F);
+    else if (F.model == MODEL_DIFF) hipLaunchKernelGGL((k_fleet_plan<R, MODEL_DIFF>), dim3(F.n_agents), dim3(64), 0, s, F);
+    else hipLaunchKernelGGL((k_fleet_plan<R, MODEL_RACE>), dim3(F.n_agents), dim3(64), 0, s, F);
 }
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s) {
     hipLaunchKernelGGL(k_eval_filter<R>, dim3(1), dim3(256), sizeof(R) * 2 * (size_t)(T + W + 2), s, xx, out, T, W, mode);
@@ -2632,6 +2767,7 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
     template void launch_eval<R>(const KParams<R> &, int, const R *, const R *, const int *, int, R *, hipStream_t);   \
     template void launch_eval_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_fleet_rows<R>(const FleetParams &, hipStream_t);                                            \
+    template void launch_eval_plan_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_filter<R>(const R *, R *, int, int, int, hipStream_t);                                 \
     template void launch_set_state_dev<R>(const KParams<R> &, const double *, int, hipStream_t);                     \
     template void launch_viz<R>(const KParams<R> &, const R *, const R *, long long, float *, float *, hipStream_t);

@@ -125,6 +125,22 @@ class Engine:
         self._ck(self.lib.mppi_get_fleet_clearance(self._h, _dp(d), n.ctypes.data_as(C.POINTER(C.c_int64)), int(bool(reset))))
         return d, n
 
+    def set_fleet_prediction(self, mode):
+        """How a fleet handle predicts an agent's mates along the horizon: ``"velocity"`` (the default: constant velocity from
+        the mate rows) or ``"plan"`` (along each mate's own nominal rollout, made afresh at the start of every iteration);
+        mppi_set_fleet_prediction."""
+        modes = {"velocity": capi.FLEET_VELOCITY, "plan": capi.FLEET_PLAN}
+        if mode not in modes:
+            raise capi.MppiError(capi.ERR_BAD_ARG, f"fleet prediction {mode!r} is neither 'velocity' nor 'plan'")
+        self._ck(self.lib.mppi_set_fleet_prediction(self._h, modes[mode]))
+
+    def fleet_plans(self):
+        """[n_agents, T + 1, 2]: every agent's plan as of the current states and nominal controls -- point 0 its position, point
+        j the position after j steps of its nominal sequence (plan mode only; mppi_get_fleet_plans)."""
+        xy = np.empty((self.n_agents, self.T + 1, 2))
+        self._ck(self.lib.mppi_get_fleet_plans(self._h, _dp(xy)))
+        return xy
+
     def agent_status(self):
         """(idx[n_agents], path_end[n_agents]): every agent's waypoint index and whether its last x0 call found the end of
         its own path -- which agent stopped a `run_closed_loop` that raised MPPI_ERR_PATH_END."""

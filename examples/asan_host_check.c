@@ -75,6 +75,9 @@ int main(void) {
         int64_t n = -1;
         EXPECT(mppi_get_agent_circles(NULL, 0, &d, &d, 1, &m) == MPPI_ERR_BAD_ARG && m == -7);
         EXPECT(mppi_get_fleet_clearance(NULL, &d, &n, 1) == MPPI_ERR_BAD_ARG && n == -1);
+        /* and so do the two of the fleet's plan mode */
+        EXPECT(mppi_set_fleet_prediction(NULL, MPPI_FLEET_PLAN) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_get_fleet_plans(NULL, &d) == MPPI_ERR_BAD_ARG && d == -1.0);
     }
     c.obstacle_model = MPPI_OBSTACLE_NONE;
     c.obstacle_motion = 0;

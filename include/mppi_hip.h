@@ -455,6 +455,36 @@ int mppi_get_agent_circles(mppi_handle *h, int32_t agent, double *xyr_out, doubl
  * (A closed-loop call of many iterations returns only the last state: this says whether two robots touched in between.  The
  * refreshes in front of mppi_eval_* and mppi_get_agent_circles are not counted.) */
 int mppi_get_fleet_clearance(mppi_handle *h, double *min_dist, int64_t *contact_iters, int32_t reset);
+/* How a fleet handle (mppi_config.fleet_radius > 0) predicts an agent's mates along the horizon, switched at run time.
+ * MPPI_FLEET_VELOCITY (the default): constant velocity from the mate rows, as documented at mppi_config.fleet_radius, bit for
+ * bit what a handle gives that never called this.  MPPI_FLEET_PLAN: every mate is predicted along its own planned trajectory.
+ * THE PLANS.  At the start of every iteration mppi_run_closed_loop runs -- the moment the mate rows are written in velocity mode
+ * -- the plan of agent a is
+ *   P_a[0] = (x, y) of a's state;
+ *   P_a[j], j = 1 .. T: the position after the model's Euler steps with rows 0 .. j - 1 of a's nominal sequence as it stands then
+ *           (what mppi_get_u_prev returns for a), clamped to +-u_max exactly where the rollout clamps (mppi_config.clamp_rollout).
+ * Both models (unicycle, bicycle), in the handle's precision R from the state rounded to R: the arithmetic of the rollout itself
+ * at zero noise for an exploiting sample (prefix sums over the horizon in R), so P_a is the trajectory a's own iteration prices
+ * as its nominal one.  The state agent b reaches after j rollout steps is tested against P_a[j] for every a != b, with the
+ * threshold a mate has in velocity mode ((0.5 safety_margin + fleet_radius)^2 for MPPI_OBSTACLE_CIRCLE, fleet_radius^2 for
+ * MPPI_OBSTACLE_OUTLINE -- there against the nearest of the outline points as the race-car kernels fold them, for both
+ * models); j = 1 .. T for the stage calls, T for the terminal call, 0 for what prices "now".  A plan has no clock and is not
+ * back-dated: it is made from now.  b's own circles (static or moving) are priced exactly as on the same handle in velocity
+ * mode: own rows, iter0, the same arithmetic.  In plan mode an agent's table is its own rows alone (n_obs = m_b:
+ * mppi_get_agent_circles returns the own circles only); an agent without circles of its own still prices its mates and counts
+ * them in mppi_stats.n_collided.  One launch (k_fleet_plan) takes the place of k_fleet_rows at the front of every slot, inside a
+ * captured graph and inside the first timing bracket, and keeps the clearance record (mppi_get_fleet_clearance: unchanged in
+ * meaning).  mppi_eval_is_collided[_at] and mppi_eval_cost see agent 0's own circles and its mates' plans, refreshed first;
+ * mppi_eval_is_collided_at refuses a step outside [0, T] (MPPI_ERR_BAD_ARG).
+ * Like every setter this synchronises, re-uploads the scenes and drops a cached graph.  NULL handle or unknown mode:
+ * MPPI_ERR_BAD_ARG; a handle without fleet_radius > 0: MPPI_ERR_STATE.  Limits: those of fleet handles. */
+#define MPPI_FLEET_VELOCITY 0
+#define MPPI_FLEET_PLAN 1
+int mppi_set_fleet_prediction(mppi_handle *h, int32_t mode);
+/* Plan mode (else MPPI_ERR_STATE): every agent's plan, host xy [n_agents][T + 1][2], made afresh from the current states and
+ * nominal controls before it is read back (the values are the table's own, in the handle's precision; the refresh does not
+ * count for the clearance record). */
+int mppi_get_fleet_plans(mppi_handle *h, double *xy);
 int mppi_eval_nearest_waypoint(mppi_handle *h, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
                                int32_t *idx_out);
 int mppi_eval_cost(mppi_handle *h, int32_t terminal, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
