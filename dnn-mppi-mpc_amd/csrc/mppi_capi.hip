@@ -143,6 +143,20 @@ struct mppi_handle {
     // k_fleet_rows' place and writes d_plans, [B][T + 1][2] in the handle's precision, which the plan rollout forms read
     bool fleet_plan = false;
     DevBuf<void> d_plans;
+    // Obstacle tracks (mppi_set_obstacle_tracks): the set every agent shares, what mppi_set_agent_obstacle_tracks gave an agent
+    // instead (own_tracks[a], several agents only), and d_tracks, the descriptors the track forms read: every agent's view,
+    // rewritten by every setter (tracks_of, upload_tracks) and allocated by the first one.
+    struct TrackOwn {  // (move-only)
+        DevBuf<void> d_pts, d_thr;  // PlanPoint<R>[n][L], R[n]
+        int n = 0, L = 1;
+        bool has = false;           // (an own set of n = 0 tracks has no buffer)
+        long long iter0 = 0;        // the agent's iteration counter when the set was uploaded
+        std::vector<double> radius;  // as given (mppi_get_obstacle_tracks_at)
+    };
+    TrackOwn tracks;
+    std::vector<TrackOwn> own_tracks;
+    DevBuf<TrackSet> d_tracks;
+    int tracks_max = 0;  // the largest set among the agents, kept by upload_tracks (0: a handle that never had any)
     DevBuf<int> d_pout;
     DevBuf<void> d_partials;        // block records in the handle's precision
     DevBuf<double> d_w, d_trace;
@@ -231,8 +245,16 @@ static AgentScene scene_of(const mppi_handle *h, int a) {
     if (h->fleet) sc.obs = h->fleet_tab[a], sc.n_obs += h->fleet_plan ? 0 : h->B - 1;
     return sc;
 }
+// Agent a's obstacle tracks: what it was given for itself, else the shared set
+static const mppi_handle::TrackOwn &tracks_of(const mppi_handle *h, int a) {
+    return a < (int)h->own_tracks.size() && h->own_tracks[a].has ? h->own_tracks[a] : h->tracks;
+}
+// the largest track set among the agents (0: no agent has tracks and the handle is one that never had any); a field, so that
+// the per-iteration parameter packing of a handle without tracks does what it did
+static int max_tracks(const mppi_handle *h) { return h->tracks_max; }
 // some agent has obstacles: the obstacle instantiations serve and the records carry collision counts
 static bool any_obstacles(const mppi_handle *h) {
+    if (max_tracks(h) > 0) return true;  // (tracks stand in no circle table: a handle may have tracks and no circles)
     if (h->fleet) return true;  // (the mates: rows of every table, or -- plan mode, where an agent may have n_obs = 0 -- their plans)
     for (int a = 0; a < h->B; ++a)
         if (scene_of(h, a).n_obs > 0) return true;
@@ -256,6 +278,8 @@ static bool index_can_move(const mppi_handle *h) { return h->hyp && !(h->idx_val
 template <typename R> static KParams<R> make_params(const mppi_handle *h, const float *eps);
 template <typename R> static RolloutPlan front_plan(const mppi_handle *h, const KParams<R> &P);
 static int upload_scenes(mppi_handle *h);
+static int upload_tracks(mppi_handle *h);
+static void drop_graph(mppi_handle *h);
 static int build_fleet_tables(mppi_handle *h, int only);
 
 // host double[] -> device array in the kernel precision
@@ -637,6 +661,120 @@ extern "C" int mppi_set_agent_obstacles_moving(mppi_handle *h, int32_t agent, co
     return set_agent_circles(h, "mppi_set_agent_obstacles_moving", agent, xyr, vel, m);
 }
 
+// ------------------------------------------------------------------------------------------
+// obstacle tracks
+// ------------------------------------------------------------------------------------------
+// The track forms' table (TrackSet[n_agents]), rewritten from the host's view of every agent (the caller has synchronised the
+// device).  It is read at run time, so a replayed graph sees the new sets; what a launch carries by value -- the table's
+// address and the staged bytes in KParams -- is part of the graph's key.
+static int upload_tracks(mppi_handle *h) {
+    if (!h->d_tracks) return MPPI_OK;
+    std::vector<TrackSet> tab(h->B);
+    h->tracks_max = 0;
+    for (int a = 0; a < h->B; ++a) {
+        const mppi_handle::TrackOwn &t = tracks_of(h, a);
+        h->tracks_max = std::max(h->tracks_max, t.n);
+        tab[a] = TrackSet{t.d_pts.get(), t.d_thr.get(), t.n, t.n > 0 ? t.L : 1, t.iter0};
+    }
+    HIPCHECK(h, hipMemcpy(h->d_tracks, tab.data(), sizeof(TrackSet) * tab.size(), hipMemcpyHostToDevice));
+    return MPPI_OK;
+}
+
+// agent < 0: the set every agent shares.  Everything that can refuse the call stands before the device is touched; the new
+// buffers are allocated into locals and moved in, so a failed allocation leaves the previous set.
+static int set_tracks_impl(mppi_handle *h, const char *who, int agent, const double *xy, const double *radius, int32_t n, int32_t L) {
+    if (!h->cfg.obstacle_motion)
+        FAIL(h, MPPI_ERR_STATE, "%s: the handle was created with obstacle_motion = 0; obstacle tracks need "
+                                "mppi_config.obstacle_motion = 1 at mppi_create", who);
+    if (h->fleet)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: a fleet handle (fleet_radius > 0) takes no obstacle tracks: its plan mode uses the same "
+                                      "parameter words (limit: fleet_radius = 0)", who);
+    if (!h->fused)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: obstacle tracks are served for horizons T <= 128 (T = %d runs the unfused rollout)", who, h->cfg.T);
+    if (agent >= h->B || (agent < 0 && agent != -1)) FAIL(h, MPPI_ERR_BAD_ARG, "%s: agent %d not in [0, %d)", who, agent, h->B);
+    if (n < 0 || n > TRACKS_MAX) FAIL(h, MPPI_ERR_SHAPE, "%s: n = %d tracks, not in [0, %d]", who, n, TRACKS_MAX);
+    if (n > 0 && (L < 1 || L > TRACK_LEN_MAX)) FAIL(h, MPPI_ERR_SHAPE, "%s: L = %d points per track, not in [1, %d]", who, L, TRACK_LEN_MAX);
+    if (n > 0 && (!xy || !radius)) FAIL(h, MPPI_ERR_BAD_ARG, "%s: null argument", who);
+    for (size_t i = 0; n > 0 && i < (size_t)2 * n * L; ++i)
+        if (!std::isfinite(xy[i])) FAIL(h, MPPI_ERR_BAD_ARG, "%s: point %zu of track %zu is not finite", who, (i / 2) % L, i / 2 / L);
+    for (int m = 0; m < n; ++m)
+        if (!std::isfinite(radius[m]) || radius[m] < 0) FAIL(h, MPPI_ERR_BAD_ARG, "%s: the radius of track %d is not finite and >= 0", who, m);
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    long long now = 0;
+    HIPCHECK(h, hipMemcpy(&now, &h->d_st[agent < 0 ? 0 : agent].iter, sizeof(now), hipMemcpyDeviceToHost));
+    DevBuf<void> pts, thr;
+    DevBuf<TrackSet> table;
+    if (n > 0) {
+        std::vector<double> thr2(n);
+        for (int m = 0; m < n; ++m) {  // (as set_circles packs a circle of this radius)
+            const double t = h->cfg.obstacle_model == MPPI_OBSTACLE_CIRCLE ? 0.5 * h->cfg.safety_margin + radius[m] : radius[m];
+            thr2[m] = t * t;
+        }
+        HIPCHECK(h, pts.alloc(rsz(h) * 2 * (size_t)n * L));
+        HIPCHECK(h, thr.alloc(rsz(h) * (size_t)n));
+        if (int rc = upload_real(h, pts, xy, (size_t)2 * n * L)) return rc;  // (rounded to the handle's precision, nothing else)
+        if (int rc = upload_real(h, thr, thr2.data(), (size_t)n)) return rc;
+    }
+    if (!h->d_tracks) HIPCHECK(h, table.alloc(sizeof(TrackSet) * (size_t)h->B));
+    // (nothing below refuses: the previous set goes, behind the synchronisation above)
+    if (table) h->d_tracks = std::move(table);
+    if (agent < 0) {
+        for (mppi_handle::TrackOwn &o : h->own_tracks) o = mppi_handle::TrackOwn{};
+    } else if (h->own_tracks.empty()) {
+        h->own_tracks.resize(h->B);
+    }
+    mppi_handle::TrackOwn &t = agent < 0 ? h->tracks : h->own_tracks[agent];
+    t.d_pts = std::move(pts);
+    t.d_thr = std::move(thr);
+    t.n = n;
+    t.L = n > 0 ? L : 1;
+    t.has = agent >= 0;
+    t.iter0 = now;
+    t.radius.assign(radius, radius + (n > 0 ? n : 0));
+    h->dev_loop_primed = false;
+    drop_graph(h);
+    return upload_tracks(h);
+}
+
+extern "C" int mppi_set_obstacle_tracks(mppi_handle *h, const double *xy, const double *radius, int32_t n, int32_t L) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    return set_tracks_impl(h, "mppi_set_obstacle_tracks", -1, xy, radius, n, L);
+}
+extern "C" int mppi_set_agent_obstacle_tracks(mppi_handle *h, int32_t agent, const double *xy, const double *radius, int32_t n, int32_t L) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (agent < 0) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_agent_obstacle_tracks: agent %d not in [0, %d)", agent, h->B);
+    return set_tracks_impl(h, "mppi_set_agent_obstacle_tracks", h->B == 1 && agent == 0 ? -1 : agent, xy, radius, n, L);
+}
+
+extern "C" int mppi_get_obstacle_tracks_at(mppi_handle *h, int32_t agent, int32_t step, double *xyr_out, int32_t cap, int32_t *n_out) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (!n_out || cap < 0 || (cap > 0 && !xyr_out)) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_get_obstacle_tracks_at: bad argument");
+    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_get_obstacle_tracks_at: agent %d not in [0, %d)", agent, h->B);
+    if (step < 0) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_get_obstacle_tracks_at: step %d is negative (steps count ahead of the clock)", step);
+    const mppi_handle::TrackOwn &t = tracks_of(h, agent);
+    *n_out = t.n;
+    if (cap < t.n) FAIL(h, MPPI_ERR_SHAPE, "mppi_get_obstacle_tracks_at: agent %d has %d tracks, cap = %d", agent, t.n, cap);
+    if (t.n == 0) return MPPI_OK;
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    long long now = 0;
+    HIPCHECK(h, hipMemcpy(&now, &h->d_st[agent].iter, sizeof(now), hipMemcpyDeviceToHost));
+    const int at = track_index(track_clock(now, t.iter0, t.L), step, t.L);
+    return with_real(h, [&](auto r) -> int {
+        using R = decltype(r);
+        std::vector<R> pt((size_t)2 * t.n);  // (point `at` of every track: rows L points apart)
+        HIPCHECK(h, hipMemcpy2D(pt.data(), 2 * sizeof(R), static_cast<const R *>(t.d_pts.get()) + (size_t)2 * at, 2 * sizeof(R) * (size_t)t.L,
+                                2 * sizeof(R), (size_t)t.n, hipMemcpyDeviceToHost));
+        for (int m = 0; m < t.n; ++m) {
+            xyr_out[3 * m] = (double)pt[2 * m];
+            xyr_out[3 * m + 1] = (double)pt[2 * m + 1];
+            xyr_out[3 * m + 2] = t.radius[m];
+        }
+        return MPPI_OK;
+    });
+}
+
 extern "C" int mppi_get_agent_status(mppi_handle *h, int32_t *idx_out, int32_t *path_end_out) {
     if (!h) return MPPI_ERR_BAD_ARG;
     HIPCHECK(h, hipSetDevice(h->cfg.device));
@@ -948,12 +1086,15 @@ extern "C" int mppi_set_iteration(mppi_handle *h, int64_t iteration) {
             HIPCHECK(h, hipMemcpy(&old, &h->d_st[a].iter, sizeof(old), hipMemcpyDeviceToHost));
             if (a == 0) h->obs_iter0 += it - old;
             if (a < (int)h->own.size()) h->own[a].obs_iter0 += it - old;
+            if (a == 0) h->tracks.iter0 += it - old;  // (and the tracks' with the circles')
+            if (a < (int)h->own_tracks.size()) h->own_tracks[a].iter0 += it - old;
         }
         HIPCHECK(h, hipMemcpy(&h->d_st[a].iter, &it, sizeof(it), hipMemcpyHostToDevice));
     }
     h->iter = it;
     if (h->cfg.obstacle_motion) {
         h->dev_loop_primed = false;
+        if (int rc = upload_tracks(h)) return rc;
         return upload_scenes(h);
     }
     return MPPI_OK;
@@ -1071,6 +1212,8 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
         const double thr = c.obstacle_model == MPPI_OBSTACLE_CIRCLE ? 0.5 * c.safety_margin + c.fleet_radius : c.fleet_radius;
         set_fleet_plan<R>(P, h->d_plans, (R)(thr * thr));
     }
+    // (obstacle tracks, never on a fleet handle: the descriptors and the launch's staged bytes, sized by the largest set)
+    if (const int n_max = max_tracks(h)) set_tracks<R>(P, h->d_tracks, n_max);
     return P;
 }
 
@@ -1129,7 +1272,8 @@ static FinalizeParams make_finalize(const mppi_handle *h, int plant, const void 
     F.n_ref = sc0.n_ref;
     F.window = c.search_window;
     F.is_f64 = h->f64;
-    F.count_hits = h->fleet_plan ? 2 : any_obstacles(h);  // (2: every agent counts, also one without rows of its own -- its mates' plans)
+    // (2: every agent counts, also one without rows of its own -- its mates' plans, or its obstacle tracks)
+    F.count_hits = h->fleet_plan || (h->B > 1 && max_tracks(h) > 0) ? 2 : any_obstacles(h);
     F.beta = record_beta(h);
     F.dt = c.delta_t;
     F.wheel_base = c.wheel_base;
@@ -2232,6 +2376,7 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
         else if (at) {
             if (h->fleet) launch_fleet_rows<R>(make_fleet(h, 0), nullptr);  // agent 0's mates as of the current states
             if (h->fleet_plan) launch_eval_plan_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+            else if (tracks_of(h, 0).n > 0) launch_eval_tracks_at<R>(P, what, dx, di, ds, n, dout, nullptr);
             else launch_eval_at<R>(P, what, dx, di, ds, n, dout, nullptr);
         }
         else

@@ -287,6 +287,39 @@ __device__ __forceinline__ bool mates_collided(const KParams<R> &P, const PlanPo
     return hit;
 }
 
+// Obstacle tracks (mppi_set_obstacle_tracks): this lane's state against the point of every track that its step owns.  `pt` is
+// that point of track 0 -- the caller has folded step and clock into it -- and track m's stands `stride` points behind: T + 1
+// in the workgroup's staged window (LDS, one conflict-free `ds_read_b64` per f32 test, consecutive lanes consecutive
+// addresses), L in the table in memory; `thr2[m]` is track m's own squared threshold (a wave-uniform read).  The caller makes
+// one call per address space, so that each compiles to its own load.  OBS_CIRCLE: the circle test of collided(); OBS_OUTLINE:
+// its folded outline form, for both models, as mates_collided has it.  No self to skip.  A function of its own beside
+// collided() and mates_collided(), whose text and callers stay as they are.
+template <typename R>
+__device__ __forceinline__ bool tracks_collided(const KParams<R> &P, const PlanPoint<R> *pt, const R *thr2, int n, int stride,
+                                                R x, R y, R yaw) {
+    bool hit = false;
+    if (P.obstacle_model == OBS_CIRCLE) {
+        for (int m = 0; m < n; ++m) {
+            const PlanPoint<R> c = pt[(size_t)m * stride];
+            const R dx = x - c.x, dy = y - c.y;
+            hit |= dx * dx + dy * dy < thr2[m];
+        }
+        return hit;
+    }
+    R sn, cs;
+    mf::sincos_(yaw, sn, cs);
+    const R ha = P.shape_x[3], hb = P.shape_y[3];
+    for (int m = 0; m < n; ++m) {
+        const PlanPoint<R> c = pt[(size_t)m * stride];
+        const R dx = c.x - x, dy = c.y - y;
+        const R bx = fabs(dx * cs + dy * sn), by = fabs(dy * cs - dx * sn);
+        const R ex = bx - ha, ey = by - hb;
+        const R ex2 = ex * ex, ey2 = ey * ey;
+        hit |= fmin(fmin(ex2 + by * by, ex2 + ey2), bx * bx + ey2) < thr2[m];
+    }
+    return hit;
+}
+
 // weighted squared tracking error against waypoint i (`_compute_cost` :222-236, `_c` mppi_race_car.py:137-146)
 template <typename R, int MODEL>
 __device__ __forceinline__ R tracking_cost_row(const KParams<R> &P, const R (&w)[4], bool wrap, const R *r, R x, R y, R yaw,

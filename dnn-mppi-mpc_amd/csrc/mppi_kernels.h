@@ -139,7 +139,8 @@ template <typename R> struct KParams {
     const R *u;        // [T][2] nominal controls
     const float *eps;  // [K][T][2] or nullptr (Philox); with eps_slots > 0: a ring [eps_slots][n_agents][K][T][2]
     int eps_slots;     // 0: `eps` is this call's tensor; 2^n: iteration i reads slot i mod eps_slots (mppi_set_noise_ring)
-    int obs_motion;    // mppi_config.obstacle_motion: the circles carry velocities and the moving instantiations serve (this
+    int obs_motion;    // mppi_config.obstacle_motion: the circles carry velocities and the moving instantiations serve; 2
+                       // (OBS_MOTION_TRACKS): some agent has obstacle tracks as well and the track forms serve (this
                        // word was padding: the layout stays)
     R *S;              // [K]
     int *pout;         // [K] waypoint index after sample k (sequential mode)
@@ -197,6 +198,47 @@ template <typename R> inline void set_fleet_plan(KParams<R> &P, const void *tabl
     P.pad_scenes[0] = (long long)reinterpret_cast<uintptr_t>(table);
     P.pad_scenes[1] = 0;
     __builtin_memcpy(&P.pad_scenes[1], &thr2, sizeof(R));
+}
+// Obstacle tracks (mppi_set_obstacle_tracks; a handle with obstacle_motion and no fleet, so pad_scenes is free): one descriptor
+// per agent in device memory, rewritten by every setter and read afresh by every launch (a replayed graph too).  Track m's
+// point i -- its centre i control steps after the upload -- is pts[m L + i]; thr2[m] is its squared threshold, packed as
+// set_circles packs a circle of that radius; iter0 is the agent's DevState::iter at the upload.  The state a rollout reaches
+// after j steps is tested against point track_index(clock, j, L).  n = 0: the agent has no tracks.
+struct alignas(32) TrackSet {
+    const void *pts;   // PlanPoint<R>[n][L]
+    const void *thr2;  // R[n]
+    int n, L;
+    long long iter0;
+};
+static_assert(sizeof(TrackSet) == 32, "TrackSet layout");
+constexpr int TRACKS_MAX = 256, TRACK_LEN_MAX = 65536;
+// KParams::pad_scenes on such a handle: word 0 the address of TrackSet[n_agents] (0: no agent has tracks, the SPEC = 3 forms
+// serve), word 1 the bytes of dynamic LDS the launch was sized for (0: the points are read from memory)
+template <typename R> __host__ __device__ inline const TrackSet *track_sets(const KParams<R> &P) {
+    return reinterpret_cast<const TrackSet *>(P.pad_scenes[0]);
+}
+// (KParams::obs_motion says which of the two users of pad_scenes a handle is: the planners read it, no kernel does)
+constexpr int OBS_MOTION_TRACKS = 2;
+template <typename R> __host__ __device__ inline int track_staged_bytes(const KParams<R> &P) { return (int)P.pad_scenes[1]; }
+// the control steps since the upload, kept inside the table whatever the counter says
+__host__ __device__ inline int track_clock(long long iter, long long iter0, int L) {
+    const long long c = iter - iter0;
+    return c < 0 ? 0 : c > L - 1 ? L - 1 : (int)c;
+}
+// the point a state j >= 0 steps ahead is tested against: a track holds its last point once it runs out
+__host__ __device__ inline int track_index(int clock, int j, int L) { return j < L - 1 - clock ? clock + j : L - 1; }
+// A workgroup of the track forms stages the window its clock selects -- T + 1 points per track, then the thresholds -- into
+// dynamic LDS where the largest set among the agents fits beside the forms' own LDS within the 64 KB a workgroup gets without
+// raising a limit: fleet_plan_lds_bytes' limits, for its reason.  Larger sets are read from memory with the clamped index.
+// One function for the planner, which sizes the launch by it, and (through pad_scenes[1]) the kernel.
+template <typename R> __host__ __device__ inline int track_lds_bytes(int n_max, int T) {
+    const long long bytes = (long long)n_max * ((T + 1) * 2 + 1) * (long long)sizeof(R);
+    return bytes <= (sizeof(R) == 4 ? 40000 : 16384) ? (int)bytes : 0;
+}
+template <typename R> inline void set_tracks(KParams<R> &P, const TrackSet *sets, int n_max) {
+    P.pad_scenes[0] = (long long)reinterpret_cast<uintptr_t>(sets);
+    P.pad_scenes[1] = sets ? track_lds_bytes<R>(n_max, P.T) : 0;
+    if (sets) P.obs_motion = OBS_MOTION_TRACKS;
 }
 // (lb_timeout took the place of a padding word: the layout the kernels' argument loads were tuned for stays as it was)
 static_assert(sizeof(KParams<float>) == 424 && sizeof(KParams<double>) == 576, "KParams layout");
@@ -431,6 +473,10 @@ template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s
 // their plans (P carries the table: set_fleet_plan; steps inside [0, T])
 template <typename R>
 void launch_eval_plan_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
+// launch_eval_at for a handle whose agent 0 has obstacle tracks: its own circles at steps[i] of their clock and its tracks at
+// point track_index(clock, steps[i], L) (P carries the descriptors: set_tracks; any step >= 0)
+template <typename R>
+void launch_eval_tracks_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s);
 void launch_eval_weights(const double *S, int n, double beta, double *w, hipStream_t s);
 template <typename R> void launch_set_state_dev(const KParams<R> &P, const double *x_dev, int nx, hipStream_t s);

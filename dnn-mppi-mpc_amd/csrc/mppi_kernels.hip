@@ -104,9 +104,33 @@ template <typename R> struct RolloutMotion<R, true> {
         clock = obstacle_clock(sv.iter, P.iter0);
     }
 };
+// What a TRACKS rollout carries (mppi_set_obstacle_tracks): its agent's descriptor and the clock of that set, kept inside the
+// table (track_clock).  The other forms' is empty, so that they keep their code.
+template <typename R, bool TRACKS> struct RolloutTracks {
+    RolloutTracks() = default;
+    __device__ __forceinline__ RolloutTracks(const KParams<R> &, const DevState &, int) {}
+};
+template <typename R> struct RolloutTracks<R, true> {
+    const PlanPoint<R> *trk_pts = nullptr;
+    const R *trk_thr2 = nullptr;
+    int trk_n = 0, trk_L = 1, trk_clock = 0;
+    RolloutTracks() = default;
+    __device__ __forceinline__ RolloutTracks(const KParams<R> &P, const DevState &sv, int agent) {
+        const TrackSet ts = track_sets(P)[agent];
+        trk_pts = static_cast<const PlanPoint<R> *>(ts.pts);
+        trk_thr2 = static_cast<const R *>(ts.thr2);
+        trk_n = ts.n;
+        trk_L = ts.L;
+        trk_clock = track_clock(sv.iter, ts.iter0, ts.L);
+    }
+};
 // PLANS (MPPI_FLEET_PLAN, with MOVING): beside its own moving circles the agent tests its mates at the point of their plans
 // that its step owns (mates_collided, mppi_device.h); the table and the threshold travel in KParams.
-template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVING = false, bool PLANS = false> struct Rollout : RolloutMotion<R, MOVING> {
+// TRACKS (with MOVING, never with PLANS): beside its own moving circles the agent tests its obstacle tracks at the point its
+// step and the set's clock select (tracks_collided, mppi_device.h); k_rollout_fused hands the descriptor over (set_tracks).
+template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVING = false, bool PLANS = false, bool TRACKS = false>
+struct Rollout : RolloutMotion<R, MOVING>, RolloutTracks<R, TRACKS> {
+    __device__ __forceinline__ void set_tracks(const RolloutTracks<R, TRACKS> &tk) { static_cast<RolloutTracks<R, TRACKS> &>(*this) = tk; }
     __device__ __forceinline__ bool use_philox() const { return PLAIN || P.use_philox; }
     __device__ __forceinline__ bool clamp_rollout() const { return PLAIN || P.clamp_rollout; }
     __device__ __forceinline__ bool wrap_stage() const { return !PLAIN && P.wrap_stage; }
@@ -144,7 +168,24 @@ template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVIN
     // collision test of this lane's state after step 64 ch + lane.  MOVING: that state lies j = 64 ch + lane + 1 steps ahead;
     // the terminal call prices the same state, and only lane_last's terminal value is read: j = T there
     __device__ __forceinline__ bool collided_at(int ch, R x, R y, R yaw) const {
-        if constexpr (PLANS) {  // (a lane beyond the horizon reads point T: its cost is never read)
+        if constexpr (TRACKS) {  // (a lane beyond the horizon reads the point of step T: its cost is never read)
+            static_assert(MOVING && !PLANS, "the track forms extend the moving ones");
+            const ObsLanesMoving<R> tab{obs.x, obs.y, obs.r2, this->vx, this->vy};
+            const int j = 64 * ch + lane + 1;
+            bool hit = collided<MODEL == MODEL_RACE, true>(P, x, y, yaw, tab, false, R(0), R(1), obstacle_time(P, this->clock + j));
+            const int jp = j < P.T ? j : P.T;
+            // (the workgroup's window in dynamic LDS where the launch was sized for it -- k_rollout_fused staged it with the clock
+            // folded in: points, then thresholds --, else the table in memory with the clamped index)
+            extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
+            if (track_staged_bytes(P) > 0) {
+                const PlanPoint<R> *w = reinterpret_cast<const PlanPoint<R> *>(dyn_lds);
+                hit |= tracks_collided(P, w + jp, reinterpret_cast<const R *>(w + this->trk_n * (P.T + 1)), this->trk_n, P.T + 1, x, y, yaw);
+            } else {
+                hit |= tracks_collided(P, this->trk_pts + track_index(this->trk_clock, jp, this->trk_L), this->trk_thr2, this->trk_n,
+                                       this->trk_L, x, y, yaw);
+            }
+            return hit;
+        } else if constexpr (PLANS) {  // (a lane beyond the horizon reads point T: its cost is never read)
             static_assert(MOVING, "the plan forms extend the moving ones");
             const ObsLanesMoving<R> tab{obs.x, obs.y, obs.r2, this->vx, this->vy};
             const int j = 64 * ch + lane + 1;
@@ -596,14 +637,14 @@ __device__ __forceinline__ void per_rollout_thread(const KParams<R> &P, int c, c
 // MULTI: several agents per launch, one row of workgroups (blockIdx.y) each; a single agent compiles to the
 // offset-free code (the offsets cost config 2 half a microsecond per iteration when they were unconditional)
 // SPEC: 0 general, 1 no obstacles, 2 no obstacles + the PLAIN switches (see Rollout), 3 general with moving obstacles, 4 the
-// same with the mates' plans (MULTI only: a mate is another agent of the launch)
+// same with the mates' plans (MULTI only: a mate is another agent of the launch), 5 general, moving, with obstacle tracks
 // HYPK: the instantiation that can resolve the sequential index in one launch (fused_lookback).  A separate instantiation,
 // picked by the host while the waypoint index can still move (KParams::hyp): carrying that code costs the lean kernel
 // 0.17 us per launch in registers and LDS (A/B on one box), and at the end of the path nothing moves any more.
 template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK = false>
 __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevState *st_pre, KParams<R> P,
                                                                     R *__restrict__ partials) {
-    constexpr bool OBS = SPEC == 0 || SPEC == 3 || SPEC == 4, PLAIN = SPEC == 2, MOVING = SPEC == 3 || SPEC == 4, PLANS = SPEC == 4;
+    constexpr bool OBS = SPEC == 0 || SPEC >= 3, PLAIN = SPEC == 2, MOVING = SPEC >= 3, PLANS = SPEC == 4, TRACKS = SPEC == 5;
     static_assert(!PLANS || MULTI, "the mates are the other agents of a batched launch");
     static_assert(!(HYPK && MOVING), "the look-back prices the last state with a collision test of its own: static obstacles only");
     const int agent = MULTI ? (int)blockIdx.y : 0;
@@ -649,6 +690,23 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
             if (!(use_win || seq_search)) __syncthreads();  // (else the barrier below serves)
         }
     }
+    // TRACKS: the window of T + 1 points per track that this agent's clock selects, then its thresholds, into dynamic LDS where
+    // the planner sized the launch for the largest set (KParams::pad_scenes[1]: the launch's decision, the same for every agent)
+    const RolloutTracks<R, TRACKS> tk(P, sv, agent);
+    if constexpr (TRACKS) {
+        extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
+        if (track_staged_bytes(P) > 0) {
+            PlanPoint<R> *dst = reinterpret_cast<PlanPoint<R> *>(dyn_lds);
+            const int n_pts = tk.trk_n * (P.T + 1);  // (n <= the launch's largest set: inside the bytes it was sized for)
+            for (int i = threadIdx.x; i < n_pts; i += blockDim.x) {
+                const int m = i / (P.T + 1), j = i - m * (P.T + 1);
+                dst[i] = tk.trk_pts[(size_t)m * tk.trk_L + track_index(tk.trk_clock, j, tk.trk_L)];
+            }
+            R *thr = reinterpret_cast<R *>(dst + n_pts);
+            for (int m = threadIdx.x; m < tk.trk_n; m += blockDim.x) thr[m] = tk.trk_thr2[m];
+            if (!(use_win || seq_search)) __syncthreads();  // (else the barrier below serves)
+        }
+    }
     if (use_win || seq_search) __syncthreads();
     float e0[NCH], e1[NCH];
     R S_k = R(INFINITY);
@@ -669,8 +727,9 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
         const bool ref_lds = P.n_ref <= PR_REF_LDS;
         if (ref_lds)
             for (int i = threadIdx.x; i < P.n_ref; i += blockDim.x) { sh_pref[2 * i] = P.ref[4 * i]; sh_pref[2 * i + 1] = P.ref[4 * i + 1]; }
-        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS> r(P, sv, k, lane, nullptr, obs, agent, mv);
-        typename Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
+        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS> r(P, sv, k, lane, nullptr, obs, agent, mv);
+        if constexpr (TRACKS) r.set_tracks(tk);
+        typename Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
         if (valid) sp = r.dynamics(0, e0[0], e1[0]);
         sh_px[wid][lane] = sp.x;
         sh_py[wid][lane] = sp.y;
@@ -682,7 +741,8 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
             S_k = r.finish(false);
         }
     } else if (valid) {
-        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
+        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
+        if constexpr (TRACKS) r.set_tracks(tk);
         r.sh_first = seq_search ? &sh_first : nullptr;
         if (k >= k_start) {
 #pragma unroll
@@ -2418,6 +2478,34 @@ __global__ __launch_bounds__(256) void k_eval_plan_at(const KParams<R> P, int wh
     }
 }
 
+// k_eval_at for a handle whose agent 0 has obstacle tracks: its own circles steps[i] rollout steps ahead of their clock, and
+// its tracks at the point that step and the tracks' clock select -- any step >= 0: the index is kept inside the table
+template <typename R, int MODEL>
+__global__ __launch_bounds__(256) void k_eval_tracks_at(const KParams<R> P, int what, const R *__restrict__ x, const int *__restrict__ idx,
+                                                        const int *__restrict__ steps, int n, R *__restrict__ out) {
+    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
+    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
+    const bool act = i < n;
+    R s[4] = {R(0), R(0), R(0), R(0)};
+    if (act)
+        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
+    const int j = act && steps ? steps[i] : 0;
+    const R tau = obstacle_time(P, obstacle_clock(P.st->iter, P.iter0) + j);
+    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
+    const TrackSet ts = track_sets(P)[0];
+    const int at = track_index(track_clock(P.st->iter, ts.iter0, ts.L), j < 0 ? 0 : j, ts.L);
+    hit |= tracks_collided(P, static_cast<const PlanPoint<R> *>(ts.pts) + at, static_cast<const R *>(ts.thr2), ts.n, ts.L, s[0], s[1], s[2]);
+    if (what == EVAL_COLLIDED) {
+        if (act) out[i] = hit ? R(1) : R(0);
+    } else {
+        const bool term = what == EVAL_COST_TERMINAL;
+        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
+                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit);
+        if (act) out[i] = c;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
@@ -2543,8 +2631,10 @@ template <typename R, int MODEL, bool MULTI, int SPW> static KernelLaunch dual_p
 }
 // k_rollout_fused<R, MODEL, NCH, MULTI, SPEC, HYPK>: SPEC 2 the plain form, 1 no obstacles, 0 everything, 3 everything with
 // moving obstacles (never with the look-back: lookback_serves, mppi_capi.hip), 4 the same with the mates' plans (batched
-// launches of a handle that carries a plan table)
+// launches of a handle that carries a plan table), 5 the moving form with obstacle tracks (some agent has a track set)
 template <typename R, int MODEL, int NCH, bool MULTI, bool HYPK> static KernelLaunch fused_plan(int spec) {
+    if constexpr (!HYPK)
+        if (spec == 5) return fused_entry<R, MODEL, NCH, MULTI, 5, false>();
     if constexpr (!HYPK && MULTI)
         if (spec == 4) return fused_entry<R, MODEL, NCH, true, 4, false>();
     if constexpr (!HYPK)
@@ -2588,8 +2678,9 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
             // (a handle with obstacle motion takes the moving form whatever its set holds at the moment -- none yet, or m = 0:
             // an agent of a batch with no circles of its own then computes what its single-agent handle computes, bit for
             // bit; the forms contract their cost arithmetic differently in the last place)
-            const bool plans = MULTI && P.obs_motion && fleet_plan_table(P) != nullptr;
-            const int spec = plans ? 4 : P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
+            const bool tracks = P.obs_motion == OBS_MOTION_TRACKS;  // (never a fleet handle: pad_scenes carries the descriptors)
+            const bool plans = MULTI && P.obs_motion && !tracks && fleet_plan_table(P) != nullptr;
+            const int spec = tracks ? 5 : plans ? 4 : P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
             p.lookback = !MULTI && MODEL == MODEL_DIFF && P.hyp && P.T <= 64 && !P.obs_motion;  // (the HYPK form: one agent, diff-drive, one chunk)
             p.k = p.lookback  ? fused_plan<R, MODEL_DIFF, 1, false, true>(spec)
                   : P.T <= 64 ? fused_plan<R, MODEL, 1, MULTI, false>(spec)
@@ -2599,7 +2690,9 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
     p.records = blocks;
     p.k.grid = dim3(blocks, MULTI ? P.n_agents : 1);
     // (the plan forms: the staged table, or 0 -- the memory path)
-    if (MULTI && P.obs_motion && fleet_plan_table(P) != nullptr && (P.layout & LAYOUT_KIND) == LAYOUT_FUSED)
+    if (P.obs_motion == OBS_MOTION_TRACKS) {  // (the track forms: the staged windows of the largest set, or 0 -- the memory path)
+        if ((P.layout & LAYOUT_KIND) == LAYOUT_FUSED) p.k.lds = (size_t)track_staged_bytes(P);
+    } else if (MULTI && P.obs_motion && fleet_plan_table(P) != nullptr && (P.layout & LAYOUT_KIND) == LAYOUT_FUSED)
         p.k.lds = (size_t)fleet_plan_lds_bytes<R>(P.n_agents, P.T);
     return p;
 }
@@ -2710,6 +2803,12 @@ void launch_eval_plan_at(const KParams<R> &P, int what, const R *x, const int *i
     if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_plan_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
     else hipLaunchKernelGGL((k_eval_plan_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
 }
+template <typename R>
+void launch_eval_tracks_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
+    const dim3 grid((n + 255) / 256), block(256);
+    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_tracks_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+    else hipLaunchKernelGGL((k_eval_tracks_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+}
 template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s) {
     if (!F.plans) hipLaunchKernelGGL(k_fleet_rows<R>, dim3(F.n_agents), dim3(64), 0, s, F);
     else if (F.model == MODEL_DIFF) hipLaunchKernelGGL((k_fleet_plan<R, MODEL_DIFF>), dim3(F.n_agents), dim3(64), 0, s, F);
@@ -2768,6 +2867,7 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
     template void launch_eval_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_fleet_rows<R>(const FleetParams &, hipStream_t);                                            \
     template void launch_eval_plan_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
+    template void launch_eval_tracks_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_filter<R>(const R *, R *, int, int, int, hipStream_t);                                 \
     template void launch_set_state_dev<R>(const KParams<R> &, const double *, int, hipStream_t);                     \
     template void launch_viz<R>(const KParams<R> &, const R *, const R *, long long, float *, float *, hipStream_t);

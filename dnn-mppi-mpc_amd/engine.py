@@ -117,6 +117,30 @@ class Engine:
             self._ck(self.lib.mppi_get_agent_circles(self._h, int(agent), _dp(c), _dp(v), m.value, C.byref(m)))
         return c, v
 
+    def set_obstacle_tracks(self, xy, radii, agent=None):
+        """Obstacles given as predicted positions: ``xy`` [n, L, 2], point i of a track its centre i control steps after this
+        call (it holds the last one afterwards), ``radii`` [n]; for a handle created with ``obstacle_motion=1``.  ``agent``: as
+        in `set_ref_path`.  n = 0 removes the set (mppi_set_obstacle_tracks / mppi_set_agent_obstacle_tracks)."""
+        r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+        p = np.ascontiguousarray(xy, dtype=np.float64)
+        p = p.reshape(r.shape[0], -1, 2) if r.shape[0] else p.reshape(0, 1, 2)
+        if agent is None:
+            self._ck(self.lib.mppi_set_obstacle_tracks(self._h, _dp(p), _dp(r), p.shape[0], p.shape[1]))
+        else:
+            self._ck(self.lib.mppi_set_agent_obstacle_tracks(self._h, int(agent), _dp(p), _dp(r), p.shape[0], p.shape[1]))
+
+    def obstacle_tracks_at(self, step, agent=0):
+        """[n, 3] = x, y, r: the centres and radii ``agent`` tests at rollout step ``step`` >= 0 of the current clock
+        (mppi_get_obstacle_tracks_at)."""
+        n = C.c_int32()
+        rc = self.lib.mppi_get_obstacle_tracks_at(self._h, int(agent), int(step), None, 0, C.byref(n))
+        if rc != capi.ERR_SHAPE:  # (cap = 0 holds no track: MPPI_ERR_SHAPE with n written, or n = 0)
+            self._ck(rc)
+        out = np.empty((n.value, 3))
+        if n.value:
+            self._ck(self.lib.mppi_get_obstacle_tracks_at(self._h, int(agent), int(step), _dp(out), n.value, C.byref(n)))
+        return out
+
     def fleet_clearance(self, reset=False):
         """(min_dist[n_agents], contact_iters[n_agents]) over the iterations run since the handle was made or the last call
         with ``reset=True``: the smallest centre distance of every agent to any mate at the start of an iteration (inf: none

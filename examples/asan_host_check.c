@@ -78,6 +78,10 @@ int main(void) {
         /* and so do the two of the fleet's plan mode */
         EXPECT(mppi_set_fleet_prediction(NULL, MPPI_FLEET_PLAN) == MPPI_ERR_BAD_ARG);
         EXPECT(mppi_get_fleet_plans(NULL, &d) == MPPI_ERR_BAD_ARG && d == -1.0);
+        /* and the three of the obstacle tracks */
+        EXPECT(mppi_set_obstacle_tracks(NULL, &d, &d, 1, 1) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_agent_obstacle_tracks(NULL, 0, &d, &d, 1, 1) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_get_obstacle_tracks_at(NULL, 0, 0, &d, 1, &m) == MPPI_ERR_BAD_ARG && m == -7 && d == -1.0);
     }
     c.obstacle_model = MPPI_OBSTACLE_NONE;
     c.obstacle_motion = 0;

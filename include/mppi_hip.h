@@ -485,6 +485,36 @@ int mppi_set_fleet_prediction(mppi_handle *h, int32_t mode);
  * nominal controls before it is read back (the values are the table's own, in the handle's precision; the refresh does not
  * count for the clearance record). */
 int mppi_get_fleet_plans(mppi_handle *h, double *xy);
+/* OBSTACLE TRACKS: obstacles that an outside predictor delivers as a list of positions, one per control step, instead of
+ * {centre, velocity}.  The setters work on a handle created with obstacle_motion = 1 (any other: MPPI_ERR_STATE).
+ * THE TRACKS.  xy is [n][L][2]: point i of track m, xy[m][i], is the centre of obstacle m i control steps (delta_t each) after
+ * this call; radius[m] is its radius.  The points are stored rounded to the handle's precision R with no other arithmetic, so
+ * what the device tests is R(xy) exactly.
+ * THE CLOCK is that of the moving circles: the setter records iter0 = the handle's iteration counter in a word of the set's own
+ * (the circles' iter0 is untouched), and with c = iteration - iter0 the state a rollout reaches after j steps is tested against
+ * point min(c + j, L - 1) of every track; j = 1 .. T for the stage calls, T for the terminal call, 0 for what prices "now".  A
+ * track holds its last point once it runs out; a track of L = 1 is a static circle.  One iteration is one tick, speculation
+ * rounds share it, mppi_run_closed_loop and a replayed graph read the clock on the device.  mppi_set_iteration shifts the
+ * tracks' iter0 with the circles' (the clock does not move); a fresh upload re-bases it.
+ * THE TEST.  Every track has a threshold of its own, packed from radius[m] exactly as a circle of that radius is packed:
+ * (0.5 safety_margin + r)^2 for MPPI_OBSTACLE_CIRCLE, r^2 for MPPI_OBSTACLE_OUTLINE -- there against the nearest of the outline
+ * points as the race-car kernels fold them, for both models.  The handle's own circles, static or moving, are priced exactly as
+ * before, beside the tracks; a handle may have tracks and no circles.  A sample that hits a track counts in
+ * mppi_stats.n_collided.  mppi_eval_is_collided[_at] and mppi_eval_cost see agent 0's tracks; any step >= 0 is valid there.
+ * n = 0 removes the set: the handle is then bit for bit the handle that never called the setter.
+ * BATCHES.  mppi_set_obstacle_tracks gives every agent the same set (and takes back what the agent setter gave);
+ * mppi_set_agent_obstacle_tracks gives one agent a set of its own.  Sets may differ in n and L, and an agent may have none: the
+ * semantics of mppi_set_obstacles / mppi_set_agent_obstacles.
+ * REFUSALS leave the scene as it was.  NULL handle, NULL xy or radius with n > 0, a non-finite point, a non-finite or negative
+ * radius, an agent outside [0, n_agents): MPPI_ERR_BAD_ARG.  n outside [0, 256], L outside [1, 65536] (n > 0): MPPI_ERR_SHAPE.
+ * A fleet handle (fleet_radius > 0: its plan mode uses the same parameter words) or a horizon T > 128 (the unfused rollout):
+ * MPPI_ERR_UNSUPPORTED.  Like every setter this synchronises and drops a cached graph. */
+int mppi_set_obstacle_tracks(mppi_handle *h, const double *xy, const double *radius, int32_t n, int32_t L);
+int mppi_set_agent_obstacle_tracks(mppi_handle *h, int32_t agent, const double *xy, const double *radius, int32_t n, int32_t L);
+/* The centres and radii agent `agent` tests at rollout step `step` >= 0 of the current clock: xyr_out [cap][3] receives
+ * {R(xy)[m][min(c + step, L - 1)], radius[m]} for its n tracks (for visualisation and tests).  *n_out is written even when cap
+ * is too small (MPPI_ERR_SHAPE then). */
+int mppi_get_obstacle_tracks_at(mppi_handle *h, int32_t agent, int32_t step, double *xyr_out, int32_t cap, int32_t *n_out);
 int mppi_eval_nearest_waypoint(mppi_handle *h, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
                                int32_t *idx_out);
 int mppi_eval_cost(mppi_handle *h, int32_t terminal, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
