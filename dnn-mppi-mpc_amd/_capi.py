@@ -144,6 +144,10 @@ PROTOTYPES = {
     "mppi_set_obstacle_tracks": (C.c_int, [_H, _D, _D, C.c_int32, C.c_int32]),
     "mppi_set_agent_obstacle_tracks": (C.c_int, [_H, C.c_int32, _D, _D, C.c_int32, C.c_int32]),
     "mppi_get_obstacle_tracks_at": (C.c_int, [_H, C.c_int32, C.c_int32, _D, C.c_int32, C.POINTER(C.c_int32)]),
+    "mppi_set_cost_grid": (C.c_int, [_H, _D, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "mppi_set_agent_cost_grid": (C.c_int, [_H, C.c_int32, _D, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                           C.c_double]),
+    "mppi_eval_cost_grid": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D]),
     "mppi_eval_nearest_waypoint": (C.c_int, [_H, _D, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "mppi_eval_cost": (C.c_int, [_H, C.c_int32, _D, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _D, C.POINTER(C.c_int32)]),
     "mppi_eval_moving_average": (C.c_int, [_H, _D, _D]),

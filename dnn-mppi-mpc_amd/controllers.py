@@ -49,11 +49,11 @@ class _ControllerBase:
     _ref_dtype = np.float64
 
     def _finish_init(self, cfg, ref_path, obstacle_circles, precision, device, seed, process_group, obstacle_velocities=None,
-                     obstacle_tracks=None):
+                     obstacle_tracks=None, cost_grid=None):
         if obstacle_velocities is not None and obstacle_circles is None:
             raise ValueError("obstacle_velocities needs obstacle_circles")
-        # a create-time switch (mppi_config.obstacle_motion): either keyword sets it
-        cfg.update(obstacle_motion=int(obstacle_velocities is not None or obstacle_tracks is not None))
+        # a create-time switch (mppi_config.obstacle_motion): any of the three keywords sets it
+        cfg.update(obstacle_motion=int(obstacle_velocities is not None or obstacle_tracks is not None or cost_grid is not None))
         cfg.update(precision=capi.PREC_F64 if precision in ("f64", "float64") else capi.PREC_F32,
                    device=int(device), seed=int(seed), collision_penalty=1.0e10, filter_window=10)
         self._pg = process_group
@@ -79,6 +79,9 @@ class _ControllerBase:
         self._tracks = None
         if obstacle_tracks is not None:
             self.obstacle_tracks = obstacle_tracks
+        self._cost_grid = None
+        if cost_grid is not None:
+            self.cost_grid = cost_grid
         self._u_host = np.zeros((self.T, self.dim_u))  # `u_prev`, mppi_differential_drive.py:82
         self._u_dev_copy = self._u_host.copy()
         self._idx_dev = 0
@@ -226,6 +229,26 @@ class _ControllerBase:
         xy = _arr(xy).reshape(radii.shape[0], -1, 2) if radii.shape[0] else np.zeros((0, 1, 2))
         self._engine.set_obstacle_tracks(xy, radii)
         self._tracks = (xy, radii) if radii.shape[0] else None
+
+    @property
+    def cost_grid(self):
+        """``dict(cells=[ny, nx], origin=(x, y), resolution=..., weight=1.0, lethal=inf)``: a costmap looked up bilinearly at
+        every rollout state (`Engine.set_cost_grid`), priced beside ``obstacle_circles``, or None.  The controller must have
+        been built with ``cost_grid``, ``obstacle_tracks`` or ``obstacle_velocities`` (the switch is a create-time one);
+        assigning None removes the grid."""
+        return self._cost_grid
+
+    @cost_grid.setter
+    def cost_grid(self, value):
+        if value is None:
+            self._engine.set_cost_grid(None)
+            self._cost_grid = None
+            return
+        g = dict(value)
+        g["cells"] = _arr(g["cells"])
+        self._engine.set_cost_grid(g["cells"], g.get("origin", (0.0, 0.0)), g.get("resolution", 1.0), g.get("weight", 1.0),
+                                   g.get("lethal", float("inf")))
+        self._cost_grid = g
 
     @property
     def u_prev(self):
@@ -478,7 +501,7 @@ class MPPIAlgorithms(_ControllerBase):
                  safety_margin_rate=None, visualize_optimal_traj=True, visualze_sampled_trajs=True,
                  visualize_sampled_traj=None, *, variant="numpy", precision="f32", device=0, seed=0,
                  process_group=None, waypoint_mode=None, learned_dynamics=None, learned_scalers=None,
-                 obstacle_velocities=None, obstacle_tracks=None):
+                 obstacle_velocities=None, obstacle_tracks=None, cost_grid=None):
         if visualize_sampled_traj is not None:  # the torch variant's spelling (:63-64)
             visualze_sampled_trajs = visualize_sampled_traj
         self.delta_t = _num(delta_t)
@@ -524,13 +547,14 @@ class MPPIAlgorithms(_ControllerBase):
             clamp_rollout=0 if variant == "torch" else 1,
             clamp_u_after_update=int(self.visualze_sampled_trajs),  # :145-149
             filter_mode=capi.FILTER_TORCH if variant == "torch" else capi.FILTER_DIFFDRIVE,  # _torch.py:252-263
-            obstacle_model=capi.OBSTACLE_CIRCLE if obstacle_circles is not None or obstacle_tracks is not None else capi.OBSTACLE_NONE,
+            obstacle_model=(capi.OBSTACLE_CIRCLE if obstacle_circles is not None or obstacle_tracks is not None or cost_grid is not None
+                            else capi.OBSTACLE_NONE),
             raise_at_path_end=0,
             safety_margin=0.0 if safety_margin_rate is None else self.safefy_margin_rate,
             vehicle_w=0.0, vehicle_l=0.0,
         )
         self._finish_init(cfg, ref_path, obstacle_circles, precision, device, seed, process_group, obstacle_velocities,
-                          obstacle_tracks)
+                          obstacle_tracks, cost_grid)
         self._learned = learned_dynamics is not None
         if self._learned:
             self._engine.set_mlp(learned_dynamics, learned_scalers)
@@ -579,7 +603,7 @@ class MPPIRacecarController(_ControllerBase):
                  stage_cost_weight=(50.0, 50.0, 1.0, 20.0), terminal_cost_weight=(50.0, 50.0, 1.0, 20.0),
                  obstacle_circles=None, collision_safety_margin_rat=1.5, visualize_optimal_traj=True,
                  visualze_sampled_trajs=True, *, variant="numpy", precision="f32", device=0, seed=0, process_group=None,
-                 obstacle_velocities=None, obstacle_tracks=None):
+                 obstacle_velocities=None, obstacle_tracks=None, cost_grid=None):
         if variant not in ("numpy", "cupy", "torch"):
             raise ValueError("variant must be 'numpy', 'cupy' or 'torch'")
         # mppi_race_car_cupy.py is the NumPy file with cp. for np.; mppi_race_car_torch.py differs in its moving
@@ -603,7 +627,7 @@ class MPPIRacecarController(_ControllerBase):
         self.max_accel_abs = _num(max_accel_abs)
         self.vehicle_w, self.vehicle_l = 3.0, 4.0  # mppi_race_car_obstacle.py:53-54
         self.collision_safety_margin_rate = _num(collision_safety_margin_rat)
-        self._has_obstacles = obstacle_circles is not None or obstacle_tracks is not None
+        self._has_obstacles = obstacle_circles is not None or obstacle_tracks is not None or cost_grid is not None
         if self.T < 5:  # the padded 'same' convolution cannot be sliced back to T rows (mppi_race_car.py:220)
             raise ValueError(f"could not broadcast input array into shape ({self.T},)")
         cfg = dict(
@@ -622,7 +646,7 @@ class MPPIRacecarController(_ControllerBase):
             safety_margin=self.collision_safety_margin_rate, vehicle_w=self.vehicle_w, vehicle_l=self.vehicle_l,
         )
         self._finish_init(cfg, ref_path, obstacle_circles, precision, device, seed, process_group, obstacle_velocities,
-                          obstacle_tracks)
+                          obstacle_tracks, cost_grid)
 
     prev_waypoints_idx = property(_ControllerBase._get_idx, _ControllerBase._set_idx)
 

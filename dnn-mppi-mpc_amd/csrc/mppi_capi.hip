@@ -157,6 +157,19 @@ struct mppi_handle {
     std::vector<TrackOwn> own_tracks;
     DevBuf<TrackSet> d_tracks;
     int tracks_max = 0;  // the largest set among the agents, kept by upload_tracks (0: a handle that never had any)
+    // Cost grids (mppi_set_cost_grid): the grid every agent shares, what mppi_set_agent_cost_grid gave an agent instead
+    // (own_grids[a], several agents only), and d_grids, the descriptors the grid forms read (GridSet<R>[n_agents]): every
+    // agent's view, rewritten by every setter (grid_of, upload_grids) and allocated by the first one.
+    struct GridOwn {  // (move-only)
+        DevBuf<void> d_cells;  // R[ny][nx]
+        int nx = 0, ny = 0;    // (0: none)
+        bool has = false;      // an agent's own entry stands in place of the shared one (also an own "none")
+        double ox = 0, oy = 0, inv = 0, weight = 0, lethal = 0;
+    };
+    GridOwn grid;
+    std::vector<GridOwn> own_grids;
+    DevBuf<void> d_grids;
+    bool any_grid = false;  // some agent has a grid, kept by upload_grids (false: a handle that never had one, or cleared)
     DevBuf<int> d_pout;
     DevBuf<void> d_partials;        // block records in the handle's precision
     DevBuf<double> d_w, d_trace;
@@ -252,9 +265,14 @@ static const mppi_handle::TrackOwn &tracks_of(const mppi_handle *h, int a) {
 // the largest track set among the agents (0: no agent has tracks and the handle is one that never had any); a field, so that
 // the per-iteration parameter packing of a handle without tracks does what it did
 static int max_tracks(const mppi_handle *h) { return h->tracks_max; }
+// Agent a's cost grid: what it was given for itself, else the shared one
+static const mppi_handle::GridOwn &grid_of(const mppi_handle *h, int a) {
+    return a < (int)h->own_grids.size() && h->own_grids[a].has ? h->own_grids[a] : h->grid;
+}
 // some agent has obstacles: the obstacle instantiations serve and the records carry collision counts
 static bool any_obstacles(const mppi_handle *h) {
     if (max_tracks(h) > 0) return true;  // (tracks stand in no circle table: a handle may have tracks and no circles)
+    if (h->any_grid) return true;        // (nor does a grid)
     if (h->fleet) return true;  // (the mates: rows of every table, or -- plan mode, where an agent may have n_obs = 0 -- their plans)
     for (int a = 0; a < h->B; ++a)
         if (scene_of(h, a).n_obs > 0) return true;
@@ -279,6 +297,7 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
 template <typename R> static RolloutPlan front_plan(const mppi_handle *h, const KParams<R> &P);
 static int upload_scenes(mppi_handle *h);
 static int upload_tracks(mppi_handle *h);
+static int upload_grids(mppi_handle *h);
 static void drop_graph(mppi_handle *h);
 static int build_fleet_tables(mppi_handle *h, int only);
 
@@ -691,6 +710,9 @@ static int set_tracks_impl(mppi_handle *h, const char *who, int agent, const dou
                                       "parameter words (limit: fleet_radius = 0)", who);
     if (!h->fused)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: obstacle tracks are served for horizons T <= 128 (T = %d runs the unfused rollout)", who, h->cfg.T);
+    if (h->any_grid)
+        FAIL(h, MPPI_ERR_STATE, "%s: the handle has a cost grid, which uses the same parameter words (limit: remove it first, "
+                                "mppi_set_cost_grid with cells = NULL)", who);
     if (agent >= h->B || (agent < 0 && agent != -1)) FAIL(h, MPPI_ERR_BAD_ARG, "%s: agent %d not in [0, %d)", who, agent, h->B);
     if (n < 0 || n > TRACKS_MAX) FAIL(h, MPPI_ERR_SHAPE, "%s: n = %d tracks, not in [0, %d]", who, n, TRACKS_MAX);
     if (n > 0 && (L < 1 || L > TRACK_LEN_MAX)) FAIL(h, MPPI_ERR_SHAPE, "%s: L = %d points per track, not in [1, %d]", who, L, TRACK_LEN_MAX);
@@ -772,6 +794,120 @@ extern "C" int mppi_get_obstacle_tracks_at(mppi_handle *h, int32_t agent, int32_
             xyr_out[3 * m + 2] = t.radius[m];
         }
         return MPPI_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// cost grids
+// ------------------------------------------------------------------------------------------
+// The grid forms' table (GridSet<R>[n_agents]), rewritten from the host's view of every agent (the caller has synchronised the
+// device).  It is read at run time, so a replayed graph sees the new grids; the table's address, which a launch carries by
+// value in KParams, stays for the handle's life.
+static int upload_grids(mppi_handle *h) {
+    if (!h->d_grids) return MPPI_OK;
+    h->any_grid = false;
+    return with_real(h, [&](auto r) -> int {
+        using R = decltype(r);
+        std::vector<GridSet<R>> tab(h->B);
+        for (int a = 0; a < h->B; ++a) {
+            const mppi_handle::GridOwn &g = grid_of(h, a);
+            h->any_grid |= g.nx > 0;
+            tab[a] = GridSet<R>{static_cast<const R *>(g.d_cells.get()), g.nx, g.ny, (R)g.ox, (R)g.oy, (R)g.inv, (R)g.weight, (R)g.lethal};
+        }
+        HIPCHECK(h, hipMemcpy(h->d_grids, tab.data(), sizeof(GridSet<R>) * tab.size(), hipMemcpyHostToDevice));
+        return MPPI_OK;
+    });
+}
+
+// agent < 0: the grid every agent shares.  Everything that can refuse the call stands before the device is touched; new
+// buffers are allocated into locals and moved in, so a failed allocation leaves the previous grid.  A grid of the shape the
+// entry already has is copied into its buffer: the descriptor's addresses, the plan and a cached graph stay.
+static int set_grid_impl(mppi_handle *h, const char *who, int agent, const double *cells, int32_t nx, int32_t ny, double ox, double oy,
+                         double resolution, double weight, double lethal) {
+    if (!h->cfg.obstacle_motion)
+        FAIL(h, MPPI_ERR_STATE, "%s: the handle was created with obstacle_motion = 0; a cost grid needs "
+                                "mppi_config.obstacle_motion = 1 at mppi_create", who);
+    if (h->fleet)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: a fleet handle (fleet_radius > 0) takes no cost grid: its plan mode uses the same "
+                                      "parameter words (limit: fleet_radius = 0)", who);
+    if (!h->fused)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: cost grids are served for horizons T <= 128 (T = %d runs the unfused rollout)", who, h->cfg.T);
+    if (max_tracks(h) > 0)
+        FAIL(h, MPPI_ERR_STATE, "%s: the handle has obstacle tracks, which use the same parameter words (limit: remove them first, "
+                                "mppi_set_obstacle_tracks with n = 0)", who);
+    if (agent >= h->B || (agent < 0 && agent != -1)) FAIL(h, MPPI_ERR_BAD_ARG, "%s: agent %d not in [0, %d)", who, agent, h->B);
+    const bool clear = !cells || nx == 0;
+    if (!clear) {
+        if (nx < GRID_DIM_MIN || nx > GRID_DIM_MAX || ny < GRID_DIM_MIN || ny > GRID_DIM_MAX)
+            FAIL(h, MPPI_ERR_BAD_ARG, "%s: a grid of %d x %d nodes, each side not in [%d, %d]", who, nx, ny, GRID_DIM_MIN, GRID_DIM_MAX);
+        if (!std::isfinite(ox) || !std::isfinite(oy)) FAIL(h, MPPI_ERR_BAD_ARG, "%s: the origin (%g, %g) is not finite", who, ox, oy);
+        if (!std::isfinite(resolution) || !(resolution > 0)) FAIL(h, MPPI_ERR_BAD_ARG, "%s: resolution %g is not finite and > 0", who, resolution);
+        if (!std::isfinite(weight) || weight < 0) FAIL(h, MPPI_ERR_BAD_ARG, "%s: weight %g is not finite and >= 0", who, weight);
+        if (std::isnan(lethal) || !(lethal > 0)) FAIL(h, MPPI_ERR_BAD_ARG, "%s: lethal %g is not > 0 (+inf: soft cost only)", who, lethal);
+        for (size_t i = 0; i < (size_t)nx * ny; ++i)
+            if (!std::isfinite(cells[i])) FAIL(h, MPPI_ERR_BAD_ARG, "%s: cell (%zu, %zu) is not finite", who, i % nx, i / nx);
+    }
+    if (clear && !h->d_grids) return MPPI_OK;  // (nothing to remove: the handle stays the one that never called the setter)
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    mppi_handle::GridOwn *cur = agent < 0 ? &h->grid : !h->own_grids.empty() ? &h->own_grids[agent] : nullptr;
+    // (the shared setter takes back what the agent setter gave, so it keeps its buffers only while no agent has an own entry)
+    bool own_any = false;
+    for (const mppi_handle::GridOwn &o : h->own_grids) own_any |= o.has;
+    const bool same = !clear && cur && cur->nx == nx && cur->ny == ny && (agent < 0 ? !own_any : cur->has);
+    DevBuf<void> buf, table;
+    if (!clear && !same) HIPCHECK(h, buf.alloc(rsz(h) * (size_t)nx * ny));
+    if (!h->d_grids) HIPCHECK(h, table.alloc(sizeof(GridSet<double>) * (size_t)h->B));
+    if (!clear)
+        if (int rc = upload_real(h, same ? cur->d_cells.get() : buf.get(), cells, (size_t)nx * ny)) return rc;
+    // (nothing below refuses)
+    if (table) h->d_grids = std::move(table);
+    if (agent < 0) {
+        for (mppi_handle::GridOwn &o : h->own_grids) o = mppi_handle::GridOwn{};
+    } else if (h->own_grids.empty()) {
+        h->own_grids.resize(h->B);
+    }
+    mppi_handle::GridOwn &g = agent < 0 ? h->grid : h->own_grids[agent];
+    if (!same) g.d_cells = std::move(buf);
+    g.nx = clear ? 0 : nx;
+    g.ny = clear ? 0 : ny;
+    g.has = agent >= 0;
+    g.ox = ox; g.oy = oy; g.inv = clear ? 0.0 : 1.0 / resolution; g.weight = weight; g.lethal = lethal;
+    h->dev_loop_primed = false;
+    if (!same) drop_graph(h);
+    return upload_grids(h);
+}
+
+extern "C" int mppi_set_cost_grid(mppi_handle *h, const double *cells, int32_t nx, int32_t ny, double origin_x, double origin_y,
+                                  double resolution, double weight, double lethal) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    return set_grid_impl(h, "mppi_set_cost_grid", -1, cells, nx, ny, origin_x, origin_y, resolution, weight, lethal);
+}
+extern "C" int mppi_set_agent_cost_grid(mppi_handle *h, int32_t agent, const double *cells, int32_t nx, int32_t ny, double origin_x,
+                                        double origin_y, double resolution, double weight, double lethal) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (agent < 0) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_agent_cost_grid: agent %d not in [0, %d)", agent, h->B);
+    return set_grid_impl(h, "mppi_set_agent_cost_grid", h->B == 1 && agent == 0 ? -1 : agent, cells, nx, ny, origin_x, origin_y,
+                         resolution, weight, lethal);
+}
+// the raw value of agent `agent`'s grid at n points, from the device helper the rollout prices with (grid_value)
+extern "C" int mppi_eval_cost_grid(mppi_handle *h, int32_t agent, const double *xy, int32_t n, double *value) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (!xy || !value || n < 1) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_cost_grid: bad argument");
+    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_cost_grid: agent %d not in [0, %d)", agent, h->B);
+    if (grid_of(h, agent).nx == 0) FAIL(h, MPPI_ERR_STATE, "mppi_eval_cost_grid: agent %d has no cost grid", agent);
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    return with_real(h, [&](auto r) -> int {
+        using R = decltype(r);
+        const KParams<R> P = make_params<R>(h, nullptr);
+        DevBuf<R> dxy, dout;
+        HIPCHECK(h, dxy.alloc(sizeof(R) * (size_t)n * 2));
+        HIPCHECK(h, dout.alloc(sizeof(R) * (size_t)n));
+        if (int rc = upload_real(h, dxy, xy, (size_t)n * 2)) return rc;
+        launch_eval_grid_at<R>(P, EVAL_GRID_POINTS, agent, dxy, nullptr, nullptr, n, dout, nullptr);
+        HIPCHECK(h, hipGetLastError());
+        HIPCHECK(h, hipDeviceSynchronize());
+        return download_real(h, value, dout, (size_t)n);
     });
 }
 
@@ -1214,6 +1350,8 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     }
     // (obstacle tracks, never on a fleet handle: the descriptors and the launch's staged bytes, sized by the largest set)
     if (const int n_max = max_tracks(h)) set_tracks<R>(P, h->d_tracks, n_max);
+    // (a cost grid, never beside tracks or on a fleet handle: the descriptors)
+    if (h->any_grid) set_grids<R>(P, h->d_grids.get());
     return P;
 }
 
@@ -1272,8 +1410,8 @@ static FinalizeParams make_finalize(const mppi_handle *h, int plant, const void 
     F.n_ref = sc0.n_ref;
     F.window = c.search_window;
     F.is_f64 = h->f64;
-    // (2: every agent counts, also one without rows of its own -- its mates' plans, or its obstacle tracks)
-    F.count_hits = h->fleet_plan || (h->B > 1 && max_tracks(h) > 0) ? 2 : any_obstacles(h);
+    // (2: every agent counts, also one without rows of its own -- its mates' plans, its obstacle tracks or its cost grid)
+    F.count_hits = h->fleet_plan || (h->B > 1 && (max_tracks(h) > 0 || h->any_grid)) ? 2 : any_obstacles(h);
     F.beta = record_beta(h);
     F.dt = c.delta_t;
     F.wheel_base = c.wheel_base;
@@ -2377,6 +2515,7 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
             if (h->fleet) launch_fleet_rows<R>(make_fleet(h, 0), nullptr);  // agent 0's mates as of the current states
             if (h->fleet_plan) launch_eval_plan_at<R>(P, what, dx, di, ds, n, dout, nullptr);
             else if (tracks_of(h, 0).n > 0) launch_eval_tracks_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+            else if (grid_of(h, 0).nx > 0) launch_eval_grid_at<R>(P, what, 0, dx, di, ds, n, dout, nullptr);
             else launch_eval_at<R>(P, what, dx, di, ds, n, dout, nullptr);
         }
         else

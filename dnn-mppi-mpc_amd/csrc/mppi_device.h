@@ -320,6 +320,20 @@ __device__ __forceinline__ bool tracks_collided(const KParams<R> &P, const PlanP
     return hit;
 }
 
+// Cost grids (mppi_set_cost_grid): the bilinear value of grid G at this lane's position, in R.  The positions differ per lane,
+// so every lane gathers its own cell: the two nodes of row iy and the two of row iy + 1, all four reads issued before the
+// first use, so that the lane waits once.  A row pair starts at any node, so it is aligned to one element only: two loads
+// of one element each per row (DESIGN 3.12 says what the compiler makes of them).  grid_index keeps every read inside the
+// table whatever the state is.  A function of its own beside collided(), mates_collided() and tracks_collided().
+template <typename R> __device__ __forceinline__ R grid_value(const GridSet<R> &G, R x, R y) {
+    R fx, fy;
+    const int ix = grid_index(x, G.ox, G.inv, G.nx, fx), iy = grid_index(y, G.oy, G.inv, G.ny, fy);
+    const R *r0 = G.cells + (size_t)iy * G.nx + ix, *r1 = r0 + G.nx;
+    const R a0 = r0[0], a1 = r0[1], b0 = r1[0], b1 = r1[1];
+    const R c0 = fma_(fx, a1 - a0, a0), c1 = fma_(fx, b1 - b0, b0);
+    return fma_(fy, c1 - c0, c0);
+}
+
 // weighted squared tracking error against waypoint i (`_compute_cost` :222-236, `_c` mppi_race_car.py:137-146)
 template <typename R, int MODEL>
 __device__ __forceinline__ R tracking_cost_row(const KParams<R> &P, const R (&w)[4], bool wrap, const R *r, R x, R y, R yaw,

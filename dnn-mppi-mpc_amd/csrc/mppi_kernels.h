@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "mppi_grid_index.h"
+
 namespace mppi {
 
 constexpr int MODEL_DIFF = 0, MODEL_RACE = 1;
@@ -140,8 +142,9 @@ template <typename R> struct KParams {
     const float *eps;  // [K][T][2] or nullptr (Philox); with eps_slots > 0: a ring [eps_slots][n_agents][K][T][2]
     int eps_slots;     // 0: `eps` is this call's tensor; 2^n: iteration i reads slot i mod eps_slots (mppi_set_noise_ring)
     int obs_motion;    // mppi_config.obstacle_motion: the circles carry velocities and the moving instantiations serve; 2
-                       // (OBS_MOTION_TRACKS): some agent has obstacle tracks as well and the track forms serve (this
-                       // word was padding: the layout stays)
+                       // (OBS_MOTION_TRACKS): some agent has obstacle tracks as well and the track forms serve; 3
+                       // (OBS_MOTION_GRID): some agent has a cost grid and the grid forms serve (this word was padding:
+                       // the layout stays)
     R *S;              // [K]
     int *pout;         // [K] waypoint index after sample k (sequential mode)
     DevState *st;
@@ -240,6 +243,33 @@ template <typename R> inline void set_tracks(KParams<R> &P, const TrackSet *sets
     P.pad_scenes[1] = sets ? track_lds_bytes<R>(n_max, P.T) : 0;
     if (sets) P.obs_motion = OBS_MOTION_TRACKS;
 }
+// Cost grids (mppi_set_cost_grid; a handle with obstacle_motion, no fleet and no tracks, so pad_scenes is free): one descriptor
+// per agent in device memory, rewritten by every setter and read afresh by every launch (a replayed graph too).  cells is the
+// table [ny][nx], row-major, node (ix, iy) at the world point (ox + ix / inv, oy + iy / inv); everything in the handle's
+// precision.  nx = 0: the agent has no grid.
+template <typename R> struct alignas(8) GridSet {
+    const R *cells;
+    int nx, ny;
+    R ox, oy, inv, weight, lethal;
+};
+static_assert(sizeof(GridSet<float>) == 40 && sizeof(GridSet<double>) == 56, "GridSet layout");
+constexpr int GRID_DIM_MIN = 2, GRID_DIM_MAX = 4096;
+// KParams::pad_scenes on such a handle: word 0 the address of GridSet<R>[n_agents] (0: no agent has a grid, the SPEC = 3 forms
+// serve), word 1 is 0 (the cells are read from memory: a staged window was tried and cost more).
+// KParams::obs_motion = OBS_MOTION_GRID marks the third user of those words (the planners read it)
+constexpr int OBS_MOTION_GRID = 3;
+template <typename R> __host__ __device__ inline const GridSet<R> *grid_sets(const KParams<R> &P) {
+    return reinterpret_cast<const GridSet<R> *>(P.pad_scenes[0]);
+}
+template <typename R> inline void set_grids(KParams<R> &P, const void *sets) {
+    P.pad_scenes[0] = (long long)reinterpret_cast<uintptr_t>(sets);
+    P.pad_scenes[1] = 0;
+    if (sets) P.obs_motion = OBS_MOTION_GRID;
+}
+// the lower node and the fraction of coordinate x along an axis of n >= 2 nodes (mppi_grid_index.h: inside [0, n - 2] and
+// [0, 1] whatever x is, a NaN included)
+__host__ __device__ inline int grid_index(float x, float o, float inv, int n, float &f) { return mppi_grid_index_f32(x, o, inv, n, &f); }
+__host__ __device__ inline int grid_index(double x, double o, double inv, int n, double &f) { return mppi_grid_index_f64(x, o, inv, n, &f); }
 // (lb_timeout took the place of a padding word: the layout the kernels' argument loads were tuned for stays as it was)
 static_assert(sizeof(KParams<float>) == 424 && sizeof(KParams<double>) == 576, "KParams layout");
 static_assert(offsetof(KParams<float>, hyp) == 376 && offsetof(KParams<double>, hyp) == 528, "KParams layout");
@@ -477,6 +507,12 @@ void launch_eval_plan_at(const KParams<R> &P, int what, const R *x, const int *i
 // point track_index(clock, steps[i], L) (P carries the descriptors: set_tracks; any step >= 0)
 template <typename R>
 void launch_eval_tracks_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
+// launch_eval_at for a handle whose agent 0 has a cost grid: its own circles at steps[i] of their clock, and the grid's value
+// at the state's position in the hit and in the cost (P carries the descriptors: set_grids).  what == EVAL_GRID_POINTS: x is
+// xy[n][2] and out[i] the raw value of agent `agent`'s grid there (idx and steps are not read)
+constexpr int EVAL_GRID_POINTS = 16;
+template <typename R>
+void launch_eval_grid_at(const KParams<R> &P, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s);
 void launch_eval_weights(const double *S, int n, double beta, double *w, hipStream_t s);
 template <typename R> void launch_set_state_dev(const KParams<R> &P, const double *x_dev, int nx, hipStream_t s);

@@ -124,13 +124,28 @@ template <typename R> struct RolloutTracks<R, true> {
         trk_clock = track_clock(sv.iter, ts.iter0, ts.L);
     }
 };
+// What a GRID rollout carries (mppi_set_cost_grid): its agent's descriptor (nx = 0: the agent has no grid).  The other forms'
+// is empty, so that they keep their code.
+template <typename R, bool GRID> struct RolloutGrid {
+    RolloutGrid() = default;
+    __device__ __forceinline__ RolloutGrid(const KParams<R> &, int) {}
+};
+template <typename R> struct RolloutGrid<R, true> {
+    GridSet<R> grid = {nullptr, 0, 0, R(0), R(0), R(0), R(0), R(0)};
+    RolloutGrid() = default;
+    __device__ __forceinline__ RolloutGrid(const KParams<R> &P, int agent) : grid(grid_sets(P)[agent]) {}
+};
 // PLANS (MPPI_FLEET_PLAN, with MOVING): beside its own moving circles the agent tests its mates at the point of their plans
 // that its step owns (mates_collided, mppi_device.h); the table and the threshold travel in KParams.
 // TRACKS (with MOVING, never with PLANS): beside its own moving circles the agent tests its obstacle tracks at the point its
 // step and the set's clock select (tracks_collided, mppi_device.h); k_rollout_fused hands the descriptor over (set_tracks).
-template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVING = false, bool PLANS = false, bool TRACKS = false>
-struct Rollout : RolloutMotion<R, MOVING>, RolloutTracks<R, TRACKS> {
+// GRID (with MOVING, never with PLANS or TRACKS): wherever a state is priced its cost gains weight g and it counts as hit
+// when g >= lethal, g the agent's cost grid at the state's position (grid_value, mppi_device.h; Rollout::costs).
+template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVING = false, bool PLANS = false, bool TRACKS = false,
+          bool GRID = false>
+struct Rollout : RolloutMotion<R, MOVING>, RolloutTracks<R, TRACKS>, RolloutGrid<R, GRID> {
     __device__ __forceinline__ void set_tracks(const RolloutTracks<R, TRACKS> &tk) { static_cast<RolloutTracks<R, TRACKS> &>(*this) = tk; }
+    __device__ __forceinline__ void set_grid(const RolloutGrid<R, GRID> &gr) { static_cast<RolloutGrid<R, GRID> &>(*this) = gr; }
     __device__ __forceinline__ bool use_philox() const { return PLAIN || P.use_philox; }
     __device__ __forceinline__ bool clamp_rollout() const { return PLAIN || P.clamp_rollout; }
     __device__ __forceinline__ bool wrap_stage() const { return !PLAIN && P.wrap_stage; }
@@ -361,8 +376,19 @@ struct Rollout : RolloutMotion<R, MOVING>, RolloutTracks<R, TRACKS> {
         // ---- stage cost of every call (only the last one survives when !accumulate) ------
         const bool last_chunk = ch == n_chunk - 1;
         if (P.accumulate || last_chunk) {
-            const bool hit = OBS ? collided_at(ch, x, y, yaw) : false;
-            const R stage = stage_cost<R, MODEL>(P, wrap_stage(), my_idx, x, y, yaw, vel, hit, u0, u1, v0, v1);
+            bool hit = OBS ? collided_at(ch, x, y, yaw) : false;
+            // GRID: the grid's value at this state -- a lane beyond the horizon reads a node inside the table like any other,
+            // and its cost is never read -- joins the hit and, weighted, both costs of the state (wg = 0: an agent without)
+            R wg = R(0);
+            if constexpr (GRID) {
+                if (this->grid.nx > 0) {
+                    const R g = grid_value(this->grid, x, y);
+                    hit |= g >= this->grid.lethal;
+                    wg = this->grid.weight * g;
+                }
+            }
+            R stage = stage_cost<R, MODEL>(P, wrap_stage(), my_idx, x, y, yaw, vel, hit, u0, u1, v0, v1);
+            if constexpr (GRID) stage += wg;
             if (P.accumulate) {
                 if (sizeof(R) == 4) {
                     // `S[k] += ...` one step at a time (mppi_race_car.py:84): with 1e10 collision penalties
@@ -388,7 +414,8 @@ struct Rollout : RolloutMotion<R, MOVING>, RolloutTracks<R, TRACKS> {
                     p = nearest_uniform(ref, p, window_len<R>(P.window, P.n_ref, p), xt, yt, lane);
                     idx_term = p;
                 }
-                const R term = terminal_cost<R, MODEL>(P, wrap_term(), idx_term, x, y, yaw, vel, hit);
+                R term = terminal_cost<R, MODEL>(P, wrap_term(), idx_term, x, y, yaw, vel, hit);
+                if constexpr (GRID) term += wg;  // (the terminal call prices the same state: with `S[k] =` it is priced twice)
                 s_last = P.accumulate ? term : stage + term;
             }
         }
@@ -637,14 +664,15 @@ __device__ __forceinline__ void per_rollout_thread(const KParams<R> &P, int c, c
 // MULTI: several agents per launch, one row of workgroups (blockIdx.y) each; a single agent compiles to the
 // offset-free code (the offsets cost config 2 half a microsecond per iteration when they were unconditional)
 // SPEC: 0 general, 1 no obstacles, 2 no obstacles + the PLAIN switches (see Rollout), 3 general with moving obstacles, 4 the
-// same with the mates' plans (MULTI only: a mate is another agent of the launch), 5 general, moving, with obstacle tracks
+// same with the mates' plans (MULTI only: a mate is another agent of the launch), 5 general, moving, with obstacle tracks, 6
+// general, moving, with a cost grid (mppi_set_cost_grid)
 // HYPK: the instantiation that can resolve the sequential index in one launch (fused_lookback).  A separate instantiation,
 // picked by the host while the waypoint index can still move (KParams::hyp): carrying that code costs the lean kernel
 // 0.17 us per launch in registers and LDS (A/B on one box), and at the end of the path nothing moves any more.
 template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK = false>
 __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevState *st_pre, KParams<R> P,
                                                                     R *__restrict__ partials) {
-    constexpr bool OBS = SPEC == 0 || SPEC >= 3, PLAIN = SPEC == 2, MOVING = SPEC >= 3, PLANS = SPEC == 4, TRACKS = SPEC == 5;
+    constexpr bool OBS = SPEC == 0 || SPEC >= 3, PLAIN = SPEC == 2, MOVING = SPEC >= 3, PLANS = SPEC == 4, TRACKS = SPEC == 5, GRID = SPEC == 6;
     static_assert(!PLANS || MULTI, "the mates are the other agents of a batched launch");
     static_assert(!(HYPK && MOVING), "the look-back prices the last state with a collision test of its own: static obstacles only");
     const int agent = MULTI ? (int)blockIdx.y : 0;
@@ -707,6 +735,8 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
             if (!(use_win || seq_search)) __syncthreads();  // (else the barrier below serves)
         }
     }
+    // GRID: this agent's descriptor; the cells stay in memory, every workgroup of an XCD reads the same table
+    const RolloutGrid<R, GRID> gr(P, agent);
     if (use_win || seq_search) __syncthreads();
     float e0[NCH], e1[NCH];
     R S_k = R(INFINITY);
@@ -727,9 +757,10 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
         const bool ref_lds = P.n_ref <= PR_REF_LDS;
         if (ref_lds)
             for (int i = threadIdx.x; i < P.n_ref; i += blockDim.x) { sh_pref[2 * i] = P.ref[4 * i]; sh_pref[2 * i + 1] = P.ref[4 * i + 1]; }
-        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS> r(P, sv, k, lane, nullptr, obs, agent, mv);
+        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID> r(P, sv, k, lane, nullptr, obs, agent, mv);
         if constexpr (TRACKS) r.set_tracks(tk);
-        typename Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
+        if constexpr (GRID) r.set_grid(gr);
+        typename Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
         if (valid) sp = r.dynamics(0, e0[0], e1[0]);
         sh_px[wid][lane] = sp.x;
         sh_py[wid][lane] = sp.y;
@@ -741,8 +772,9 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
             S_k = r.finish(false);
         }
     } else if (valid) {
-        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
+        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
         if constexpr (TRACKS) r.set_tracks(tk);
+        if constexpr (GRID) r.set_grid(gr);
         r.sh_first = seq_search ? &sh_first : nullptr;
         if (k >= k_start) {
 #pragma unroll
@@ -2506,6 +2538,43 @@ __global__ __launch_bounds__(256) void k_eval_tracks_at(const KParams<R> P, int 
     }
 }
 
+// k_eval_at for a handle whose agent 0 has a cost grid: its own circles steps[i] rollout steps ahead of their clock, and the
+// grid's value at the state's position -- in the hit (g >= lethal) and, weighted, in the cost, as Rollout::costs prices it.
+// EVAL_GRID_POINTS: x is xy[n][2] and out[i] = the raw value of agent `agent`'s grid there (nothing else is read).
+template <typename R, int MODEL>
+__global__ __launch_bounds__(256) void k_eval_grid_at(const KParams<R> P, int what, int agent, const R *__restrict__ x,
+                                                      const int *__restrict__ idx, const int *__restrict__ steps, int n, R *__restrict__ out) {
+    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
+    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool act = i < n;
+    const GridSet<R> G = grid_sets(P)[agent];
+    if (what == EVAL_GRID_POINTS) {
+        if (act) out[i] = G.nx > 0 ? grid_value(G, x[2 * (size_t)i], x[2 * (size_t)i + 1]) : R(0);
+        return;
+    }
+    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
+    R s[4] = {R(0), R(0), R(0), R(0)};
+    if (act)
+        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
+    const int j = act && steps ? steps[i] : 0;
+    const R tau = obstacle_time(P, obstacle_clock(P.st->iter, P.iter0) + j);
+    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
+    R wg = R(0);
+    if (G.nx > 0) {
+        const R g = grid_value(G, s[0], s[1]);
+        hit |= g >= G.lethal;
+        wg = G.weight * g;
+    }
+    if (what == EVAL_COLLIDED) {
+        if (act) out[i] = hit ? R(1) : R(0);
+    } else {
+        const bool term = what == EVAL_COST_TERMINAL;
+        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
+                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit) + wg;
+        if (act) out[i] = c;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
@@ -2631,8 +2700,11 @@ template <typename R, int MODEL, bool MULTI, int SPW> static KernelLaunch dual_p
 }
 // k_rollout_fused<R, MODEL, NCH, MULTI, SPEC, HYPK>: SPEC 2 the plain form, 1 no obstacles, 0 everything, 3 everything with
 // moving obstacles (never with the look-back: lookback_serves, mppi_capi.hip), 4 the same with the mates' plans (batched
-// launches of a handle that carries a plan table), 5 the moving form with obstacle tracks (some agent has a track set)
+// launches of a handle that carries a plan table), 5 the moving form with obstacle tracks (some agent has a track set), 6 the
+// moving form with a cost grid (some agent has one)
 template <typename R, int MODEL, int NCH, bool MULTI, bool HYPK> static KernelLaunch fused_plan(int spec) {
+    if constexpr (!HYPK)
+        if (spec == 6) return fused_entry<R, MODEL, NCH, MULTI, 6, false>();
     if constexpr (!HYPK)
         if (spec == 5) return fused_entry<R, MODEL, NCH, MULTI, 5, false>();
     if constexpr (!HYPK && MULTI)
@@ -2679,8 +2751,9 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
             // an agent of a batch with no circles of its own then computes what its single-agent handle computes, bit for
             // bit; the forms contract their cost arithmetic differently in the last place)
             const bool tracks = P.obs_motion == OBS_MOTION_TRACKS;  // (never a fleet handle: pad_scenes carries the descriptors)
-            const bool plans = MULTI && P.obs_motion && !tracks && fleet_plan_table(P) != nullptr;
-            const int spec = tracks ? 5 : plans ? 4 : P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
+            const bool grid = P.obs_motion == OBS_MOTION_GRID;  // (likewise, and never with tracks)
+            const bool plans = MULTI && P.obs_motion && !tracks && !grid && fleet_plan_table(P) != nullptr;
+            const int spec = grid ? 6 : tracks ? 5 : plans ? 4 : P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
             p.lookback = !MULTI && MODEL == MODEL_DIFF && P.hyp && P.T <= 64 && !P.obs_motion;  // (the HYPK form: one agent, diff-drive, one chunk)
             p.k = p.lookback  ? fused_plan<R, MODEL_DIFF, 1, false, true>(spec)
                   : P.T <= 64 ? fused_plan<R, MODEL, 1, MULTI, false>(spec)
@@ -2689,10 +2762,11 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
     }
     p.records = blocks;
     p.k.grid = dim3(blocks, MULTI ? P.n_agents : 1);
-    // (the plan forms: the staged table, or 0 -- the memory path)
+    // (the plan forms -- obs_motion == 1: pad_scenes is theirs --: the staged table, or 0 -- the memory path; the grid forms take no
+    // dynamic LDS: their cells are read from memory)
     if (P.obs_motion == OBS_MOTION_TRACKS) {  // (the track forms: the staged windows of the largest set, or 0 -- the memory path)
         if ((P.layout & LAYOUT_KIND) == LAYOUT_FUSED) p.k.lds = (size_t)track_staged_bytes(P);
-    } else if (MULTI && P.obs_motion && fleet_plan_table(P) != nullptr && (P.layout & LAYOUT_KIND) == LAYOUT_FUSED)
+    } else if (MULTI && P.obs_motion == 1 && fleet_plan_table(P) != nullptr && (P.layout & LAYOUT_KIND) == LAYOUT_FUSED)
         p.k.lds = (size_t)fleet_plan_lds_bytes<R>(P.n_agents, P.T);
     return p;
 }
@@ -2809,6 +2883,12 @@ void launch_eval_tracks_at(const KParams<R> &P, int what, const R *x, const int 
     if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_tracks_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
     else hipLaunchKernelGGL((k_eval_tracks_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
 }
+template <typename R>
+void launch_eval_grid_at(const KParams<R> &P, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
+    const dim3 grid((n + 255) / 256), block(256);
+    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_grid_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, agent, x, idx, steps, n, out);
+    else hipLaunchKernelGGL((k_eval_grid_at<R, MODEL_RACE>), grid, block, 0, s, P, what, agent, x, idx, steps, n, out);
+}
 template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s) {
     if (!F.plans) hipLaunchKernelGGL(k_fleet_rows<R>, dim3(F.n_agents), dim3(64), 0, s, F);
     else if (F.model == MODEL_DIFF) hipLaunchKernelGGL((k_fleet_plan<R, MODEL_DIFF>), dim3(F.n_agents), dim3(64), 0, s, F);
@@ -2868,6 +2948,7 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
     template void launch_fleet_rows<R>(const FleetParams &, hipStream_t);                                            \
     template void launch_eval_plan_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_tracks_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
+    template void launch_eval_grid_at<R>(const KParams<R> &, int, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_filter<R>(const R *, R *, int, int, int, hipStream_t);                                 \
     template void launch_set_state_dev<R>(const KParams<R> &, const double *, int, hipStream_t);                     \
     template void launch_viz<R>(const KParams<R> &, const R *, const R *, long long, float *, float *, hipStream_t);

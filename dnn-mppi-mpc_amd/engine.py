@@ -141,6 +141,33 @@ class Engine:
             self._ck(self.lib.mppi_get_obstacle_tracks_at(self._h, int(agent), int(step), _dp(out), n.value, C.byref(n)))
         return out
 
+    def set_cost_grid(self, cells, origin=(0.0, 0.0), resolution=1.0, weight=1.0, lethal=float("inf"), agent=None):
+        """A costmap priced along every rollout: ``cells`` [ny, nx], ``cells[iy, ix]`` the value at ``origin + (ix, iy) *
+        resolution``, looked up bilinearly at every state's (x, y); the state's cost gains ``weight * g`` and it counts as
+        collided when ``g >= lethal``.  For a handle created with ``obstacle_motion=1``.  ``agent``: as in `set_ref_path`.
+        ``cells=None`` removes the grid (mppi_set_cost_grid / mppi_set_agent_cost_grid)."""
+        if cells is None:
+            c, ny, nx = None, 0, 0
+        else:
+            c = np.ascontiguousarray(cells, dtype=np.float64)
+            if c.ndim != 2:
+                raise ValueError("cells must be a 2-D array [ny, nx]")
+            ny, nx = c.shape
+        ox, oy = (float(v) for v in origin)
+        tail = (_dp(c) if c is not None else None, nx, ny, ox, oy, float(resolution), float(weight), float(lethal))
+        if agent is None:
+            self._ck(self.lib.mppi_set_cost_grid(self._h, *tail))
+        else:
+            self._ck(self.lib.mppi_set_agent_cost_grid(self._h, int(agent), *tail))
+
+    def cost_grid_at(self, xy, agent=0):
+        """The raw value of ``agent``'s cost grid at the points ``xy`` [n, 2], computed by the device function the rollout
+        prices with (mppi_eval_cost_grid)."""
+        p = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        out = np.empty(p.shape[0])
+        self._ck(self.lib.mppi_eval_cost_grid(self._h, int(agent), _dp(p), p.shape[0], _dp(out)))
+        return out
+
     def fleet_clearance(self, reset=False):
         """(min_dist[n_agents], contact_iters[n_agents]) over the iterations run since the handle was made or the last call
         with ``reset=True``: the smallest centre distance of every agent to any mate at the start of an iteration (inf: none

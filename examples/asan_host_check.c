@@ -3,9 +3,11 @@
  * without a device -- are driven with good and bad arguments; ASan reports any out-of-bounds access or leak. */
 #include <math.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "mppi_hip.h"
+#include "mppi_grid_index.h" /* the cost grids' index arithmetic, as the kernels and the host compile it */
 
 static int fails = 0;
 #define EXPECT(cond)                                              \
@@ -82,6 +84,34 @@ int main(void) {
         EXPECT(mppi_set_obstacle_tracks(NULL, &d, &d, 1, 1) == MPPI_ERR_BAD_ARG);
         EXPECT(mppi_set_agent_obstacle_tracks(NULL, 0, &d, &d, 1, 1) == MPPI_ERR_BAD_ARG);
         EXPECT(mppi_get_obstacle_tracks_at(NULL, 0, 0, &d, 1, &m) == MPPI_ERR_BAD_ARG && m == -7 && d == -1.0);
+        /* and the three of the cost grids */
+        EXPECT(mppi_set_cost_grid(NULL, &d, 2, 2, 0.0, 0.0, 1.0, 1.0, 0.5) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_agent_cost_grid(NULL, 0, &d, 2, 2, 0.0, 0.0, 1.0, 1.0, 0.5) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_eval_cost_grid(NULL, 0, &d, 1, &d) == MPPI_ERR_BAD_ARG && d == -1.0);
+    }
+    {   /* the grids' index function stays inside [0, n - 2] and its fraction inside [0, 1] whatever the coordinate is; the
+         * table below is read at both nodes it names, so a wrong index is an out-of-bounds read for ASan */
+        static const double xs[] = {NAN, INFINITY, -INFINITY, 1e30, -1e30, 0.0, -0.0, 1e-30, 0.999999, 1.0, 2.5, 4094.5, 4095.0, 4096.0};
+        static const int ns[] = {2, 3, 7, 4096};
+        for (size_t q = 0; q < sizeof(ns) / sizeof(ns[0]); ++q) {
+            const int n = ns[q];
+            float *row32 = (float *)calloc((size_t)n, sizeof(float));
+            double *row64 = (double *)calloc((size_t)n, sizeof(double));
+            for (size_t i = 0; i < sizeof(xs) / sizeof(xs[0]); ++i) {
+                float f32 = -1.0f;
+                double f64 = -1.0;
+                const int i32 = mppi_grid_index_f32((float)xs[i], 0.0f, 1.0f, n, &f32);
+                const int i64 = mppi_grid_index_f64(xs[i], 0.0, 1.0, n, &f64);
+                EXPECT(i32 >= 0 && i32 <= n - 2 && f32 >= 0.0f && f32 <= 1.0f);
+                EXPECT(i64 >= 0 && i64 <= n - 2 && f64 >= 0.0 && f64 <= 1.0);
+                EXPECT(row32[i32] + row32[i32 + 1] == 0.0f && row64[i64] + row64[i64 + 1] == 0.0);
+            }
+            /* a shifted and scaled axis: o = -3, resolution 0.5 */
+            float f = -1.0f;
+            EXPECT(mppi_grid_index_f32(-2.25f, -3.0f, 2.0f, n, &f) == (n > 2 ? 1 : 0) && f == (n > 2 ? 0.5f : 1.0f));
+            free(row32);
+            free(row64);
+        }
     }
     c.obstacle_model = MPPI_OBSTACLE_NONE;
     c.obstacle_motion = 0;

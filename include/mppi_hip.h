@@ -515,6 +515,42 @@ int mppi_set_agent_obstacle_tracks(mppi_handle *h, int32_t agent, const double *
  * {R(xy)[m][min(c + step, L - 1)], radius[m]} for its n tracks (for visualisation and tests).  *n_out is written even when cap
  * is too small (MPPI_ERR_SHAPE then). */
 int mppi_get_obstacle_tracks_at(mppi_handle *h, int32_t agent, int32_t step, double *xyr_out, int32_t cap, int32_t *n_out);
+/* COST GRIDS: a costmap -- a lidar or occupancy grid, inflated -- priced along every rollout by bilinear lookup, whatever the
+ * scene holds.  The setters work on a handle created with obstacle_motion = 1 (any other: MPPI_ERR_STATE).
+ * STORAGE.  cells is a host array [ny][nx], row-major: cells[iy][ix] is the value at the world point (origin_x + ix resolution,
+ * origin_y + iy resolution).  Cells, origin, inv = 1 / resolution (divided in double), weight and lethal are stored rounded once
+ * to the handle's precision R; nothing else is kept.
+ * THE VALUE at a state's position (x, y), all in R:
+ *     gx = fmin(fmax((x - ox) inv, 0), nx - 1);   ix = min((int)gx, nx - 2);   fx = gx - ix;        (the same for y)
+ *     c0 = fma(fx, G[iy][ix+1]   - G[iy][ix],   G[iy][ix]);
+ *     c1 = fma(fx, G[iy+1][ix+1] - G[iy+1][ix], G[iy+1][ix]);
+ *     g  = fma(fy, c1 - c0, c0)
+ * A node returns its cell exactly (the last node of an axis, where ix = nx - 2 and fx = 1: a + (b - a), the cell to one rounding
+ * of the difference); outside the grid the edge value continues; a non-finite coordinate lands on an edge node (NaN: node 0 of
+ * its axis); every read stays inside the table whatever the state is.
+ * PRICING.  Wherever the handle adds the collision penalty -- every stage call it prices, and the terminal call -- the state's
+ * cost also gains weight g, and the state counts as hit when g >= lethal or a circle says so.  With accumulate_stage_cost = 0
+ * the last state is therefore priced twice, as the penalty is.  lethal = +inf: soft cost only.  mppi_stats.n_collided keeps its
+ * definition (S >= collision_penalty); an agent with a grid and no circles counts its hits.  Both dynamics models sample the
+ * state's (x, y) only (no footprint).  The handle's circles, static or moving, are priced exactly as before, beside the grid.
+ * The grid has no clock: it stands until replaced.  cells == NULL or nx == 0 removes it: the handle is then bit for bit the
+ * handle that never called the setter.  A re-upload of the same nx x ny reuses the buffers and keeps a cached graph
+ * (MPPI_GRAPH=1): the rolling-costmap loop; origin, resolution, weight and lethal may change with it.
+ * BATCHES.  mppi_set_cost_grid gives every agent the same grid (and takes back what the agent setter gave);
+ * mppi_set_agent_cost_grid gives one agent a grid of its own, of any shape, or (cells == NULL) none.
+ * mppi_eval_cost, mppi_eval_is_collided and mppi_eval_is_collided_at include agent 0's grid.
+ * REFUSALS leave the scene as it was.  A handle that has obstacle tracks: MPPI_ERR_STATE (and the track setters refuse a
+ * handle that has a grid: both use the same parameter words).  A fleet handle (fleet_radius > 0) or a horizon T > 128 (the
+ * unfused rollout): MPPI_ERR_UNSUPPORTED.  nx or ny outside [2, 4096], a non-finite cell or origin, resolution not finite
+ * or not > 0, weight not finite or < 0, lethal NaN or <= 0, an agent outside [0, n_agents), a NULL handle: MPPI_ERR_BAD_ARG.
+ * Like every setter this synchronises. */
+int mppi_set_cost_grid(mppi_handle *h, const double *cells, int32_t nx, int32_t ny, double origin_x, double origin_y,
+                       double resolution, double weight, double lethal);
+int mppi_set_agent_cost_grid(mppi_handle *h, int32_t agent, const double *cells, int32_t nx, int32_t ny, double origin_x,
+                             double origin_y, double resolution, double weight, double lethal);
+/* The raw value g of agent `agent`'s grid at n points xy [n][2], from the device function the rollout prices with (for
+ * visualisation and tests).  An agent without a grid: MPPI_ERR_STATE. */
+int mppi_eval_cost_grid(mppi_handle *h, int32_t agent, const double *xy, int32_t n, double *value);
 int mppi_eval_nearest_waypoint(mppi_handle *h, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
                                int32_t *idx_out);
 int mppi_eval_cost(mppi_handle *h, int32_t terminal, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
