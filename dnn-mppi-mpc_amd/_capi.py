@@ -25,6 +25,7 @@ OBSTACLE_NONE, OBSTACLE_CIRCLE, OBSTACLE_OUTLINE = 0, 1, 2
 OK, ERR_BAD_ARG, ERR_SHAPE, ERR_NO_DEVICE, ERR_HIP, ERR_PATH_END, ERR_UNSUPPORTED, ERR_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 ERR_COMM = -8
 FLEET_VELOCITY, FLEET_PLAN = 0, 1  # mppi_set_fleet_prediction
+SCENE_EXCLUSIVE, SCENE_COMPOSED = 0, 1  # mppi_set_scene_mode
 LAYOUT_FUSED, LAYOUT_DUAL, LAYOUT_PAIR, LAYOUT_TRI, LAYOUT_KIND, LAYOUT_TWICE = 0, 1, 2, 3, 3, 4  # mppi_get_rollout_layout (KIND: mask)
 
 
@@ -148,6 +149,8 @@ PROTOTYPES = {
     "mppi_set_agent_cost_grid": (C.c_int, [_H, C.c_int32, _D, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
                                            C.c_double]),
     "mppi_eval_cost_grid": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D]),
+    "mppi_set_scene_mode": (C.c_int, [_H, C.c_int32]),
+    "mppi_get_scene_mode": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "mppi_eval_nearest_waypoint": (C.c_int, [_H, _D, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "mppi_eval_cost": (C.c_int, [_H, C.c_int32, _D, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _D, C.POINTER(C.c_int32)]),
     "mppi_eval_moving_average": (C.c_int, [_H, _D, _D]),

@@ -49,7 +49,7 @@ class _ControllerBase:
     _ref_dtype = np.float64
 
     def _finish_init(self, cfg, ref_path, obstacle_circles, precision, device, seed, process_group, obstacle_velocities=None,
-                     obstacle_tracks=None, cost_grid=None):
+                     obstacle_tracks=None, cost_grid=None, compose_scene=False):
         if obstacle_velocities is not None and obstacle_circles is None:
             raise ValueError("obstacle_velocities needs obstacle_circles")
         # a create-time switch (mppi_config.obstacle_motion): any of the three keywords sets it
@@ -76,6 +76,8 @@ class _ControllerBase:
             self.obstacle_velocities = obstacle_velocities
         elif obstacle_circles is not None:
             self.obstacle_circles = obstacle_circles
+        if compose_scene:  # before the two setters below, which refuse each other on an exclusive handle
+            self._engine.set_scene_mode("composed")
         self._tracks = None
         if obstacle_tracks is not None:
             self.obstacle_tracks = obstacle_tracks
@@ -219,7 +221,8 @@ class _ControllerBase:
         """``(xy [n, L, 2], radii [n])``: obstacles given as predicted positions, one per control step from the moment they are
         assigned (a track holds its last point afterwards), or None.  They are priced beside ``obstacle_circles``.  The
         controller must have been built with ``obstacle_tracks`` or ``obstacle_velocities`` (the switch is a create-time
-        one); assigning ``(empty, empty)`` removes them."""
+        one); assigning ``(empty, empty)`` removes them.  Tracks and a ``cost_grid`` together need a controller built with
+        ``compose_scene=True`` (`Engine.set_scene_mode`)."""
         return self._tracks
 
     @obstacle_tracks.setter
@@ -501,7 +504,7 @@ class MPPIAlgorithms(_ControllerBase):
                  safety_margin_rate=None, visualize_optimal_traj=True, visualze_sampled_trajs=True,
                  visualize_sampled_traj=None, *, variant="numpy", precision="f32", device=0, seed=0,
                  process_group=None, waypoint_mode=None, learned_dynamics=None, learned_scalers=None,
-                 obstacle_velocities=None, obstacle_tracks=None, cost_grid=None):
+                 obstacle_velocities=None, obstacle_tracks=None, cost_grid=None, compose_scene=False):
         if visualize_sampled_traj is not None:  # the torch variant's spelling (:63-64)
             visualze_sampled_trajs = visualize_sampled_traj
         self.delta_t = _num(delta_t)
@@ -554,7 +557,7 @@ class MPPIAlgorithms(_ControllerBase):
             vehicle_w=0.0, vehicle_l=0.0,
         )
         self._finish_init(cfg, ref_path, obstacle_circles, precision, device, seed, process_group, obstacle_velocities,
-                          obstacle_tracks, cost_grid)
+                          obstacle_tracks, cost_grid, compose_scene)
         self._learned = learned_dynamics is not None
         if self._learned:
             self._engine.set_mlp(learned_dynamics, learned_scalers)
@@ -603,7 +606,7 @@ class MPPIRacecarController(_ControllerBase):
                  stage_cost_weight=(50.0, 50.0, 1.0, 20.0), terminal_cost_weight=(50.0, 50.0, 1.0, 20.0),
                  obstacle_circles=None, collision_safety_margin_rat=1.5, visualize_optimal_traj=True,
                  visualze_sampled_trajs=True, *, variant="numpy", precision="f32", device=0, seed=0, process_group=None,
-                 obstacle_velocities=None, obstacle_tracks=None, cost_grid=None):
+                 obstacle_velocities=None, obstacle_tracks=None, cost_grid=None, compose_scene=False):
         if variant not in ("numpy", "cupy", "torch"):
             raise ValueError("variant must be 'numpy', 'cupy' or 'torch'")
         # mppi_race_car_cupy.py is the NumPy file with cp. for np.; mppi_race_car_torch.py differs in its moving
@@ -646,7 +649,7 @@ class MPPIRacecarController(_ControllerBase):
             safety_margin=self.collision_safety_margin_rate, vehicle_w=self.vehicle_w, vehicle_l=self.vehicle_l,
         )
         self._finish_init(cfg, ref_path, obstacle_circles, precision, device, seed, process_group, obstacle_velocities,
-                          obstacle_tracks, cost_grid)
+                          obstacle_tracks, cost_grid, compose_scene)
 
     prev_waypoints_idx = property(_ControllerBase._get_idx, _ControllerBase._set_idx)
 

@@ -170,6 +170,11 @@ struct mppi_handle {
     std::vector<GridOwn> own_grids;
     DevBuf<void> d_grids;
     bool any_grid = false;  // some agent has a grid, kept by upload_grids (false: a handle that never had one, or cleared)
+    // Composed scenes (mppi_set_scene_mode): in MPPI_SCENE_COMPOSED the three above may stand together, and d_scene is the one
+    // SceneTable<R> a launch with two or more of them reads: the addresses of d_plans, d_tracks and d_grids (null: none) and the
+    // mates' threshold, rewritten by every setter that changes an ingredient (upload_scene_table), allocated by the first switch
+    int scene_mode = MPPI_SCENE_EXCLUSIVE;
+    DevBuf<void> d_scene;
     DevBuf<int> d_pout;
     DevBuf<void> d_partials;        // block records in the handle's precision
     DevBuf<double> d_w, d_trace;
@@ -269,6 +274,11 @@ static int max_tracks(const mppi_handle *h) { return h->tracks_max; }
 static const mppi_handle::GridOwn &grid_of(const mppi_handle *h, int a) {
     return a < (int)h->own_grids.size() && h->own_grids[a].has ? h->own_grids[a] : h->grid;
 }
+// composed scenes: how many of {plan mode, tracks on some agent, a grid on some agent} the handle holds; two or more run the
+// composed rollout form behind the SceneTable, fewer the single-ingredient forms with their own carriers
+static bool scene_composed(const mppi_handle *h) { return h->scene_mode == MPPI_SCENE_COMPOSED; }
+static int scene_ingredients(const mppi_handle *h) { return (h->fleet_plan ? 1 : 0) + (max_tracks(h) > 0 ? 1 : 0) + (h->any_grid ? 1 : 0); }
+static bool scene_form(const mppi_handle *h) { return scene_composed(h) && scene_ingredients(h) >= 2; }
 // some agent has obstacles: the obstacle instantiations serve and the records carry collision counts
 static bool any_obstacles(const mppi_handle *h) {
     if (max_tracks(h) > 0) return true;  // (tracks stand in no circle table: a handle may have tracks and no circles)
@@ -686,6 +696,7 @@ extern "C" int mppi_set_agent_obstacles_moving(mppi_handle *h, int32_t agent, co
 // The track forms' table (TrackSet[n_agents]), rewritten from the host's view of every agent (the caller has synchronised the
 // device).  It is read at run time, so a replayed graph sees the new sets; what a launch carries by value -- the table's
 // address and the staged bytes in KParams -- is part of the graph's key.
+static int upload_scene_table(mppi_handle *h);
 static int upload_tracks(mppi_handle *h) {
     if (!h->d_tracks) return MPPI_OK;
     std::vector<TrackSet> tab(h->B);
@@ -696,7 +707,7 @@ static int upload_tracks(mppi_handle *h) {
         tab[a] = TrackSet{t.d_pts.get(), t.d_thr.get(), t.n, t.n > 0 ? t.L : 1, t.iter0};
     }
     HIPCHECK(h, hipMemcpy(h->d_tracks, tab.data(), sizeof(TrackSet) * tab.size(), hipMemcpyHostToDevice));
-    return MPPI_OK;
+    return upload_scene_table(h);
 }
 
 // agent < 0: the set every agent shares.  Everything that can refuse the call stands before the device is touched; the new
@@ -705,12 +716,12 @@ static int set_tracks_impl(mppi_handle *h, const char *who, int agent, const dou
     if (!h->cfg.obstacle_motion)
         FAIL(h, MPPI_ERR_STATE, "%s: the handle was created with obstacle_motion = 0; obstacle tracks need "
                                 "mppi_config.obstacle_motion = 1 at mppi_create", who);
-    if (h->fleet)
+    if (h->fleet && !scene_composed(h))
         FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: a fleet handle (fleet_radius > 0) takes no obstacle tracks: its plan mode uses the same "
                                       "parameter words (limit: fleet_radius = 0)", who);
     if (!h->fused)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: obstacle tracks are served for horizons T <= 128 (T = %d runs the unfused rollout)", who, h->cfg.T);
-    if (h->any_grid)
+    if (h->any_grid && !scene_composed(h))
         FAIL(h, MPPI_ERR_STATE, "%s: the handle has a cost grid, which uses the same parameter words (limit: remove it first, "
                                 "mppi_set_cost_grid with cells = NULL)", who);
     if (agent >= h->B || (agent < 0 && agent != -1)) FAIL(h, MPPI_ERR_BAD_ARG, "%s: agent %d not in [0, %d)", who, agent, h->B);
@@ -815,6 +826,23 @@ static int upload_grids(mppi_handle *h) {
             tab[a] = GridSet<R>{static_cast<const R *>(g.d_cells.get()), g.nx, g.ny, (R)g.ox, (R)g.oy, (R)g.inv, (R)g.weight, (R)g.lethal};
         }
         HIPCHECK(h, hipMemcpy(h->d_grids, tab.data(), sizeof(GridSet<R>) * tab.size(), hipMemcpyHostToDevice));
+        return upload_scene_table(h);
+    });
+}
+
+// The composed form's table (SceneTable<R>), rewritten from the host's view of the three ingredients (the caller has
+// synchronised the device).  It is read at run time, so a replayed graph sees an ingredient come or go as far as the launch it
+// captured still serves; the table's address, which a launch carries by value in KParams, stays for the handle's life.
+static int upload_scene_table(mppi_handle *h) {
+    if (!h->d_scene) return MPPI_OK;
+    const mppi_config &c = h->cfg;
+    const double thr = c.obstacle_model == MPPI_OBSTACLE_CIRCLE ? 0.5 * c.safety_margin + c.fleet_radius : c.fleet_radius;
+    return with_real(h, [&](auto r) -> int {
+        using R = decltype(r);
+        const SceneTable<R> tb = {h->fleet_plan ? static_cast<const PlanPoint<R> *>(h->d_plans.get()) : nullptr,
+                                  max_tracks(h) > 0 ? h->d_tracks.get() : nullptr,
+                                  h->any_grid ? static_cast<const GridSet<R> *>(h->d_grids.get()) : nullptr, (R)(thr * thr)};
+        HIPCHECK(h, hipMemcpy(h->d_scene, &tb, sizeof(tb), hipMemcpyHostToDevice));
         return MPPI_OK;
     });
 }
@@ -827,12 +855,12 @@ static int set_grid_impl(mppi_handle *h, const char *who, int agent, const doubl
     if (!h->cfg.obstacle_motion)
         FAIL(h, MPPI_ERR_STATE, "%s: the handle was created with obstacle_motion = 0; a cost grid needs "
                                 "mppi_config.obstacle_motion = 1 at mppi_create", who);
-    if (h->fleet)
+    if (h->fleet && !scene_composed(h))
         FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: a fleet handle (fleet_radius > 0) takes no cost grid: its plan mode uses the same "
                                       "parameter words (limit: fleet_radius = 0)", who);
     if (!h->fused)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: cost grids are served for horizons T <= 128 (T = %d runs the unfused rollout)", who, h->cfg.T);
-    if (max_tracks(h) > 0)
+    if (max_tracks(h) > 0 && !scene_composed(h))
         FAIL(h, MPPI_ERR_STATE, "%s: the handle has obstacle tracks, which use the same parameter words (limit: remove them first, "
                                 "mppi_set_obstacle_tracks with n = 0)", who);
     if (agent >= h->B || (agent < 0 && agent != -1)) FAIL(h, MPPI_ERR_BAD_ARG, "%s: agent %d not in [0, %d)", who, agent, h->B);
@@ -899,7 +927,8 @@ extern "C" int mppi_eval_cost_grid(mppi_handle *h, int32_t agent, const double *
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     return with_real(h, [&](auto r) -> int {
         using R = decltype(r);
-        const KParams<R> P = make_params<R>(h, nullptr);
+        KParams<R> P = make_params<R>(h, nullptr);
+        if (P.obs_motion == OBS_MOTION_SCENE) set_grids<R>(P, h->d_grids.get());  // (k_eval_grid_at reads the descriptors themselves)
         DevBuf<R> dxy, dout;
         HIPCHECK(h, dxy.alloc(sizeof(R) * (size_t)n * 2));
         HIPCHECK(h, dout.alloc(sizeof(R) * (size_t)n));
@@ -1344,13 +1373,20 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.hyp = index_can_move(h);
     P.lb_seq = 0;
     P.hyp_slots = h->d_hyp_slots;
+    // (a composed handle with two or more of the three below: the one table that points at all of them, and the launch's
+    // staged bytes of plans and tracks; with fewer it takes the single-ingredient carrier like any other handle)
+    if (scene_form(h)) {
+        set_scene<R>(P, h->d_scene.get(), h->fleet_plan ? h->B : 0, max_tracks(h));
+        return P;
+    }
     if (h->fleet_plan) {  // (the threshold as make_fleet packs it for a mate row)
         const double thr = c.obstacle_model == MPPI_OBSTACLE_CIRCLE ? 0.5 * c.safety_margin + c.fleet_radius : c.fleet_radius;
         set_fleet_plan<R>(P, h->d_plans, (R)(thr * thr));
     }
-    // (obstacle tracks, never on a fleet handle: the descriptors and the launch's staged bytes, sized by the largest set)
+    // (obstacle tracks, beside plans or a grid only behind the table above: the descriptors and the launch's staged bytes, sized
+    // by the largest set)
     if (const int n_max = max_tracks(h)) set_tracks<R>(P, h->d_tracks, n_max);
-    // (a cost grid, never beside tracks or on a fleet handle: the descriptors)
+    // (a cost grid, likewise: the descriptors)
     if (h->any_grid) set_grids<R>(P, h->d_grids.get());
     return P;
 }
@@ -2513,7 +2549,8 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
             eval_transition_mlp(h, P, dx, dv, n, dout);
         else if (at) {
             if (h->fleet) launch_fleet_rows<R>(make_fleet(h, 0), nullptr);  // agent 0's mates as of the current states
-            if (h->fleet_plan) launch_eval_plan_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+            if (P.obs_motion == OBS_MOTION_SCENE) launch_eval_scene_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+            else if (h->fleet_plan) launch_eval_plan_at<R>(P, what, dx, di, ds, n, dout, nullptr);
             else if (tracks_of(h, 0).n > 0) launch_eval_tracks_at<R>(P, what, dx, di, ds, n, dout, nullptr);
             else if (grid_of(h, 0).nx > 0) launch_eval_grid_at<R>(P, what, 0, dx, di, ds, n, dout, nullptr);
             else launch_eval_at<R>(P, what, dx, di, ds, n, dout, nullptr);
@@ -2630,6 +2667,10 @@ extern "C" int mppi_set_fleet_prediction(mppi_handle *h, int32_t mode) {
         FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_fleet_prediction: mode %d is neither MPPI_FLEET_VELOCITY nor MPPI_FLEET_PLAN", mode);
     if (!h->fleet)
         FAIL(h, MPPI_ERR_STATE, "mppi_set_fleet_prediction: the handle was created with fleet_radius = 0 (no fleet avoidance)");
+    if (mode == MPPI_FLEET_PLAN && !scene_composed(h) && (max_tracks(h) > 0 || h->any_grid))
+        FAIL(h, MPPI_ERR_STATE, "mppi_set_fleet_prediction: the handle holds %s, which use the same parameter words as the mates' plans "
+                                "(limit: mppi_set_scene_mode with MPPI_SCENE_COMPOSED, or remove them first)",
+             max_tracks(h) > 0 && h->any_grid ? "obstacle tracks and a cost grid" : h->any_grid ? "a cost grid" : "obstacle tracks");
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
     if (mode == MPPI_FLEET_PLAN && !h->d_plans) {
@@ -2641,7 +2682,39 @@ extern "C" int mppi_set_fleet_prediction(mppi_handle *h, int32_t mode) {
     h->dev_loop_primed = false;
     drop_graph(h);
     if (int rc = build_fleet_tables(h, -1)) return rc;  // (the mate rows come or go; iter0 and the own rows stay)
+    if (int rc = upload_scene_table(h)) return rc;
     return upload_scenes(h);
+}
+
+extern "C" int mppi_set_scene_mode(mppi_handle *h, int32_t mode) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (mode != MPPI_SCENE_EXCLUSIVE && mode != MPPI_SCENE_COMPOSED)
+        FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_scene_mode: mode %d is neither MPPI_SCENE_EXCLUSIVE nor MPPI_SCENE_COMPOSED", mode);
+    if (!h->cfg.obstacle_motion)
+        FAIL(h, MPPI_ERR_STATE, "mppi_set_scene_mode: the handle was created with obstacle_motion = 0; fleet plans, obstacle tracks and "
+                                "cost grids need mppi_config.obstacle_motion = 1 at mppi_create");
+    if (!h->fused)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_scene_mode: composed scenes are served for horizons T <= 128 (T = %d runs the unfused rollout)",
+             h->cfg.T);
+    if (mode == MPPI_SCENE_EXCLUSIVE && scene_ingredients(h) > 1)
+        FAIL(h, MPPI_ERR_STATE, "mppi_set_scene_mode: the handle holds%s%s%s, which exclude each other in MPPI_SCENE_EXCLUSIVE "
+                                "(limit: remove all but one first)",
+             h->fleet_plan ? " the mates' plans (MPPI_FLEET_PLAN)" : "", max_tracks(h) > 0 ? (h->fleet_plan ? ", obstacle tracks" : " obstacle tracks") : "",
+             h->any_grid ? (h->fleet_plan || max_tracks(h) > 0 ? " and a cost grid" : " a cost grid") : "");
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    if (mode == MPPI_SCENE_COMPOSED && !h->d_scene) HIPCHECK(h, h->d_scene.alloc(sizeof(SceneTable<double>)));
+    if (mode != h->scene_mode) {
+        h->scene_mode = mode;
+        h->dev_loop_primed = false;
+        drop_graph(h);
+    }
+    return upload_scene_table(h);
+}
+extern "C" int mppi_get_scene_mode(const mppi_handle *h, int32_t *mode) {
+    if (!h || !mode) return MPPI_ERR_BAD_ARG;
+    *mode = h->scene_mode;
+    return MPPI_OK;
 }
 
 extern "C" int mppi_get_fleet_plans(mppi_handle *h, double *xy) {

@@ -7,6 +7,7 @@
 #include <stdio.h>
 
 #include "mppi_grid_index.h"
+#include "mppi_scene_staging.h"
 
 namespace mppi {
 
@@ -266,6 +267,41 @@ template <typename R> inline void set_grids(KParams<R> &P, const void *sets) {
     P.pad_scenes[1] = 0;
     if (sets) P.obs_motion = OBS_MOTION_GRID;
 }
+// Composed scenes (mppi_set_scene_mode: MPPI_SCENE_COMPOSED; a handle that holds at least two of {plans, tracks, a grid}): the
+// three users of pad_scenes behind one carrier.  KParams::obs_motion = OBS_MOTION_SCENE marks a launch whose pad_scenes[0] is
+// the address of ONE SceneTable<R> in device memory -- the handle's, rewritten by every setter and read afresh by every launch
+// (a replayed graph too) -- that points at the per-agent arrays the host keeps anyway; a null pointer: no agent has that
+// ingredient.  pad_scenes[1] carries the two staged byte counts of the launch: the plans' in its low 32 bits, the tracks' in
+// its high 32 bits (0: read from memory); the tracks stand 16-byte aligned behind the plans in dynamic LDS.
+constexpr int OBS_MOTION_SCENE = 4;
+template <typename R> struct alignas(16) SceneTable {
+    const PlanPoint<R> *plans;  // R[n_agents][T + 1][2] (fleet_plan_table), or null
+    const TrackSet *tracks;     // [n_agents], or null
+    const GridSet<R> *grids;    // [n_agents], or null
+    R thr2;                     // the mates' squared threshold (fleet_plan_thr2)
+};
+static_assert(sizeof(SceneTable<float>) == 32 && sizeof(SceneTable<double>) == 32, "SceneTable layout");
+template <typename R> __host__ __device__ inline const SceneTable<R> *scene_table(const KParams<R> &P) {
+    return reinterpret_cast<const SceneTable<R> *>(P.pad_scenes[0]);
+}
+// What a composed launch stages into dynamic LDS: mppi_scene_lds_bytes (mppi_scene_staging.h), one function for the planner,
+// which sizes the launch by it, and -- through pad_scenes[1] -- the kernel.  Plans first, the tracks' window 16-byte aligned
+// behind them, each only if it fits the budget of fleet_plan_lds_bytes; whatever does not fit is read from memory.
+template <typename R> __host__ __device__ inline mppi_scene_staging scene_lds_bytes(int n_plan_agents, int n_max, int T) {
+    return mppi_scene_lds_bytes((int)sizeof(R), n_plan_agents, n_max, T);
+}
+template <typename R> __host__ __device__ inline mppi_scene_staging scene_staged(const KParams<R> &P) {
+    const unsigned long long w = (unsigned long long)P.pad_scenes[1];
+    return mppi_scene_staging{(int)(w & 0xffffffffull), (int)(w >> 32)};
+}
+// (table: the handle's SceneTable<R>; n_plan_agents: n_agents where the handle is in plan mode, else 0; n_max: its largest
+// track set)
+template <typename R> inline void set_scene(KParams<R> &P, const void *table, int n_plan_agents, int n_max) {
+    const mppi_scene_staging s = scene_lds_bytes<R>(n_plan_agents, n_max, P.T);
+    P.pad_scenes[0] = (long long)reinterpret_cast<uintptr_t>(table);
+    P.pad_scenes[1] = (long long)(((unsigned long long)(unsigned)s.tracks << 32) | (unsigned long long)(unsigned)s.plans);
+    P.obs_motion = OBS_MOTION_SCENE;
+}
 // the lower node and the fraction of coordinate x along an axis of n >= 2 nodes (mppi_grid_index.h: inside [0, n - 2] and
 // [0, 1] whatever x is, a NaN included)
 __host__ __device__ inline int grid_index(float x, float o, float inv, int n, float &f) { return mppi_grid_index_f32(x, o, inv, n, &f); }
@@ -513,6 +549,9 @@ void launch_eval_tracks_at(const KParams<R> &P, int what, const R *x, const int 
 constexpr int EVAL_GRID_POINTS = 16;
 template <typename R>
 void launch_eval_grid_at(const KParams<R> &P, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
+// launch_eval_at for a composed handle (P carries the SceneTable: set_scene): agent 0's circles, mates, tracks and grid together
+template <typename R>
+void launch_eval_scene_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s);
 void launch_eval_weights(const double *S, int n, double beta, double *w, hipStream_t s);
 template <typename R> void launch_set_state_dev(const KParams<R> &P, const double *x_dev, int nx, hipStream_t s);

@@ -123,6 +123,18 @@ template <typename R> struct RolloutTracks<R, true> {
         trk_L = ts.L;
         trk_clock = track_clock(sv.iter, ts.iter0, ts.L);
     }
+    // the composed form: the descriptors stand behind the handle's SceneTable (null: no agent has tracks); the uniform words
+    // through readfirstlane, so that they sit in SGPRs whatever the compiler makes of the loads
+    __device__ __forceinline__ RolloutTracks(const TrackSet *sets, const DevState &sv, int agent) {
+        if (sets) {
+            const TrackSet ts = sets[agent];
+            trk_pts = static_cast<const PlanPoint<R> *>(ts.pts);
+            trk_thr2 = static_cast<const R *>(ts.thr2);
+            trk_n = __builtin_amdgcn_readfirstlane(ts.n);
+            trk_L = __builtin_amdgcn_readfirstlane(ts.L);
+            trk_clock = __builtin_amdgcn_readfirstlane(track_clock(sv.iter, ts.iter0, ts.L));
+        }
+    }
 };
 // What a GRID rollout carries (mppi_set_cost_grid): its agent's descriptor (nx = 0: the agent has no grid).  The other forms'
 // is empty, so that they keep their code.
@@ -134,16 +146,41 @@ template <typename R> struct RolloutGrid<R, true> {
     GridSet<R> grid = {nullptr, 0, 0, R(0), R(0), R(0), R(0), R(0)};
     RolloutGrid() = default;
     __device__ __forceinline__ RolloutGrid(const KParams<R> &P, int agent) : grid(grid_sets(P)[agent]) {}
+    // the composed form: the descriptors stand behind the handle's SceneTable (null: no agent has a grid)
+    __device__ __forceinline__ RolloutGrid(const GridSet<R> *sets, int agent) {
+        if (sets) {
+            grid = sets[agent];
+            grid.nx = __builtin_amdgcn_readfirstlane(grid.nx);
+            grid.ny = __builtin_amdgcn_readfirstlane(grid.ny);
+        }
+    }
 };
+// What a SCENE rollout carries (mppi_set_scene_mode, the composed form): where its launch staged the plans and the tracks'
+// windows in dynamic LDS (scene_staged: 0 bytes -- read from memory; the tracks stand at scn_trk_off behind the plans).  The
+// other forms' is empty, so that they keep their code.
+template <typename R, bool SCENE> struct RolloutScene {};
+template <typename R> struct RolloutScene<R, true> {
+    int scn_plan_bytes = 0, scn_trk_bytes = 0, scn_trk_off = 0;
+};
+// the kernel's own copy of its argument as a plan handle's: the table and the threshold where mates_collided reads them
+template <typename R> __device__ __forceinline__ void scene_plan_words(KParams<R> &P, const PlanPoint<R> *plans, R thr2) {
+    P.pad_scenes[0] = (long long)reinterpret_cast<uintptr_t>(plans);
+    P.pad_scenes[1] = 0;
+    __builtin_memcpy(&P.pad_scenes[1], &thr2, sizeof(R));
+}
 // PLANS (MPPI_FLEET_PLAN, with MOVING): beside its own moving circles the agent tests its mates at the point of their plans
 // that its step owns (mates_collided, mppi_device.h); the table and the threshold travel in KParams.
 // TRACKS (with MOVING, never with PLANS): beside its own moving circles the agent tests its obstacle tracks at the point its
 // step and the set's clock select (tracks_collided, mppi_device.h); k_rollout_fused hands the descriptor over (set_tracks).
 // GRID (with MOVING, never with PLANS or TRACKS): wherever a state is priced its cost gains weight g and it counts as hit
 // when g >= lethal, g the agent's cost grid at the state's position (grid_value, mppi_device.h; Rollout::costs).
+// SCENE (the composed form, mppi_set_scene_mode: MOVING, TRACKS and GRID together, PLANS where the launch is batched): the
+// three "never with" above do not hold for it -- a state is hit when any ingredient says so, each one guarded by its
+// descriptor (a null plan table, trk_n == 0, nx == 0: the agent lacks it), and the grid's term joins the costs as in GRID.
 template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVING = false, bool PLANS = false, bool TRACKS = false,
-          bool GRID = false>
-struct Rollout : RolloutMotion<R, MOVING>, RolloutTracks<R, TRACKS>, RolloutGrid<R, GRID> {
+          bool GRID = false, bool SCENE = false>
+struct Rollout : RolloutMotion<R, MOVING>, RolloutTracks<R, TRACKS>, RolloutGrid<R, GRID>, RolloutScene<R, SCENE> {
+    __device__ __forceinline__ void set_scene(const RolloutScene<R, SCENE> &sn) { static_cast<RolloutScene<R, SCENE> &>(*this) = sn; }
     __device__ __forceinline__ void set_tracks(const RolloutTracks<R, TRACKS> &tk) { static_cast<RolloutTracks<R, TRACKS> &>(*this) = tk; }
     __device__ __forceinline__ void set_grid(const RolloutGrid<R, GRID> &gr) { static_cast<RolloutGrid<R, GRID> &>(*this) = gr; }
     __device__ __forceinline__ bool use_philox() const { return PLAIN || P.use_philox; }
@@ -183,7 +220,32 @@ struct Rollout : RolloutMotion<R, MOVING>, RolloutTracks<R, TRACKS>, RolloutGrid
     // collision test of this lane's state after step 64 ch + lane.  MOVING: that state lies j = 64 ch + lane + 1 steps ahead;
     // the terminal call prices the same state, and only lane_last's terminal value is read: j = T there
     __device__ __forceinline__ bool collided_at(int ch, R x, R y, R yaw) const {
-        if constexpr (TRACKS) {  // (a lane beyond the horizon reads the point of step T: its cost is never read)
+        if constexpr (SCENE) {  // (a lane beyond the horizon reads point T of the plans and the tracks: its cost is never read)
+            static_assert(MOVING && TRACKS && GRID, "the composed form carries every ingredient (the plans where it is batched)");
+            // the circle test once, then the mates and the tracks, each from LDS where the launch staged it (the tracks at
+            // their offset behind the plans), else from memory; P's plan words are the kernel's own (scene_plan_words)
+            const ObsLanesMoving<R> tab{obs.x, obs.y, obs.r2, this->vx, this->vy};
+            const int j = 64 * ch + lane + 1;
+            bool hit = collided<MODEL == MODEL_RACE, true>(P, x, y, yaw, tab, false, R(0), R(1), obstacle_time(P, this->clock + j));
+            const int jp = j < P.T ? j : P.T;
+            extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
+            if constexpr (PLANS) {
+                if (fleet_plan_table(P) != nullptr) {
+                    if (this->scn_plan_bytes > 0) hit |= mates_collided(P, reinterpret_cast<const PlanPoint<R> *>(dyn_lds), x, y, yaw, agent, jp);
+                    else hit |= mates_collided(P, fleet_plan_table(P), x, y, yaw, agent, jp);
+                }
+            }
+            if (this->trk_n > 0) {
+                if (this->scn_trk_bytes > 0) {
+                    const PlanPoint<R> *w = reinterpret_cast<const PlanPoint<R> *>(dyn_lds + this->scn_trk_off);
+                    hit |= tracks_collided(P, w + jp, reinterpret_cast<const R *>(w + this->trk_n * (P.T + 1)), this->trk_n, P.T + 1, x, y, yaw);
+                } else {
+                    hit |= tracks_collided(P, this->trk_pts + track_index(this->trk_clock, jp, this->trk_L), this->trk_thr2, this->trk_n,
+                                           this->trk_L, x, y, yaw);
+                }
+            }
+            return hit;
+        } else if constexpr (TRACKS) {  // (a lane beyond the horizon reads the point of step T: its cost is never read)
             static_assert(MOVING && !PLANS, "the track forms extend the moving ones");
             const ObsLanesMoving<R> tab{obs.x, obs.y, obs.r2, this->vx, this->vy};
             const int j = 64 * ch + lane + 1;
@@ -661,23 +723,50 @@ __device__ __forceinline__ void per_rollout_thread(const KParams<R> &P, int c, c
     }
 }
 
+// where a form's descriptors stand: behind the handle's SceneTable for the composed form, behind pad_scenes for the others (the
+// argument picks the constructor of RolloutTracks / RolloutGrid; the other forms' declarations compile to what they were)
+template <bool SCENE, typename R> __device__ __forceinline__ const auto &tracks_src(const KParams<R> &P, const SceneTable<R> &tb) {
+    if constexpr (SCENE) return tb.tracks;
+    else return P;
+}
+template <bool SCENE, typename R> __device__ __forceinline__ const auto &grids_src(const KParams<R> &P, const SceneTable<R> &tb) {
+    if constexpr (SCENE) return tb.grids;
+    else return P;
+}
+
 // MULTI: several agents per launch, one row of workgroups (blockIdx.y) each; a single agent compiles to the
 // offset-free code (the offsets cost config 2 half a microsecond per iteration when they were unconditional)
 // SPEC: 0 general, 1 no obstacles, 2 no obstacles + the PLAIN switches (see Rollout), 3 general with moving obstacles, 4 the
 // same with the mates' plans (MULTI only: a mate is another agent of the launch), 5 general, moving, with obstacle tracks, 6
-// general, moving, with a cost grid (mppi_set_cost_grid)
+// general, moving, with a cost grid (mppi_set_cost_grid), 7 the composed form (mppi_set_scene_mode: a handle that holds at least
+// two of plans, tracks and a grid): moving circles, tracks and a grid, and the mates' plans where MULTI -- each guarded by its
+// descriptor, behind the handle's SceneTable (mppi_kernels.h)
 // HYPK: the instantiation that can resolve the sequential index in one launch (fused_lookback).  A separate instantiation,
 // picked by the host while the waypoint index can still move (KParams::hyp): carrying that code costs the lean kernel
 // 0.17 us per launch in registers and LDS (A/B on one box), and at the end of the path nothing moves any more.
 template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK = false>
 __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevState *st_pre, KParams<R> P,
                                                                     R *__restrict__ partials) {
-    constexpr bool OBS = SPEC == 0 || SPEC >= 3, PLAIN = SPEC == 2, MOVING = SPEC >= 3, PLANS = SPEC == 4, TRACKS = SPEC == 5, GRID = SPEC == 6;
+    constexpr bool SCENE = SPEC == 7;
+    constexpr bool OBS = SPEC == 0 || SPEC >= 3, PLAIN = SPEC == 2, MOVING = SPEC >= 3, PLANS = SPEC == 4 || (SCENE && MULTI),
+                   TRACKS = SPEC == 5 || SCENE, GRID = SPEC == 6 || SCENE;
     static_assert(!PLANS || MULTI, "the mates are the other agents of a batched launch");
+    static_assert(!(HYPK && SCENE), "the composed form extends the moving ones");
     static_assert(!(HYPK && MOVING), "the look-back prices the last state with a collision test of its own: static obstacles only");
     const int agent = MULTI ? (int)blockIdx.y : 0;
     if constexpr (MULTI) agent_scene(P, P.scenes, agent);  // (the agent's view of P: its own path and obstacles, see AgentScene)
     if constexpr (MULTI && MOVING) P.iter0 = P.scenes[agent].iter0;  // (and the clock its own set was uploaded at)
+    // SCENE: the handle's table and the launch's staging, read before P's two words become the plan forms' (scene_plan_words)
+    SceneTable<R> tb = {nullptr, nullptr, nullptr, R(0)};
+    RolloutScene<R, SCENE> sn;
+    if constexpr (SCENE) {
+        tb = *scene_table(P);
+        const mppi_scene_staging stg = scene_staged(P);
+        sn.scn_plan_bytes = PLANS ? __builtin_amdgcn_readfirstlane(stg.plans) : 0;
+        sn.scn_trk_bytes = __builtin_amdgcn_readfirstlane(stg.tracks);
+        sn.scn_trk_off = mppi_scene_track_offset(sn.scn_plan_bytes);
+        scene_plan_words(P, PLANS ? tb.plans : nullptr, tb.thr2);
+    }
     __shared__ R sh_S[FUSED_WAVES];
     __shared__ R sh_e[FUSED_WAVES];
     __shared__ R sh_acc[FUSED_WAVES][128 * NCH];
@@ -708,7 +797,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
     // PLANS: the plan table into dynamic LDS where the planner sized the launch for it (fleet_plan_lds_bytes: the same decision
     // on both sides); every point of every agent, so that the index stays that of the table in memory
     // (Rollout::collided_at reads it; a block of its own, so that the other forms keep their text)
-    if constexpr (PLANS) {
+    if constexpr (PLANS && !SCENE) {
         extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
         if (fleet_plan_lds_bytes<R>(P.n_agents, P.T) > 0) {
             PlanPoint<R> *dst = reinterpret_cast<PlanPoint<R> *>(dyn_lds);
@@ -720,8 +809,8 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
     }
     // TRACKS: the window of T + 1 points per track that this agent's clock selects, then its thresholds, into dynamic LDS where
     // the planner sized the launch for the largest set (KParams::pad_scenes[1]: the launch's decision, the same for every agent)
-    const RolloutTracks<R, TRACKS> tk(P, sv, agent);
-    if constexpr (TRACKS) {
+    const RolloutTracks<R, TRACKS> tk(tracks_src<SCENE>(P, tb), sv, agent);
+    if constexpr (TRACKS && !SCENE) {
         extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
         if (track_staged_bytes(P) > 0) {
             PlanPoint<R> *dst = reinterpret_cast<PlanPoint<R> *>(dyn_lds);
@@ -736,7 +825,30 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
         }
     }
     // GRID: this agent's descriptor; the cells stay in memory, every workgroup of an XCD reads the same table
-    const RolloutGrid<R, GRID> gr(P, agent);
+    const RolloutGrid<R, GRID> gr(grids_src<SCENE>(P, tb), agent);
+    // SCENE: the plans (every point of every agent, as PLANS has them), then -- 16-byte aligned behind them -- this agent's track
+    // windows and thresholds (as TRACKS has them), each where the launch was sized for it; one barrier for both
+    if constexpr (SCENE) {
+        extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
+        if constexpr (PLANS) {
+            if (sn.scn_plan_bytes > 0 && tb.plans != nullptr) {
+                PlanPoint<R> *dst = reinterpret_cast<PlanPoint<R> *>(dyn_lds);
+                const int n_pts = P.n_agents * (P.T + 1);  // (the bytes the launch was sized for: scene_lds_bytes)
+                for (int i = threadIdx.x; i < n_pts; i += blockDim.x) dst[i] = tb.plans[i];
+            }
+        }
+        if (sn.scn_trk_bytes > 0) {
+            PlanPoint<R> *dst = reinterpret_cast<PlanPoint<R> *>(dyn_lds + sn.scn_trk_off);
+            const int n_pts = tk.trk_n * (P.T + 1);  // (n <= the launch's largest set: inside the bytes it was sized for)
+            for (int i = threadIdx.x; i < n_pts; i += blockDim.x) {
+                const int m = i / (P.T + 1), j = i - m * (P.T + 1);
+                dst[i] = tk.trk_pts[(size_t)m * tk.trk_L + track_index(tk.trk_clock, j, tk.trk_L)];
+            }
+            R *thr = reinterpret_cast<R *>(dst + n_pts);
+            for (int m = threadIdx.x; m < tk.trk_n; m += blockDim.x) thr[m] = tk.trk_thr2[m];
+        }
+        if ((sn.scn_plan_bytes > 0 || sn.scn_trk_bytes > 0) && !(use_win || seq_search)) __syncthreads();  // (else the barrier below serves)
+    }
     if (use_win || seq_search) __syncthreads();
     float e0[NCH], e1[NCH];
     R S_k = R(INFINITY);
@@ -757,10 +869,11 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
         const bool ref_lds = P.n_ref <= PR_REF_LDS;
         if (ref_lds)
             for (int i = threadIdx.x; i < P.n_ref; i += blockDim.x) { sh_pref[2 * i] = P.ref[4 * i]; sh_pref[2 * i + 1] = P.ref[4 * i + 1]; }
-        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID> r(P, sv, k, lane, nullptr, obs, agent, mv);
+        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID, SCENE> r(P, sv, k, lane, nullptr, obs, agent, mv);
         if constexpr (TRACKS) r.set_tracks(tk);
         if constexpr (GRID) r.set_grid(gr);
-        typename Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
+        if constexpr (SCENE) r.set_scene(sn);
+        typename Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID, SCENE>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
         if (valid) sp = r.dynamics(0, e0[0], e1[0]);
         sh_px[wid][lane] = sp.x;
         sh_py[wid][lane] = sp.y;
@@ -772,9 +885,10 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
             S_k = r.finish(false);
         }
     } else if (valid) {
-        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
+        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID, SCENE> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
         if constexpr (TRACKS) r.set_tracks(tk);
         if constexpr (GRID) r.set_grid(gr);
+        if constexpr (SCENE) r.set_scene(sn);
         r.sh_first = seq_search ? &sh_first : nullptr;
         if (k >= k_start) {
 #pragma unroll
@@ -2575,6 +2689,55 @@ __global__ __launch_bounds__(256) void k_eval_grid_at(const KParams<R> P, int wh
     }
 }
 
+// k_eval_at for a composed handle (mppi_set_scene_mode; P carries the SceneTable: set_scene): agent 0's own circles steps[i]
+// rollout steps ahead of their clock, its mates at point steps[i] of their plans (kept inside [0, T]), its tracks at the point
+// that step and their clock select, and its grid's value at the state's position in the hit and, weighted, in the cost --
+// k_eval_plan_at, k_eval_tracks_at and k_eval_grid_at in one, each ingredient guarded by its descriptor.  Everything is read
+// from memory.
+template <typename R, int MODEL>
+__global__ __launch_bounds__(256) void k_eval_scene_at(KParams<R> P, int what, const R *__restrict__ x, const int *__restrict__ idx,
+                                                       const int *__restrict__ steps, int n, R *__restrict__ out) {
+    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
+    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const SceneTable<R> tb = *scene_table(P);
+    scene_plan_words(P, tb.plans, tb.thr2);
+    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
+    const bool act = i < n;
+    R s[4] = {R(0), R(0), R(0), R(0)};
+    if (act)
+        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
+    const int j = act && steps ? steps[i] : 0;
+    const int j0 = j < 0 ? 0 : j;
+    const long long iter = P.st->iter;
+    const R tau = obstacle_time(P, obstacle_clock(iter, P.iter0) + j);
+    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
+    if (tb.plans != nullptr) hit |= mates_collided(P, tb.plans, s[0], s[1], s[2], 0, j0 < P.T ? j0 : P.T);
+    if (tb.tracks != nullptr) {
+        const TrackSet ts = tb.tracks[0];
+        if (ts.n > 0) {
+            const int at = track_index(track_clock(iter, ts.iter0, ts.L), j0, ts.L);
+            hit |= tracks_collided(P, static_cast<const PlanPoint<R> *>(ts.pts) + at, static_cast<const R *>(ts.thr2), ts.n, ts.L, s[0], s[1], s[2]);
+        }
+    }
+    R wg = R(0);
+    if (tb.grids != nullptr) {
+        const GridSet<R> G = tb.grids[0];
+        if (G.nx > 0) {
+            const R g = grid_value(G, s[0], s[1]);
+            hit |= g >= G.lethal;
+            wg = G.weight * g;
+        }
+    }
+    if (what == EVAL_COLLIDED) {
+        if (act) out[i] = hit ? R(1) : R(0);
+    } else {
+        const bool term = what == EVAL_COST_TERMINAL;
+        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
+                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit) + wg;
+        if (act) out[i] = c;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
@@ -2701,8 +2864,11 @@ template <typename R, int MODEL, bool MULTI, int SPW> static KernelLaunch dual_p
 // k_rollout_fused<R, MODEL, NCH, MULTI, SPEC, HYPK>: SPEC 2 the plain form, 1 no obstacles, 0 everything, 3 everything with
 // moving obstacles (never with the look-back: lookback_serves, mppi_capi.hip), 4 the same with the mates' plans (batched
 // launches of a handle that carries a plan table), 5 the moving form with obstacle tracks (some agent has a track set), 6 the
-// moving form with a cost grid (some agent has one)
+// moving form with a cost grid (some agent has one), 7 the composed form (a handle in MPPI_SCENE_COMPOSED that holds at least
+// two of plans, tracks and a grid)
 template <typename R, int MODEL, int NCH, bool MULTI, bool HYPK> static KernelLaunch fused_plan(int spec) {
+    if constexpr (!HYPK)
+        if (spec == 7) return fused_entry<R, MODEL, NCH, MULTI, 7, false>();
     if constexpr (!HYPK)
         if (spec == 6) return fused_entry<R, MODEL, NCH, MULTI, 6, false>();
     if constexpr (!HYPK)
@@ -2750,10 +2916,11 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
             // (a handle with obstacle motion takes the moving form whatever its set holds at the moment -- none yet, or m = 0:
             // an agent of a batch with no circles of its own then computes what its single-agent handle computes, bit for
             // bit; the forms contract their cost arithmetic differently in the last place)
-            const bool tracks = P.obs_motion == OBS_MOTION_TRACKS;  // (never a fleet handle: pad_scenes carries the descriptors)
+            const bool scene = P.obs_motion == OBS_MOTION_SCENE;  // (a composed handle with two ingredients or more: the SceneTable)
+            const bool tracks = P.obs_motion == OBS_MOTION_TRACKS;  // (never a fleet handle in plan mode: pad_scenes carries the descriptors)
             const bool grid = P.obs_motion == OBS_MOTION_GRID;  // (likewise, and never with tracks)
-            const bool plans = MULTI && P.obs_motion && !tracks && !grid && fleet_plan_table(P) != nullptr;
-            const int spec = grid ? 6 : tracks ? 5 : plans ? 4 : P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
+            const bool plans = MULTI && P.obs_motion && !scene && !tracks && !grid && fleet_plan_table(P) != nullptr;
+            const int spec = scene ? 7 : grid ? 6 : tracks ? 5 : plans ? 4 : P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
             p.lookback = !MULTI && MODEL == MODEL_DIFF && P.hyp && P.T <= 64 && !P.obs_motion;  // (the HYPK form: one agent, diff-drive, one chunk)
             p.k = p.lookback  ? fused_plan<R, MODEL_DIFF, 1, false, true>(spec)
                   : P.T <= 64 ? fused_plan<R, MODEL, 1, MULTI, false>(spec)
@@ -2764,7 +2931,9 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
     p.k.grid = dim3(blocks, MULTI ? P.n_agents : 1);
     // (the plan forms -- obs_motion == 1: pad_scenes is theirs --: the staged table, or 0 -- the memory path; the grid forms take no
     // dynamic LDS: their cells are read from memory)
-    if (P.obs_motion == OBS_MOTION_TRACKS) {  // (the track forms: the staged windows of the largest set, or 0 -- the memory path)
+    if (P.obs_motion == OBS_MOTION_SCENE) {  // (the composed form: plans and track windows as scene_lds_bytes placed them)
+        if ((P.layout & LAYOUT_KIND) == LAYOUT_FUSED) p.k.lds = (size_t)mppi_scene_lds_total(scene_staged(P));
+    } else if (P.obs_motion == OBS_MOTION_TRACKS) {  // (the track forms: the staged windows of the largest set, or 0 -- the memory path)
         if ((P.layout & LAYOUT_KIND) == LAYOUT_FUSED) p.k.lds = (size_t)track_staged_bytes(P);
     } else if (MULTI && P.obs_motion == 1 && fleet_plan_table(P) != nullptr && (P.layout & LAYOUT_KIND) == LAYOUT_FUSED)
         p.k.lds = (size_t)fleet_plan_lds_bytes<R>(P.n_agents, P.T);
@@ -2889,6 +3058,12 @@ void launch_eval_grid_at(const KParams<R> &P, int what, int agent, const R *x, c
     if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_grid_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, agent, x, idx, steps, n, out);
     else hipLaunchKernelGGL((k_eval_grid_at<R, MODEL_RACE>), grid, block, 0, s, P, what, agent, x, idx, steps, n, out);
 }
+template <typename R>
+void launch_eval_scene_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
+    const dim3 grid((n + 255) / 256), block(256);
+    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_scene_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+    else hipLaunchKernelGGL((k_eval_scene_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+}
 template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s) {
     if (!F.plans) hipLaunchKernelGGL(k_fleet_rows<R>, dim3(F.n_agents), dim3(64), 0, s, F);
     else if (F.model == MODEL_DIFF) hipLaunchKernelGGL((k_fleet_plan<R, MODEL_DIFF>), dim3(F.n_agents), dim3(64), 0, s, F);
@@ -2949,6 +3124,7 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
     template void launch_eval_plan_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_tracks_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_grid_at<R>(const KParams<R> &, int, int, const R *, const int *, const int *, int, R *, hipStream_t); \
+    template void launch_eval_scene_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_filter<R>(const R *, R *, int, int, int, hipStream_t);                                 \
     template void launch_set_state_dev<R>(const KParams<R> &, const double *, int, hipStream_t);                     \
     template void launch_viz<R>(const KParams<R> &, const R *, const R *, long long, float *, float *, hipStream_t);

@@ -185,6 +185,23 @@ class Engine:
             raise capi.MppiError(capi.ERR_BAD_ARG, f"fleet prediction {mode!r} is neither 'velocity' nor 'plan'")
         self._ck(self.lib.mppi_set_fleet_prediction(self._h, modes[mode]))
 
+    def set_scene_mode(self, mode):
+        """``"composed"``: the mates' plans, obstacle tracks and a cost grid may stand together on this handle (the setters'
+        cross-refusals are lifted; a handle that holds two or more runs the composed rollout form, one that holds fewer the
+        launch it always ran).  ``"exclusive"`` (the default): they exclude each other, as the setters document.  Needs
+        ``obstacle_motion=1`` and ``T <= 128``; mppi_set_scene_mode."""
+        modes = {"exclusive": capi.SCENE_EXCLUSIVE, "composed": capi.SCENE_COMPOSED}
+        if mode not in modes:
+            raise capi.MppiError(capi.ERR_BAD_ARG, f"scene mode {mode!r} is neither 'exclusive' nor 'composed'")
+        self._ck(self.lib.mppi_set_scene_mode(self._h, modes[mode]))
+
+    @property
+    def scene_mode(self):
+        """``"exclusive"`` or ``"composed"`` (mppi_get_scene_mode)."""
+        m = C.c_int32(0)
+        self._ck(self.lib.mppi_get_scene_mode(self._h, C.byref(m)))
+        return "composed" if m.value == capi.SCENE_COMPOSED else "exclusive"
+
     def fleet_plans(self):
         """[n_agents, T + 1, 2]: every agent's plan as of the current states and nominal controls -- point 0 its position, point
         j the position after j steps of its nominal sequence (plan mode only; mppi_get_fleet_plans)."""

@@ -8,6 +8,7 @@
 
 #include "mppi_hip.h"
 #include "mppi_grid_index.h" /* the cost grids' index arithmetic, as the kernels and the host compile it */
+#include "mppi_scene_staging.h" /* what a composed launch stages into LDS, likewise */
 
 static int fails = 0;
 #define EXPECT(cond)                                              \
@@ -88,6 +89,32 @@ int main(void) {
         EXPECT(mppi_set_cost_grid(NULL, &d, 2, 2, 0.0, 0.0, 1.0, 1.0, 0.5) == MPPI_ERR_BAD_ARG);
         EXPECT(mppi_set_agent_cost_grid(NULL, 0, &d, 2, 2, 0.0, 0.0, 1.0, 1.0, 0.5) == MPPI_ERR_BAD_ARG);
         EXPECT(mppi_eval_cost_grid(NULL, 0, &d, 1, &d) == MPPI_ERR_BAD_ARG && d == -1.0);
+        /* and the two of the composed scenes: NULL comes first, a good or a bad mode alike */
+        EXPECT(mppi_set_scene_mode(NULL, MPPI_SCENE_COMPOSED) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_scene_mode(NULL, 2) == MPPI_ERR_BAD_ARG && mppi_set_scene_mode(NULL, -1) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_get_scene_mode(NULL, &m) == MPPI_ERR_BAD_ARG && m == -7);
+    }
+    {   /* the composed launches' staging at its budget edges (T = 128: 2064 bytes of plans per agent and 2072 per track in
+         * f64, half of each in f32): plans first, the tracks 16-byte aligned behind them, each only if it fits; a buffer of the
+         * total is written at both regions' last bytes, so a wrong size or offset is an out-of-bounds write for ASan */
+        static const int cases[][6] = {/* elem, plan agents, tracks, T -> plans, tracks */
+            {8, 3, 4, 128, 6192, 8288}, {8, 3, 5, 128, 6192, 0}, {8, 7, 1, 128, 14448, 0}, {8, 8, 7, 128, 0, 14504},
+            {8, 8, 8, 128, 0, 0}, {8, 0, 7, 128, 0, 14504}, {8, 0, 8, 128, 0, 0}, {4, 38, 0, 128, 39216, 0}, {4, 39, 0, 128, 0, 0},
+            {4, 3, 35, 128, 3096, 36260}, {4, 3, 36, 128, 3096, 0}, {4, 39, 38, 128, 0, 39368}, {4, 39, 39, 128, 0, 0},
+            {4, 1, 1, 2, 24, 28}, {4, 0, 0, 50, 0, 0}};
+        for (size_t q = 0; q < sizeof(cases) / sizeof(cases[0]); ++q) {
+            const int *c = cases[q];
+            const mppi_scene_staging s = mppi_scene_lds_bytes(c[0], c[1], c[2], c[3]);
+            const int off = mppi_scene_track_offset(s.plans), total = mppi_scene_lds_total(s);
+            EXPECT(s.plans == c[4] && s.tracks == c[5]);
+            EXPECT(off % 16 == 0 && off >= s.plans && off < s.plans + 16 && total <= (c[0] == 4 ? 40000 : 16384));
+            char *lds = (char *)calloc((size_t)total + 1, 1);
+            if (s.plans > 0) lds[s.plans - 1] = 1;
+            if (s.tracks > 0) { lds[off] = 2; lds[off + s.tracks - 1] = 3; }
+            EXPECT(total == (s.tracks > 0 ? off + s.tracks : s.plans));
+            free(lds);
+        }
+        EXPECT(mppi_scene_track_offset(24) == 32 && mppi_scene_track_offset(32) == 32 && mppi_scene_track_offset(0) == 0);
     }
     {   /* the grids' index function stays inside [0, n - 2] and its fraction inside [0, 1] whatever the coordinate is; the
          * table below is read at both nodes it names, so a wrong index is an out-of-bounds read for ASan */

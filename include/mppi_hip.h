@@ -551,6 +551,30 @@ int mppi_set_agent_cost_grid(mppi_handle *h, int32_t agent, const double *cells,
 /* The raw value g of agent `agent`'s grid at n points xy [n][2], from the device function the rollout prices with (for
  * visualisation and tests).  An agent without a grid: MPPI_ERR_STATE. */
 int mppi_eval_cost_grid(mppi_handle *h, int32_t agent, const double *xy, int32_t n, double *value);
+/* ---- composed scenes: fleet plans, obstacle tracks and a cost grid on one handle ----
+ * By default (MPPI_SCENE_EXCLUSIVE) the mates' plans, the obstacle tracks and the cost grid exclude each other on a handle, as
+ * the three setters document: a handle that never calls this behaves bit for bit as before, refusals and messages included.
+ * MPPI_SCENE_COMPOSED lifts exactly those cross-refusals: a grid beside tracks, and tracks or a grid on a fleet handle (in
+ * either prediction mode).  Every other refusal of mppi_set[_agent]_cost_grid, mppi_set[_agent]_obstacle_tracks and
+ * mppi_set_fleet_prediction stays, with its code and text.
+ * SEMANTICS.  Nothing new is defined: every ingredient keeps what its setter documents -- the tracks their own clock and their
+ * last point, the grid its formula and `lethal`, the plans their thresholds, the handle's circles their pricing -- and a state
+ * counts as hit when ANY of them says so; its cost gains weight g wherever the penalty is added.  mppi_stats.n_collided keeps
+ * its definition.  mppi_eval_is_collided[_at] and mppi_eval_cost see all of agent 0's ingredients; mppi_eval_is_collided_at
+ * refuses a step outside [0, T] only when the mates' plans are among them.  The getters answer as on the exclusive handles.
+ * COST.  A composed handle that holds at most one of {plan mode, tracks on some agent, a grid on some agent} runs the very
+ * launch the exclusive handle runs (bit for bit); with two or more it runs the composed rollout form, which carries all of
+ * them.  Removing ingredients returns the handle to the single-ingredient forms.
+ * ACCEPTED on a handle created with obstacle_motion = 1 (any other: MPPI_ERR_STATE) whose horizon is T <= 128 (longer:
+ * MPPI_ERR_UNSUPPORTED).  A NULL handle or an unknown mode: MPPI_ERR_BAD_ARG.  Switching back to MPPI_SCENE_EXCLUSIVE while
+ * the handle holds more than one of the three: MPPI_ERR_STATE, the message names what is held, nothing changes.  In
+ * MPPI_SCENE_EXCLUSIVE mppi_set_fleet_prediction(MPPI_FLEET_PLAN) refuses (MPPI_ERR_STATE) a handle that holds tracks or a
+ * grid -- which only a handle that was composed before can.  Like every setter this synchronises; a switch drops a cached
+ * graph. */
+#define MPPI_SCENE_EXCLUSIVE 0   /* default: plans, tracks and a grid exclude each other, as documented */
+#define MPPI_SCENE_COMPOSED  1
+int mppi_set_scene_mode(mppi_handle *h, int32_t mode);
+int mppi_get_scene_mode(const mppi_handle *h, int32_t *mode);
 int mppi_eval_nearest_waypoint(mppi_handle *h, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
                                int32_t *idx_out);
 int mppi_eval_cost(mppi_handle *h, int32_t terminal, const double *x, int32_t n, int32_t *prev_idx, int32_t update_prev_idx,
