@@ -26,6 +26,7 @@ OK, ERR_BAD_ARG, ERR_SHAPE, ERR_NO_DEVICE, ERR_HIP, ERR_PATH_END, ERR_UNSUPPORTE
 ERR_COMM = -8
 FLEET_VELOCITY, FLEET_PLAN = 0, 1  # mppi_set_fleet_prediction
 SCENE_EXCLUSIVE, SCENE_COMPOSED = 0, 1  # mppi_set_scene_mode
+GRID_FOOTPRINT_CENTRE, GRID_FOOTPRINT_OUTLINE = 0, 1  # mppi_set_cost_grid_footprint
 LAYOUT_FUSED, LAYOUT_DUAL, LAYOUT_PAIR, LAYOUT_TRI, LAYOUT_KIND, LAYOUT_TWICE = 0, 1, 2, 3, 3, 4  # mppi_get_rollout_layout (KIND: mask)
 
 
@@ -149,6 +150,9 @@ PROTOTYPES = {
     "mppi_set_agent_cost_grid": (C.c_int, [_H, C.c_int32, _D, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
                                            C.c_double]),
     "mppi_eval_cost_grid": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D]),
+    "mppi_set_cost_grid_footprint": (C.c_int, [_H, C.c_int32]),
+    "mppi_get_cost_grid_footprint": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "mppi_eval_cost_grid_footprint": (C.c_int, [_H, C.c_int32, _D, C.c_int32, _D, _D]),
     "mppi_set_scene_mode": (C.c_int, [_H, C.c_int32]),
     "mppi_get_scene_mode": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "mppi_eval_nearest_waypoint": (C.c_int, [_H, _D, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),

@@ -236,7 +236,9 @@ class _ControllerBase:
     @property
     def cost_grid(self):
         """``dict(cells=[ny, nx], origin=(x, y), resolution=..., weight=1.0, lethal=inf)``: a costmap looked up bilinearly at
-        every rollout state (`Engine.set_cost_grid`), priced beside ``obstacle_circles``, or None.  The controller must have
+        every rollout state (`Engine.set_cost_grid`), priced beside ``obstacle_circles``, or None.  The key ``footprint``
+        (``"centre"``, the default, or ``"outline"``: the vehicle's outline is priced, `Engine.set_cost_grid_footprint` -- for
+        the controllers that test the outline against circles) stays in force when the grid is removed.  The controller must have
         been built with ``cost_grid``, ``obstacle_tracks`` or ``obstacle_velocities`` (the switch is a create-time one);
         assigning None removes the grid."""
         return self._cost_grid
@@ -249,6 +251,9 @@ class _ControllerBase:
             return
         g = dict(value)
         g["cells"] = _arr(g["cells"])
+        g.setdefault("footprint", "centre")
+        if g["footprint"] != self._engine.cost_grid_footprint:
+            self._engine.set_cost_grid_footprint(g["footprint"])
         self._engine.set_cost_grid(g["cells"], g.get("origin", (0.0, 0.0)), g.get("resolution", 1.0), g.get("weight", 1.0),
                                    g.get("lethal", float("inf")))
         self._cost_grid = g

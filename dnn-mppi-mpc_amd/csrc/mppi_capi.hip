@@ -170,6 +170,9 @@ struct mppi_handle {
     std::vector<GridOwn> own_grids;
     DevBuf<void> d_grids;
     bool any_grid = false;  // some agent has a grid, kept by upload_grids (false: a handle that never had one, or cleared)
+    // mppi_set_cost_grid_footprint: every grid of the handle is priced under the vehicle's outline (MPPI_GRID_FOOTPRINT_OUTLINE).
+    // A property of the launch's form: front_plan hands it to the planner, the eval entry points pick their kernels by it.
+    int grid_footprint = MPPI_GRID_FOOTPRINT_CENTRE;
     // Composed scenes (mppi_set_scene_mode): in MPPI_SCENE_COMPOSED the three above may stand together, and d_scene is the one
     // SceneTable<R> a launch with two or more of them reads: the addresses of d_plans, d_tracks and d_grids (null: none) and the
     // mates' threshold, rewritten by every setter that changes an ingredient (upload_scene_table), allocated by the first switch
@@ -940,6 +943,60 @@ extern "C" int mppi_eval_cost_grid(mppi_handle *h, int32_t agent, const double *
     });
 }
 
+// The footprint mode: one for every agent, kept across grid uploads and removals.  Every refusal stands before the device is
+// touched; a call that leaves the mode as it is changes nothing.
+extern "C" int mppi_set_cost_grid_footprint(mppi_handle *h, int32_t mode) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (mode != MPPI_GRID_FOOTPRINT_CENTRE && mode != MPPI_GRID_FOOTPRINT_OUTLINE)
+        FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_cost_grid_footprint: mode %d is neither MPPI_GRID_FOOTPRINT_CENTRE nor MPPI_GRID_FOOTPRINT_OUTLINE", mode);
+    if (!h->cfg.obstacle_motion)
+        FAIL(h, MPPI_ERR_STATE, "mppi_set_cost_grid_footprint: the handle was created with obstacle_motion = 0; a cost grid needs "
+                                "mppi_config.obstacle_motion = 1 at mppi_create");
+    if (mode == MPPI_GRID_FOOTPRINT_OUTLINE && h->cfg.obstacle_model != MPPI_OBSTACLE_OUTLINE)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_cost_grid_footprint: the outline footprint needs obstacle_model = MPPI_OBSTACLE_OUTLINE "
+                                      "(limit: a disc is served by inflating the map by its radius)");
+    if (mode == MPPI_GRID_FOOTPRINT_OUTLINE && !h->fused)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_cost_grid_footprint: cost grids are served for horizons T <= 128 (T = %d runs the unfused rollout)",
+             h->cfg.T);
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    HIPCHECK(h, hipDeviceSynchronize());
+    if (mode == h->grid_footprint) return MPPI_OK;
+    h->grid_footprint = mode;
+    h->dev_loop_primed = false;
+    drop_graph(h);
+    return MPPI_OK;
+}
+extern "C" int mppi_get_cost_grid_footprint(const mppi_handle *h, int32_t *mode) {
+    if (!h || !mode) return MPPI_ERR_BAD_ARG;
+    *mode = h->grid_footprint;
+    return MPPI_OK;
+}
+// g_foot of agent `agent`'s grid at n poses, and the nine world points, from the device function the rollout prices with
+// (grid_value_outline), whatever the handle's mode
+extern "C" int mppi_eval_cost_grid_footprint(mppi_handle *h, int32_t agent, const double *pose, int32_t n, double *value, double *points) {
+    if (!h) return MPPI_ERR_BAD_ARG;
+    if (!pose || !value || n < 1) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_cost_grid_footprint: bad argument");
+    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_cost_grid_footprint: agent %d not in [0, %d)", agent, h->B);
+    if (grid_of(h, agent).nx == 0) FAIL(h, MPPI_ERR_STATE, "mppi_eval_cost_grid_footprint: agent %d has no cost grid", agent);
+    HIPCHECK(h, hipSetDevice(h->cfg.device));
+    return with_real(h, [&](auto r) -> int {
+        using R = decltype(r);
+        KParams<R> P = make_params<R>(h, nullptr);
+        if (P.obs_motion == OBS_MOTION_SCENE) set_grids<R>(P, h->d_grids.get());  // (the kernel reads the descriptors themselves)
+        DevBuf<R> dpose, dout, dpts;
+        HIPCHECK(h, dpose.alloc(sizeof(R) * (size_t)n * 3));
+        HIPCHECK(h, dout.alloc(sizeof(R) * (size_t)n));
+        if (points) HIPCHECK(h, dpts.alloc(sizeof(R) * (size_t)n * 18));
+        if (int rc = upload_real(h, dpose, pose, (size_t)n * 3)) return rc;
+        launch_eval_grid_foot_at<R>(P, EVAL_GRID_FOOTPRINT, agent, dpose, nullptr, nullptr, n, dout, points ? dpts.get() : nullptr, nullptr);
+        HIPCHECK(h, hipGetLastError());
+        HIPCHECK(h, hipDeviceSynchronize());
+        if (points)
+            if (int rc = download_real(h, points, dpts, (size_t)n * 18)) return rc;
+        return download_real(h, value, dout, (size_t)n);
+    });
+}
+
 extern "C" int mppi_get_agent_status(mppi_handle *h, int32_t *idx_out, int32_t *path_end_out) {
     if (!h) return MPPI_ERR_BAD_ARG;
     HIPCHECK(h, hipSetDevice(h->cfg.device));
@@ -1502,7 +1559,7 @@ static void wire_exchange(const mppi_handle *h, FinalizeParams &F) {
 template <typename R> static RolloutPlan front_plan(const mppi_handle *h, const KParams<R> &P) {
     if constexpr (sizeof(R) == 4)
         if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) return plan_mlp(P, h->mlp, h->sw);
-    return plan_rollout<R>(P, h->fused, h->sw);
+    return plan_rollout<R>(P, h->fused, h->sw, h->grid_footprint == MPPI_GRID_FOOTPRINT_OUTLINE);
 }
 
 // One iteration slot, resolved once and executed many times: rollout (-> reduce) (-> merge) -> its reader.  The reader is
@@ -2549,9 +2606,12 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
             eval_transition_mlp(h, P, dx, dv, n, dout);
         else if (at) {
             if (h->fleet) launch_fleet_rows<R>(make_fleet(h, 0), nullptr);  // agent 0's mates as of the current states
-            if (P.obs_motion == OBS_MOTION_SCENE) launch_eval_scene_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+            const bool foot = h->grid_footprint == MPPI_GRID_FOOTPRINT_OUTLINE;  // (the grid under the outline, by the pose's yaw)
+            if (P.obs_motion == OBS_MOTION_SCENE && foot) launch_eval_scene_foot_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+            else if (P.obs_motion == OBS_MOTION_SCENE) launch_eval_scene_at<R>(P, what, dx, di, ds, n, dout, nullptr);
             else if (h->fleet_plan) launch_eval_plan_at<R>(P, what, dx, di, ds, n, dout, nullptr);
             else if (tracks_of(h, 0).n > 0) launch_eval_tracks_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+            else if (grid_of(h, 0).nx > 0 && foot) launch_eval_grid_foot_at<R>(P, what, 0, dx, di, ds, n, dout, nullptr, nullptr);
             else if (grid_of(h, 0).nx > 0) launch_eval_grid_at<R>(P, what, 0, dx, di, ds, n, dout, nullptr);
             else launch_eval_at<R>(P, what, dx, di, ds, n, dout, nullptr);
         }

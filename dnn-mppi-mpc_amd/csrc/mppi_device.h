@@ -334,6 +334,42 @@ template <typename R> __device__ __forceinline__ R grid_value(const GridSet<R> &
     return fma_(fy, c1 - c0, c0);
 }
 
+// Cost grids under the vehicle's outline (mppi_set_cost_grid_footprint: MPPI_GRID_FOOTPRINT_OUTLINE).  Point q = 1 .. 8 of the
+// outline -- (P.shape_x, P.shape_y)[q - 1], the points collided() tests -- of a pose in the world, sn / cs = mf::sincos_ of its
+// yaw: two fmas per coordinate, the offset folded into the first (the order include/mppi_hip.h documents).  Point 0 is the
+// pose's own (x, y), untouched.  The outline is (+-a, 0), (+-a, +-b), (0, +-b) with a = shape_x[3], b = shape_y[3]: the signs
+// come out of two packed words (two bits per point, sign + 1), the products with them are exact -- so that a loop over q
+// indexes nothing (an index into the kernel's own copy of its argument would put that copy into scratch).
+constexpr unsigned OUTLINE_SIGNS_X = 0x1A90u, OUTLINE_SIGNS_Y = 0x01A9u;  // -a -a 0 a a a 0 -a  /  0 b b b 0 -b -b -b
+template <typename R>
+__device__ __forceinline__ void outline_point(const KParams<R> &P, unsigned wx, unsigned wy, R x, R y, R sn, R cs, R &px, R &py) {
+    const R qx = (R)((int)(wx & 3u) - 1) * P.shape_x[3];  // (wx, wy: the words shifted down to this point)
+    const R qy = (R)((int)(wy & 3u) - 1) * P.shape_y[3];
+    px = fma_(qx, cs, fma_(-qy, sn, x));
+    py = fma_(qx, sn, fma_(qy, cs, y));
+}
+// g_foot = fmax over the nine points of grid_value: the centre first, then the outline in order, each point a grid_value of its
+// own -- its four reads issued before its first use -- folded into a running fmax (the plain form; DESIGN 3.14 says what was
+// tried beside it).  The loop stays a loop: unrolled, the scheduler keeps the reads of all nine points in flight and the f64
+// and composed forms spill.  One sincos per state.  grid_index keeps every read inside the table whatever the pose is: a NaN or
+// infinite yaw makes the outline's points NaN, which land on node 0 of each axis.  `pts` (the eval kernels' window, else null)
+// receives the nine world points [9][2].
+template <typename R>
+__device__ __forceinline__ R grid_value_outline(const GridSet<R> &G, const KParams<R> &P, R x, R y, R yaw, R *pts = nullptr) {
+    R sn, cs;
+    mf::sincos_(yaw, sn, cs);
+    R g = grid_value(G, x, y);
+    if (pts) { pts[0] = x; pts[1] = y; }
+#pragma unroll 1
+    for (unsigned wx = OUTLINE_SIGNS_X | 0x10000u, wy = OUTLINE_SIGNS_Y; wx != 1u; wx >>= 2, wy >>= 2) {  // (bit 16: the end mark)
+        R px, py;
+        outline_point(P, wx, wy, x, y, sn, cs, px, py);
+        if (pts) { pts += 2; pts[0] = px; pts[1] = py; }
+        g = fmax(g, grid_value(G, px, py));
+    }
+    return g;
+}
+
 // weighted squared tracking error against waypoint i (`_compute_cost` :222-236, `_c` mppi_race_car.py:137-146)
 template <typename R, int MODEL>
 __device__ __forceinline__ R tracking_cost_row(const KParams<R> &P, const R (&w)[4], bool wrap, const R *r, R x, R y, R yaw,

@@ -490,7 +490,9 @@ int fused_blocks(int K, int T, int layout);  // workgroups = block records of a 
 int fused_max_records(int K, int T, int layout);
 // the rollout launch of an analytic-model handle: k_rollout (fused false; launch_reduce follows, `records` is its count),
 // else k_rollout_fused / _dual / _tri by P.layout, or k_rollout_stream where it serves (T <= 128)
-template <typename R> RolloutPlan plan_rollout(const KParams<R> &P, bool fused, const Switches &sw);
+// footprint: the handle prices its cost grid under the vehicle's outline (mppi_set_cost_grid_footprint) -- a property of the
+// launch's form, carried by no descriptor: where the grid form or the composed form would have served, the one beside it
+template <typename R> RolloutPlan plan_rollout(const KParams<R> &P, bool fused, const Switches &sw, bool footprint = false);
 template <typename R> void launch_rollout(const RolloutPlan &plan, const KParams<R> &P, void *partials, hipStream_t s);
 template <typename R> MergeStep plan_merge(const void *recs, const void *heads, int n, int group, int T, void *out, void *out_heads);
 template <typename R> void launch_merge(const MergeStep &m, int T, double beta, hipStream_t s);
@@ -552,6 +554,15 @@ void launch_eval_grid_at(const KParams<R> &P, int what, int agent, const R *x, c
 // launch_eval_at for a composed handle (P carries the SceneTable: set_scene): agent 0's circles, mates, tracks and grid together
 template <typename R>
 void launch_eval_scene_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
+// launch_eval_grid_at / launch_eval_scene_at with the grid priced under the vehicle's outline (the pose's yaw column).
+// what == EVAL_GRID_FOOTPRINT: x is pose[n][3] = x, y, yaw, out[i] = g_foot of agent `agent`'s grid there and pts (nullable)
+// [n][9][2] its nine world points
+constexpr int EVAL_GRID_FOOTPRINT = 17;
+template <typename R>
+void launch_eval_grid_foot_at(const KParams<R> &P, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out,
+                              R *pts, hipStream_t s);
+template <typename R>
+void launch_eval_scene_foot_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s);
 void launch_eval_weights(const double *S, int n, double beta, double *w, hipStream_t s);
 template <typename R> void launch_set_state_dev(const KParams<R> &P, const double *x_dev, int nx, hipStream_t s);

@@ -177,8 +177,10 @@ template <typename R> __device__ __forceinline__ void scene_plan_words(KParams<R
 // SCENE (the composed form, mppi_set_scene_mode: MOVING, TRACKS and GRID together, PLANS where the launch is batched): the
 // three "never with" above do not hold for it -- a state is hit when any ingredient says so, each one guarded by its
 // descriptor (a null plan table, trk_n == 0, nx == 0: the agent lacks it), and the grid's term joins the costs as in GRID.
+// FOOT (with GRID; mppi_set_cost_grid_footprint: MPPI_GRID_FOOTPRINT_OUTLINE): g is the largest value under the centre and the
+// eight outline points of the state's pose (grid_value_outline, mppi_device.h) instead of the value at its position.
 template <typename R, int MODEL, bool OBS = true, bool PLAIN = false, bool MOVING = false, bool PLANS = false, bool TRACKS = false,
-          bool GRID = false, bool SCENE = false>
+          bool GRID = false, bool SCENE = false, bool FOOT = false>
 struct Rollout : RolloutMotion<R, MOVING>, RolloutTracks<R, TRACKS>, RolloutGrid<R, GRID>, RolloutScene<R, SCENE> {
     __device__ __forceinline__ void set_scene(const RolloutScene<R, SCENE> &sn) { static_cast<RolloutScene<R, SCENE> &>(*this) = sn; }
     __device__ __forceinline__ void set_tracks(const RolloutTracks<R, TRACKS> &tk) { static_cast<RolloutTracks<R, TRACKS> &>(*this) = tk; }
@@ -444,7 +446,9 @@ struct Rollout : RolloutMotion<R, MOVING>, RolloutTracks<R, TRACKS>, RolloutGrid
             R wg = R(0);
             if constexpr (GRID) {
                 if (this->grid.nx > 0) {
-                    const R g = grid_value(this->grid, x, y);
+                    R g;
+                    if constexpr (FOOT) g = grid_value_outline(this->grid, P, x, y, yaw);
+                    else g = grid_value(this->grid, x, y);
                     hit |= g >= this->grid.lethal;
                     wg = this->grid.weight * g;
                 }
@@ -740,16 +744,17 @@ template <bool SCENE, typename R> __device__ __forceinline__ const auto &grids_s
 // same with the mates' plans (MULTI only: a mate is another agent of the launch), 5 general, moving, with obstacle tracks, 6
 // general, moving, with a cost grid (mppi_set_cost_grid), 7 the composed form (mppi_set_scene_mode: a handle that holds at least
 // two of plans, tracks and a grid): moving circles, tracks and a grid, and the mates' plans where MULTI -- each guarded by its
-// descriptor, behind the handle's SceneTable (mppi_kernels.h)
+// descriptor, behind the handle's SceneTable (mppi_kernels.h); 8 and 9 are 6 and 7 with the grid priced under the vehicle's
+// outline (mppi_set_cost_grid_footprint: Rollout's FOOT)
 // HYPK: the instantiation that can resolve the sequential index in one launch (fused_lookback).  A separate instantiation,
 // picked by the host while the waypoint index can still move (KParams::hyp): carrying that code costs the lean kernel
 // 0.17 us per launch in registers and LDS (A/B on one box), and at the end of the path nothing moves any more.
 template <typename R, int MODEL, int NCH, bool MULTI, int SPEC, bool HYPK = false>
 __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevState *st_pre, KParams<R> P,
                                                                     R *__restrict__ partials) {
-    constexpr bool SCENE = SPEC == 7;
+    constexpr bool SCENE = SPEC == 7 || SPEC == 9, FOOT = SPEC >= 8;
     constexpr bool OBS = SPEC == 0 || SPEC >= 3, PLAIN = SPEC == 2, MOVING = SPEC >= 3, PLANS = SPEC == 4 || (SCENE && MULTI),
-                   TRACKS = SPEC == 5 || SCENE, GRID = SPEC == 6 || SCENE;
+                   TRACKS = SPEC == 5 || SCENE, GRID = SPEC == 6 || SPEC == 8 || SCENE;
     static_assert(!PLANS || MULTI, "the mates are the other agents of a batched launch");
     static_assert(!(HYPK && SCENE), "the composed form extends the moving ones");
     static_assert(!(HYPK && MOVING), "the look-back prices the last state with a collision test of its own: static obstacles only");
@@ -869,11 +874,11 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
         const bool ref_lds = P.n_ref <= PR_REF_LDS;
         if (ref_lds)
             for (int i = threadIdx.x; i < P.n_ref; i += blockDim.x) { sh_pref[2 * i] = P.ref[4 * i]; sh_pref[2 * i + 1] = P.ref[4 * i + 1]; }
-        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID, SCENE> r(P, sv, k, lane, nullptr, obs, agent, mv);
+        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID, SCENE, FOOT> r(P, sv, k, lane, nullptr, obs, agent, mv);
         if constexpr (TRACKS) r.set_tracks(tk);
         if constexpr (GRID) r.set_grid(gr);
         if constexpr (SCENE) r.set_scene(sn);
-        typename Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID, SCENE>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
+        typename Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID, SCENE, FOOT>::Step sp{R(0), R(0), R(0), R(0), R(0), R(0), R(0), R(0), false};
         if (valid) sp = r.dynamics(0, e0[0], e1[0]);
         sh_px[wid][lane] = sp.x;
         sh_py[wid][lane] = sp.y;
@@ -885,7 +890,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_rollout_fused(const DevSta
             S_k = r.finish(false);
         }
     } else if (valid) {
-        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID, SCENE> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
+        Rollout<R, MODEL, OBS, PLAIN, MOVING, PLANS, TRACKS, GRID, SCENE, FOOT> r(P, sv, k, lane, use_win ? sh_win : nullptr, obs, agent, mv);
         if constexpr (TRACKS) r.set_tracks(tk);
         if constexpr (GRID) r.set_grid(gr);
         if constexpr (SCENE) r.set_scene(sn);
@@ -2738,6 +2743,90 @@ __global__ __launch_bounds__(256) void k_eval_scene_at(KParams<R> P, int what, c
     }
 }
 
+// k_eval_grid_at with the grid priced under the vehicle's outline (mppi_set_cost_grid_footprint: grid_value_outline of the
+// pose's yaw column, as Rollout::costs prices it with FOOT).  EVAL_GRID_FOOTPRINT: x is pose[n][3] = x, y, yaw, out[i] = g_foot
+// of agent `agent`'s grid there and -- pts not null -- pts[i] its nine world points [9][2] (nothing else is read).  Kernels of
+// their own, so that k_eval_grid_at and k_eval_scene_at keep their text.
+template <typename R, int MODEL>
+__global__ __launch_bounds__(256) void k_eval_grid_foot_at(const KParams<R> P, int what, int agent, const R *__restrict__ x,
+                                                           const int *__restrict__ idx, const int *__restrict__ steps, int n,
+                                                           R *__restrict__ out, R *__restrict__ pts) {
+    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
+    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool act = i < n;
+    const GridSet<R> G = grid_sets(P)[agent];
+    if (what == EVAL_GRID_FOOTPRINT) {
+        if (act && G.nx > 0)
+            out[i] = grid_value_outline(G, P, x[3 * (size_t)i], x[3 * (size_t)i + 1], x[3 * (size_t)i + 2], pts ? pts + 18 * (size_t)i : nullptr);
+        return;
+    }
+    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
+    R s[4] = {R(0), R(0), R(0), R(0)};
+    if (act)
+        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
+    const int j = act && steps ? steps[i] : 0;
+    const R tau = obstacle_time(P, obstacle_clock(P.st->iter, P.iter0) + j);
+    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
+    R wg = R(0);
+    if (G.nx > 0) {
+        const R g = grid_value_outline(G, P, s[0], s[1], s[2]);
+        hit |= g >= G.lethal;
+        wg = G.weight * g;
+    }
+    if (what == EVAL_COLLIDED) {
+        if (act) out[i] = hit ? R(1) : R(0);
+    } else {
+        const bool term = what == EVAL_COST_TERMINAL;
+        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
+                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit) + wg;
+        if (act) out[i] = c;
+    }
+}
+// k_eval_scene_at likewise
+template <typename R, int MODEL>
+__global__ __launch_bounds__(256) void k_eval_scene_foot_at(KParams<R> P, int what, const R *__restrict__ x, const int *__restrict__ idx,
+                                                            const int *__restrict__ steps, int n, R *__restrict__ out) {
+    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
+    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const SceneTable<R> tb = *scene_table(P);
+    scene_plan_words(P, tb.plans, tb.thr2);
+    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
+    const bool act = i < n;
+    R s[4] = {R(0), R(0), R(0), R(0)};
+    if (act)
+        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
+    const int j = act && steps ? steps[i] : 0;
+    const int j0 = j < 0 ? 0 : j;
+    const long long iter = P.st->iter;
+    const R tau = obstacle_time(P, obstacle_clock(iter, P.iter0) + j);
+    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
+    if (tb.plans != nullptr) hit |= mates_collided(P, tb.plans, s[0], s[1], s[2], 0, j0 < P.T ? j0 : P.T);
+    if (tb.tracks != nullptr) {
+        const TrackSet ts = tb.tracks[0];
+        if (ts.n > 0) {
+            const int at = track_index(track_clock(iter, ts.iter0, ts.L), j0, ts.L);
+            hit |= tracks_collided(P, static_cast<const PlanPoint<R> *>(ts.pts) + at, static_cast<const R *>(ts.thr2), ts.n, ts.L, s[0], s[1], s[2]);
+        }
+    }
+    R wg = R(0);
+    if (tb.grids != nullptr) {
+        const GridSet<R> G = tb.grids[0];
+        if (G.nx > 0) {
+            const R g = grid_value_outline(G, P, s[0], s[1], s[2]);
+            hit |= g >= G.lethal;
+            wg = G.weight * g;
+        }
+    }
+    if (what == EVAL_COLLIDED) {
+        if (act) out[i] = hit ? R(1) : R(0);
+    } else {
+        const bool term = what == EVAL_COST_TERMINAL;
+        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
+                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit) + wg;
+        if (act) out[i] = c;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
@@ -2865,8 +2954,13 @@ template <typename R, int MODEL, bool MULTI, int SPW> static KernelLaunch dual_p
 // moving obstacles (never with the look-back: lookback_serves, mppi_capi.hip), 4 the same with the mates' plans (batched
 // launches of a handle that carries a plan table), 5 the moving form with obstacle tracks (some agent has a track set), 6 the
 // moving form with a cost grid (some agent has one), 7 the composed form (a handle in MPPI_SCENE_COMPOSED that holds at least
-// two of plans, tracks and a grid)
+// two of plans, tracks and a grid), 8 and 9 the forms 6 and 7 of a handle whose grid is priced under the vehicle's outline
+// (mppi_set_cost_grid_footprint)
 template <typename R, int MODEL, int NCH, bool MULTI, bool HYPK> static KernelLaunch fused_plan(int spec) {
+    if constexpr (!HYPK)
+        if (spec == 9) return fused_entry<R, MODEL, NCH, MULTI, 9, false>();
+    if constexpr (!HYPK)
+        if (spec == 8) return fused_entry<R, MODEL, NCH, MULTI, 8, false>();
     if constexpr (!HYPK)
         if (spec == 7) return fused_entry<R, MODEL, NCH, MULTI, 7, false>();
     if constexpr (!HYPK)
@@ -2881,7 +2975,7 @@ template <typename R, int MODEL, int NCH, bool MULTI, bool HYPK> static KernelLa
            : spec == 1 ? fused_entry<R, MODEL, NCH, MULTI, 1, HYPK>()
                        : fused_entry<R, MODEL, NCH, MULTI, 0, HYPK>();
 }
-template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const KParams<R> &P, const Switches &sw) {
+template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const KParams<R> &P, const Switches &sw, bool footprint) {
     RolloutPlan p;
     if (const int np = stream_passes(P, sw)) {
         const bool obs = P.obstacle_model != OBS_NONE;
@@ -2920,7 +3014,8 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
             const bool tracks = P.obs_motion == OBS_MOTION_TRACKS;  // (never a fleet handle in plan mode: pad_scenes carries the descriptors)
             const bool grid = P.obs_motion == OBS_MOTION_GRID;  // (likewise, and never with tracks)
             const bool plans = MULTI && P.obs_motion && !scene && !tracks && !grid && fleet_plan_table(P) != nullptr;
-            const int spec = scene ? 7 : grid ? 6 : tracks ? 5 : plans ? 4 : P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
+            // (footprint: the handle prices its grid under the outline -- the forms beside 6 and 7, where those would have served)
+            const int spec = scene ? (footprint ? 9 : 7) : grid ? (footprint ? 8 : 6) : tracks ? 5 : plans ? 4 : P.obs_motion ? 3 : plain ? 2 : P.obstacle_model == OBS_NONE ? 1 : 0;
             p.lookback = !MULTI && MODEL == MODEL_DIFF && P.hyp && P.T <= 64 && !P.obs_motion;  // (the HYPK form: one agent, diff-drive, one chunk)
             p.k = p.lookback  ? fused_plan<R, MODEL_DIFF, 1, false, true>(spec)
                   : P.T <= 64 ? fused_plan<R, MODEL, 1, MULTI, false>(spec)
@@ -2940,11 +3035,11 @@ template <typename R, int MODEL, bool MULTI> static RolloutPlan plan_fused(const
     return p;
 }
 
-template <typename R> RolloutPlan plan_rollout(const KParams<R> &P, bool fused, const Switches &sw) {
+template <typename R> RolloutPlan plan_rollout(const KParams<R> &P, bool fused, const Switches &sw, bool footprint) {
     const bool diff = P.model == MODEL_DIFF;
     if (fused) {
-        if (P.n_agents > 1) return diff ? plan_fused<R, MODEL_DIFF, true>(P, sw) : plan_fused<R, MODEL_RACE, true>(P, sw);
-        return diff ? plan_fused<R, MODEL_DIFF, false>(P, sw) : plan_fused<R, MODEL_RACE, false>(P, sw);
+        if (P.n_agents > 1) return diff ? plan_fused<R, MODEL_DIFF, true>(P, sw, footprint) : plan_fused<R, MODEL_RACE, true>(P, sw, footprint);
+        return diff ? plan_fused<R, MODEL_DIFF, false>(P, sw, footprint) : plan_fused<R, MODEL_RACE, false>(P, sw, footprint);
     }
     RolloutPlan p;
     if (P.obs_motion) p.k = diff ? rollout_moving_entry<R, MODEL_DIFF>() : rollout_moving_entry<R, MODEL_RACE>();
@@ -3064,6 +3159,19 @@ void launch_eval_scene_at(const KParams<R> &P, int what, const R *x, const int *
     if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_scene_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
     else hipLaunchKernelGGL((k_eval_scene_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
 }
+template <typename R>
+void launch_eval_grid_foot_at(const KParams<R> &P, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out,
+                              R *pts, hipStream_t s) {
+    const dim3 grid((n + 255) / 256), block(256);
+    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_grid_foot_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, agent, x, idx, steps, n, out, pts);
+    else hipLaunchKernelGGL((k_eval_grid_foot_at<R, MODEL_RACE>), grid, block, 0, s, P, what, agent, x, idx, steps, n, out, pts);
+}
+template <typename R>
+void launch_eval_scene_foot_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
+    const dim3 grid((n + 255) / 256), block(256);
+    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_scene_foot_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+    else hipLaunchKernelGGL((k_eval_scene_foot_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+}
 template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s) {
     if (!F.plans) hipLaunchKernelGGL(k_fleet_rows<R>, dim3(F.n_agents), dim3(64), 0, s, F);
     else if (F.model == MODEL_DIFF) hipLaunchKernelGGL((k_fleet_plan<R, MODEL_DIFF>), dim3(F.n_agents), dim3(64), 0, s, F);
@@ -3110,7 +3218,7 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
 
 #define INSTANTIATE(R)                                                                                    \
     template void launch_set_state<R>(const KParams<R> &, const double *, hipStream_t);                   \
-    template RolloutPlan plan_rollout<R>(const KParams<R> &, bool, const Switches &);                     \
+    template RolloutPlan plan_rollout<R>(const KParams<R> &, bool, const Switches &, bool);                   \
     template void launch_rollout<R>(const RolloutPlan &, const KParams<R> &, void *, hipStream_t);        \
     template void launch_reduce<R>(const KParams<R> &, void *, int, hipStream_t);                         \
     template MergeStep plan_merge<R>(const void *, const void *, int, int, int, void *, void *);             \
@@ -3125,6 +3233,8 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
     template void launch_eval_tracks_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_grid_at<R>(const KParams<R> &, int, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_scene_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
+    template void launch_eval_grid_foot_at<R>(const KParams<R> &, int, int, const R *, const int *, const int *, int, R *, R *, hipStream_t); \
+    template void launch_eval_scene_foot_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_filter<R>(const R *, R *, int, int, int, hipStream_t);                                 \
     template void launch_set_state_dev<R>(const KParams<R> &, const double *, int, hipStream_t);                     \
     template void launch_viz<R>(const KParams<R> &, const R *, const R *, long long, float *, float *, hipStream_t);

@@ -168,6 +168,34 @@ class Engine:
         self._ck(self.lib.mppi_eval_cost_grid(self._h, int(agent), _dp(p), p.shape[0], _dp(out)))
         return out
 
+    def set_cost_grid_footprint(self, mode):
+        """``"outline"``: wherever a cost grid is priced, the largest value under the vehicle's centre and its eight outline
+        points (the ones the collision test uses, turned by the state's yaw) takes the place of the value at the centre -- for
+        handles created with ``obstacle_model=OBSTACLE_OUTLINE``.  ``"centre"`` (the default): the state's (x, y) only.  One
+        mode for every agent, kept across grid uploads; mppi_set_cost_grid_footprint."""
+        modes = {"centre": capi.GRID_FOOTPRINT_CENTRE, "outline": capi.GRID_FOOTPRINT_OUTLINE}
+        if mode not in modes:
+            raise capi.MppiError(capi.ERR_BAD_ARG, f"cost grid footprint {mode!r} is neither 'centre' nor 'outline'")
+        self._ck(self.lib.mppi_set_cost_grid_footprint(self._h, modes[mode]))
+
+    @property
+    def cost_grid_footprint(self):
+        """``"centre"`` or ``"outline"`` (mppi_get_cost_grid_footprint)."""
+        m = C.c_int32(0)
+        self._ck(self.lib.mppi_get_cost_grid_footprint(self._h, C.byref(m)))
+        return "outline" if m.value == capi.GRID_FOOTPRINT_OUTLINE else "centre"
+
+    def cost_grid_footprint_at(self, poses, agent=0, points=False):
+        """The footprint value of ``agent``'s cost grid at the poses ``poses`` [n, 3] = x, y, yaw -- the largest value under
+        the centre and the eight outline points -- computed by the device function the rollout prices with, in either mode;
+        with ``points=True`` also the nine world points [n, 9, 2] (mppi_eval_cost_grid_footprint)."""
+        p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        out = np.empty(p.shape[0])
+        pts = np.empty((p.shape[0], 9, 2)) if points else None
+        self._ck(self.lib.mppi_eval_cost_grid_footprint(self._h, int(agent), _dp(p), p.shape[0], _dp(out),
+                                                        _dp(pts) if points else None))
+        return (out, pts) if points else out
+
     def fleet_clearance(self, reset=False):
         """(min_dist[n_agents], contact_iters[n_agents]) over the iterations run since the handle was made or the last call
         with ``reset=True``: the smallest centre distance of every agent to any mate at the start of an iteration (inf: none

@@ -93,6 +93,13 @@ int main(void) {
         EXPECT(mppi_set_scene_mode(NULL, MPPI_SCENE_COMPOSED) == MPPI_ERR_BAD_ARG);
         EXPECT(mppi_set_scene_mode(NULL, 2) == MPPI_ERR_BAD_ARG && mppi_set_scene_mode(NULL, -1) == MPPI_ERR_BAD_ARG);
         EXPECT(mppi_get_scene_mode(NULL, &m) == MPPI_ERR_BAD_ARG && m == -7);
+        /* and the three of the cost-grid footprint: NULL comes first, a good or a bad mode alike; nothing is written */
+        EXPECT(mppi_set_cost_grid_footprint(NULL, MPPI_GRID_FOOTPRINT_OUTLINE) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_set_cost_grid_footprint(NULL, 2) == MPPI_ERR_BAD_ARG && mppi_set_cost_grid_footprint(NULL, -1) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_get_cost_grid_footprint(NULL, &m) == MPPI_ERR_BAD_ARG && m == -7);
+        EXPECT(mppi_get_cost_grid_footprint(NULL, NULL) == MPPI_ERR_BAD_ARG);
+        EXPECT(mppi_eval_cost_grid_footprint(NULL, 0, &d, 1, &d, &d) == MPPI_ERR_BAD_ARG && d == -1.0);
+        EXPECT(mppi_eval_cost_grid_footprint(NULL, -1, NULL, 0, NULL, NULL) == MPPI_ERR_BAD_ARG);
     }
     {   /* the composed launches' staging at its budget edges (T = 128: 2064 bytes of plans per agent and 2072 per track in
          * f64, half of each in f32): plans first, the tracks 16-byte aligned behind them, each only if it fits; a buffer of the

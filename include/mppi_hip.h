@@ -532,7 +532,7 @@ int mppi_get_obstacle_tracks_at(mppi_handle *h, int32_t agent, int32_t step, dou
  * cost also gains weight g, and the state counts as hit when g >= lethal or a circle says so.  With accumulate_stage_cost = 0
  * the last state is therefore priced twice, as the penalty is.  lethal = +inf: soft cost only.  mppi_stats.n_collided keeps its
  * definition (S >= collision_penalty); an agent with a grid and no circles counts its hits.  Both dynamics models sample the
- * state's (x, y) only (no footprint).  The handle's circles, static or moving, are priced exactly as before, beside the grid.
+ * state's (x, y) only (no footprint; mppi_set_cost_grid_footprint below adds the outline).  The handle's circles, static or moving, are priced exactly as before, beside the grid.
  * The grid has no clock: it stands until replaced.  cells == NULL or nx == 0 removes it: the handle is then bit for bit the
  * handle that never called the setter.  A re-upload of the same nx x ny reuses the buffers and keeps a cached graph
  * (MPPI_GRAPH=1): the rolling-costmap loop; origin, resolution, weight and lethal may change with it.
@@ -551,6 +551,38 @@ int mppi_set_agent_cost_grid(mppi_handle *h, int32_t agent, const double *cells,
 /* The raw value g of agent `agent`'s grid at n points xy [n][2], from the device function the rollout prices with (for
  * visualisation and tests).  An agent without a grid: MPPI_ERR_STATE. */
 int mppi_eval_cost_grid(mppi_handle *h, int32_t agent, const double *xy, int32_t n, double *value);
+/* COST GRID FOOTPRINT: price the vehicle's outline against the grid, not only its centre.
+ * THE MODE belongs to the handle: one for every agent, kept across grid uploads and removals; it may be set before any grid
+ * exists.  A handle that never calls the setter, or sets MPPI_GRID_FOOTPRINT_CENTRE, is bit for bit the handle described
+ * above: the same launches, the same answer of mppi_get_rollout_kernel, the same outputs.
+ * THE POINTS.  In MPPI_GRID_FOOTPRINT_OUTLINE nine body-frame points q = 0 .. 8 are sampled wherever the handle prices a grid:
+ * q = 0 the centre (0, 0), q = 1 .. 8 the outline the collision test uses -- with a = 0.5 vehicle_l safety_margin and
+ * b = 0.5 vehicle_w safety_margin: (-a, 0), (-a, b), (0, b), (a, b), (a, 0), (a, -b), (0, -b), (-a, -b), each rounded once to
+ * the handle's precision R.  The world point of (qx, qy), all in R, with {sn, cs} the kernels' own sincos of the state's yaw --
+ * the yaw the collision test uses, unwrapped --:
+ *     px = fma(qx, cs, fma(-qy, sn, x));        py = fma(qx, sn, fma(qy, cs, y))
+ * (two roundings per coordinate; the offset joins the first product).  The centre is the state's (x, y) itself.
+ * THE VALUE.  g_foot = fmax over q of g(p_q), g the bilinear formula above, folded in the order q = 0, 1, .. 8.
+ * PRICING.  Everything said above about pricing holds with g replaced by g_foot: the cost gains weight g_foot wherever the
+ * penalty is added (the terminal call too, so twice with accumulate_stage_cost = 0), the state is hit when g_foot >= lethal or
+ * any other ingredient says so, mppi_stats.n_collided keeps its definition, and every read stays inside the table whatever the
+ * state is (a NaN or infinite yaw or position lands on edge nodes).  Composed scenes price their grid the same way.
+ * mppi_eval_is_collided[_at] and mppi_eval_cost follow the mode, using the pose's yaw column; mppi_eval_cost_grid stays the raw
+ * centre value.  Both dynamics models: MPPI_OBSTACLE_OUTLINE with the diff-drive model is a rectangular AGV.
+ * REFUSALS name their limit in mppi_last_error and change nothing.  NULL handle (or NULL mode of the getter): MPPI_ERR_BAD_ARG,
+ * before anything else.  An unknown mode: MPPI_ERR_BAD_ARG.  A handle created with obstacle_motion = 0: MPPI_ERR_STATE.
+ * MPPI_GRID_FOOTPRINT_OUTLINE on a handle whose obstacle_model is not MPPI_OBSTACLE_OUTLINE: MPPI_ERR_UNSUPPORTED (a disc is
+ * served by inflating the map by its radius), and on a horizon T > 128: MPPI_ERR_UNSUPPORTED.  MPPI_GRID_FOOTPRINT_CENTRE is
+ * accepted on any handle that has obstacle_motion.  The setter synchronises; a call that changes the mode drops a cached graph,
+ * one that does not changes nothing.  In either mode a re-upload of a grid of the same shape keeps a cached graph. */
+#define MPPI_GRID_FOOTPRINT_CENTRE  0   /* default: the state's (x, y), as documented at mppi_set_cost_grid */
+#define MPPI_GRID_FOOTPRINT_OUTLINE 1
+int mppi_set_cost_grid_footprint(mppi_handle *h, int32_t mode);
+int mppi_get_cost_grid_footprint(const mppi_handle *h, int32_t *mode);
+/* g_foot of agent `agent`'s grid at n poses pose [n][3] = x, y, yaw, and -- points not NULL -- the nine world points
+ * points [n][9][2], from the device function the rollout prices with, in either mode (for visualisation and tests).  An agent
+ * without a grid: MPPI_ERR_STATE. */
+int mppi_eval_cost_grid_footprint(mppi_handle *h, int32_t agent, const double *pose, int32_t n, double *value, double *points);
 /* ---- composed scenes: fleet plans, obstacle tracks and a cost grid on one handle ----
  * By default (MPPI_SCENE_EXCLUSIVE) the mates' plans, the obstacle tracks and the cost grid exclude each other on a handle, as
  * the three setters document: a handle that never calls this behaves bit for bit as before, refusals and messages included.
