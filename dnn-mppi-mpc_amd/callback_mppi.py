@@ -104,7 +104,7 @@ class MPPI:
             c.u_min[i], c.u_max[i], c.u_init[i], c.r_diag[i] = lo[i], hi[i], ui[i], running_cost.r_diag[i]
         for i in range(self.nx):
             c.goal[i], c.q_diag[i] = running_cost.goal[i], running_cost.q_diag[i]
-        for m, row in enumerate(running_cost.obstacles):
+        for m, row in enumerate(running_cost.obstacles[:len(c.obstacles) // 4]):  # (more than fit: mppi_cb_create refuses n_obs)
             for q in range(4):
                 c.obstacles[4 * m + q] = row[q]
         c.safety_distance, c.obstacle_weight = running_cost.safety_distance, running_cost.obstacle_weight
@@ -148,7 +148,8 @@ class MPPI:
         s = np.ascontiguousarray(_np(state).reshape(self.nx))
         eps = None
         if noise is not None:
-            if not noise.is_cuda or not noise.is_contiguous() or tuple(noise.shape) != (self.K, self.T, self.nu):
+            if not noise.is_cuda or not noise.is_contiguous() or tuple(noise.shape) != (self.K, self.T, self.nu) or \
+                    str(noise.dtype) != "torch.float32":  # (the kernels read the buffer as float whatever it holds)
                 raise ValueError(f"noise must be a contiguous CUDA float32 tensor [{self.K}, {self.T}, {self.nu}]")
             eps = C.c_void_p(noise.data_ptr())
         a = np.empty(self.nu)

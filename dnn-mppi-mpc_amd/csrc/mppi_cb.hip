@@ -251,6 +251,15 @@ extern "C" int mppi_cb_create(const mppi_cb_config *c, mppi_cb_handle **out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || c->device < 0 || c->device >= ndev)
         CB_FAIL(none, MPPI_ERR_NO_DEVICE, "mppi_cb_create: no such HIP device %d", c->device);
+    // the factorisation reads the lower triangle only: the upper one has to say the same, within rounding of the caller's own
+    // arithmetic relative to the diagonal (|S_ij - S_ji| <= 1e-9 sqrt(S_ii S_jj); NaN fails either test)
+    for (int i = 0; i < nu; ++i)
+        for (int j = 0; j < i; ++j) {
+            const double scale = sqrt(fabs(c->noise_sigma[i * 4 + i] * c->noise_sigma[j * 4 + j]));
+            if (!(fabs(c->noise_sigma[i * 4 + j] - c->noise_sigma[j * 4 + i]) <= 1e-9 * scale))
+                CB_FAIL(none, MPPI_ERR_BAD_ARG, "noise_sigma must be symmetric positive definite: [%d][%d] = %g, [%d][%d] = %g", i, j,
+                        c->noise_sigma[i * 4 + j], j, i, c->noise_sigma[j * 4 + i]);
+        }
     // Cholesky factor and inverse of the nu x nu noise covariance (f64 on the host)
     double L[16] = {0}, Li[16] = {0}, Sinv[16] = {0};
     for (int i = 0; i < nu; ++i)

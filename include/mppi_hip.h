@@ -680,7 +680,7 @@ typedef struct {
     int32_t n_obs;               /* <= 16 */
     int32_t sample_null_action;  /* the last sample applies the zero action (test_mppi_diff_dyna.py:338) */
     double dt, lambda_;
-    double noise_sigma[16];      /* row-major, leading nu x nu block of a 4 x 4 */
+    double noise_sigma[16];      /* row-major, leading nu x nu block of a 4 x 4; symmetric (both triangles are compared) positive definite */
     double u_min[4], u_max[4], u_init[4];
     double goal[5], q_diag[5], r_diag[4];
     double obstacles[64];        /* [n_obs][4] = x, y, vx, vy (per step of the horizon) */
