@@ -171,7 +171,7 @@ struct mppi_handle {
     DevBuf<void> d_grids;
     bool any_grid = false;  // some agent has a grid, kept by upload_grids (false: a handle that never had one, or cleared)
     // mppi_set_cost_grid_footprint: every grid of the handle is priced under the vehicle's outline (MPPI_GRID_FOOTPRINT_OUTLINE).
-    // A property of the launch's form: front_plan hands it to the planner, the eval entry points pick their kernels by it.
+    // A property of the launch's form: front_plan hands it to the planner, the eval entry points pick their form by it (eval_form).
     int grid_footprint = MPPI_GRID_FOOTPRINT_CENTRE;
     // Composed scenes (mppi_set_scene_mode): in MPPI_SCENE_COMPOSED the three above may stand together, and d_scene is the one
     // SceneTable<R> a launch with two or more of them reads: the addresses of d_plans, d_tracks and d_grids (null: none) and the
@@ -921,26 +921,35 @@ extern "C" int mppi_set_agent_cost_grid(mppi_handle *h, int32_t agent, const dou
     return set_grid_impl(h, "mppi_set_agent_cost_grid", h->B == 1 && agent == 0 ? -1 : agent, cells, nx, ny, origin_x, origin_y,
                          resolution, weight, lethal);
 }
-// the raw value of agent `agent`'s grid at n points, from the device helper the rollout prices with (grid_value)
-extern "C" int mppi_eval_cost_grid(mppi_handle *h, int32_t agent, const double *xy, int32_t n, double *value) {
+// mppi_eval_cost_grid / mppi_eval_cost_grid_footprint: agent `agent`'s grid alone at n rows of `width` numbers (what ==
+// EVAL_GRID_POINTS: xy, EVAL_GRID_FOOTPRINT: x, y, yaw), and -- points not null -- the nine world points of every row
+static int eval_grid_impl(mppi_handle *h, const char *who, int what, int32_t agent, const double *in, int width, int32_t n, double *value,
+                          double *points) {
     if (!h) return MPPI_ERR_BAD_ARG;
-    if (!xy || !value || n < 1) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_cost_grid: bad argument");
-    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_cost_grid: agent %d not in [0, %d)", agent, h->B);
-    if (grid_of(h, agent).nx == 0) FAIL(h, MPPI_ERR_STATE, "mppi_eval_cost_grid: agent %d has no cost grid", agent);
+    if (!in || !value || n < 1) FAIL(h, MPPI_ERR_BAD_ARG, "%s: bad argument", who);
+    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "%s: agent %d not in [0, %d)", who, agent, h->B);
+    if (grid_of(h, agent).nx == 0) FAIL(h, MPPI_ERR_STATE, "%s: agent %d has no cost grid", who, agent);
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     return with_real(h, [&](auto r) -> int {
         using R = decltype(r);
-        KParams<R> P = make_params<R>(h, nullptr);
-        if (P.obs_motion == OBS_MOTION_SCENE) set_grids<R>(P, h->d_grids.get());  // (k_eval_grid_at reads the descriptors themselves)
-        DevBuf<R> dxy, dout;
-        HIPCHECK(h, dxy.alloc(sizeof(R) * (size_t)n * 2));
+        const KParams<R> P = make_params<R>(h, nullptr);
+        DevBuf<R> din, dout, dpts;
+        HIPCHECK(h, din.alloc(sizeof(R) * (size_t)n * width));
         HIPCHECK(h, dout.alloc(sizeof(R) * (size_t)n));
-        if (int rc = upload_real(h, dxy, xy, (size_t)n * 2)) return rc;
-        launch_eval_grid_at<R>(P, EVAL_GRID_POINTS, agent, dxy, nullptr, nullptr, n, dout, nullptr);
+        if (points) HIPCHECK(h, dpts.alloc(sizeof(R) * (size_t)n * 18));
+        if (int rc = upload_real(h, din, in, (size_t)n * width)) return rc;
+        launch_eval_pose<R>(P, P.obs_motion == OBS_MOTION_SCENE ? EVAL_FORM_SCENE : EVAL_FORM_GRID, what, agent, din, nullptr, nullptr, n,
+                            dout, points ? dpts.get() : nullptr, nullptr);
         HIPCHECK(h, hipGetLastError());
         HIPCHECK(h, hipDeviceSynchronize());
+        if (points)
+            if (int rc = download_real(h, points, dpts, (size_t)n * 18)) return rc;
         return download_real(h, value, dout, (size_t)n);
     });
+}
+// the raw value of agent `agent`'s grid at n points, from the device helper the rollout prices with (grid_value)
+extern "C" int mppi_eval_cost_grid(mppi_handle *h, int32_t agent, const double *xy, int32_t n, double *value) {
+    return eval_grid_impl(h, "mppi_eval_cost_grid", EVAL_GRID_POINTS, agent, xy, 2, n, value, nullptr);
 }
 
 // The footprint mode: one for every agent, kept across grid uploads and removals.  Every refusal stands before the device is
@@ -974,27 +983,7 @@ extern "C" int mppi_get_cost_grid_footprint(const mppi_handle *h, int32_t *mode)
 // g_foot of agent `agent`'s grid at n poses, and the nine world points, from the device function the rollout prices with
 // (grid_value_outline), whatever the handle's mode
 extern "C" int mppi_eval_cost_grid_footprint(mppi_handle *h, int32_t agent, const double *pose, int32_t n, double *value, double *points) {
-    if (!h) return MPPI_ERR_BAD_ARG;
-    if (!pose || !value || n < 1) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_cost_grid_footprint: bad argument");
-    if (agent < 0 || agent >= h->B) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_eval_cost_grid_footprint: agent %d not in [0, %d)", agent, h->B);
-    if (grid_of(h, agent).nx == 0) FAIL(h, MPPI_ERR_STATE, "mppi_eval_cost_grid_footprint: agent %d has no cost grid", agent);
-    HIPCHECK(h, hipSetDevice(h->cfg.device));
-    return with_real(h, [&](auto r) -> int {
-        using R = decltype(r);
-        KParams<R> P = make_params<R>(h, nullptr);
-        if (P.obs_motion == OBS_MOTION_SCENE) set_grids<R>(P, h->d_grids.get());  // (the kernel reads the descriptors themselves)
-        DevBuf<R> dpose, dout, dpts;
-        HIPCHECK(h, dpose.alloc(sizeof(R) * (size_t)n * 3));
-        HIPCHECK(h, dout.alloc(sizeof(R) * (size_t)n));
-        if (points) HIPCHECK(h, dpts.alloc(sizeof(R) * (size_t)n * 18));
-        if (int rc = upload_real(h, dpose, pose, (size_t)n * 3)) return rc;
-        launch_eval_grid_foot_at<R>(P, EVAL_GRID_FOOTPRINT, agent, dpose, nullptr, nullptr, n, dout, points ? dpts.get() : nullptr, nullptr);
-        HIPCHECK(h, hipGetLastError());
-        HIPCHECK(h, hipDeviceSynchronize());
-        if (points)
-            if (int rc = download_real(h, points, dpts, (size_t)n * 18)) return rc;
-        return download_real(h, value, dout, (size_t)n);
-    });
+    return eval_grid_impl(h, "mppi_eval_cost_grid_footprint", EVAL_GRID_FOOTPRINT, agent, pose, 3, n, value, points);
 }
 
 extern "C" int mppi_get_agent_status(mppi_handle *h, int32_t *idx_out, int32_t *path_end_out) {
@@ -2568,6 +2557,16 @@ static void eval_transition_mlp(mppi_handle *h, const KParams<float> &P, const v
     launch_eval_mlp(P, h->mlp, h->sw, (const float *)x, (const float *)v, n, (float *)out, nullptr);
 }
 static void eval_transition_mlp(mppi_handle *, const KParams<double> &, const void *, const void *, int, void *) {}  // rejected at create
+// What k_eval_pose finds behind the words make_params set, for agent 0: the composed table, else the one ingredient the handle
+// holds (a handle whose agent 0 has none: its circles alone); the grid under the outline, by the pose's yaw, where the mode says so
+static int eval_form(const mppi_handle *h, int obs_motion) {
+    const int foot = h->grid_footprint == MPPI_GRID_FOOTPRINT_OUTLINE ? EVAL_FORM_FOOT : 0;
+    if (obs_motion == OBS_MOTION_SCENE) return EVAL_FORM_SCENE | foot;
+    if (h->fleet_plan) return EVAL_FORM_PLANS;
+    if (tracks_of(h, 0).n > 0) return EVAL_FORM_TRACKS;
+    if (grid_of(h, 0).nx > 0) return EVAL_FORM_GRID | foot;
+    return EVAL_FORM_CIRCLES;
+}
 
 template <typename R>
 static int eval_impl(mppi_handle *h, int what, const double *x, const double *v, int n, int32_t *prev_idx, int update,
@@ -2606,14 +2605,7 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
             eval_transition_mlp(h, P, dx, dv, n, dout);
         else if (at) {
             if (h->fleet) launch_fleet_rows<R>(make_fleet(h, 0), nullptr);  // agent 0's mates as of the current states
-            const bool foot = h->grid_footprint == MPPI_GRID_FOOTPRINT_OUTLINE;  // (the grid under the outline, by the pose's yaw)
-            if (P.obs_motion == OBS_MOTION_SCENE && foot) launch_eval_scene_foot_at<R>(P, what, dx, di, ds, n, dout, nullptr);
-            else if (P.obs_motion == OBS_MOTION_SCENE) launch_eval_scene_at<R>(P, what, dx, di, ds, n, dout, nullptr);
-            else if (h->fleet_plan) launch_eval_plan_at<R>(P, what, dx, di, ds, n, dout, nullptr);
-            else if (tracks_of(h, 0).n > 0) launch_eval_tracks_at<R>(P, what, dx, di, ds, n, dout, nullptr);
-            else if (grid_of(h, 0).nx > 0 && foot) launch_eval_grid_foot_at<R>(P, what, 0, dx, di, ds, n, dout, nullptr, nullptr);
-            else if (grid_of(h, 0).nx > 0) launch_eval_grid_at<R>(P, what, 0, dx, di, ds, n, dout, nullptr);
-            else launch_eval_at<R>(P, what, dx, di, ds, n, dout, nullptr);
+            launch_eval_pose<R>(P, eval_form(h, P.obs_motion), what, 0, dx, di, ds, n, dout, nullptr, nullptr);
         }
         else
             launch_eval<R>(P, what, dx, dv, di, n, dout, nullptr);

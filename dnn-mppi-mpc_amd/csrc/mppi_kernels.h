@@ -509,10 +509,20 @@ void launch_eval_index(const KParams<R> &P, const R *xy, int stride, int n, int 
                        hipStream_t s);
 template <typename R>
 void launch_eval(const KParams<R> &P, int what, const R *x, const R *v, const int *idx, int n, R *out, hipStream_t s);
-// the same for a handle with moving obstacles: pose i is tested against the circles steps[i] rollout steps ahead of the current
-// clock (steps null: 0).  what: EVAL_COST_STAGE, EVAL_COST_TERMINAL or EVAL_COLLIDED
+// the same for a handle with moving obstacles (k_eval_pose): pose i is tested against P's circles steps[i] rollout steps ahead of
+// the current clock (steps null: 0), and against what `form` says P carries for agent `agent` -- its mates at point steps[i] of
+// their plans (set_fleet_plan; steps inside [0, T]), its tracks at point track_index(clock, steps[i], L) (set_tracks; any step
+// >= 0), its cost grid at the state's position in the hit and in the cost (set_grids), or all of them behind the SceneTable
+// (set_scene); | EVAL_FORM_FOOT: the grid priced under the vehicle's outline (the pose's yaw column).
+// what: EVAL_COST_STAGE, EVAL_COST_TERMINAL or EVAL_COLLIDED, or one of the two that read the grid alone (form: GRID or SCENE;
+// idx and steps are not read) -- EVAL_GRID_POINTS: x is xy[n][2] and out[i] the raw value of the grid there;
+// EVAL_GRID_FOOTPRINT: x is pose[n][3] = x, y, yaw, out[i] = g_foot of the grid there and pts (nullable) [n][9][2] its nine
+// world points.  pts is read by no other `what`.
+enum { EVAL_FORM_CIRCLES = 0, EVAL_FORM_PLANS = 1, EVAL_FORM_TRACKS = 2, EVAL_FORM_GRID = 3, EVAL_FORM_SCENE = 4, EVAL_FORM_FOOT = 8 };
+constexpr int EVAL_GRID_POINTS = 16, EVAL_GRID_FOOTPRINT = 17;
 template <typename R>
-void launch_eval_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
+void launch_eval_pose(const KParams<R> &P, int form, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out,
+                      R *pts, hipStream_t s);
 // Fleet avoidance (mppi_config.fleet_radius): what k_fleet_rows takes.  Agent b's table (AgentScene::obs, n_obs rows of circles
 // then n_obs rows of velocities) ends in n_agents - 1 mate rows; FleetClear is agent b's persistent clearance record.
 struct FleetClear {
@@ -537,32 +547,6 @@ struct FleetParams {
 };
 // the launch at the front of a fleet handle's slot: k_fleet_rows, or k_fleet_plan where F.plans is set
 template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s);
-// launch_eval_at for a handle in plan mode: agent 0's own circles at steps[i] of the clock and its mates at point steps[i] of
-// their plans (P carries the table: set_fleet_plan; steps inside [0, T])
-template <typename R>
-void launch_eval_plan_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
-// launch_eval_at for a handle whose agent 0 has obstacle tracks: its own circles at steps[i] of their clock and its tracks at
-// point track_index(clock, steps[i], L) (P carries the descriptors: set_tracks; any step >= 0)
-template <typename R>
-void launch_eval_tracks_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
-// launch_eval_at for a handle whose agent 0 has a cost grid: its own circles at steps[i] of their clock, and the grid's value
-// at the state's position in the hit and in the cost (P carries the descriptors: set_grids).  what == EVAL_GRID_POINTS: x is
-// xy[n][2] and out[i] the raw value of agent `agent`'s grid there (idx and steps are not read)
-constexpr int EVAL_GRID_POINTS = 16;
-template <typename R>
-void launch_eval_grid_at(const KParams<R> &P, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
-// launch_eval_at for a composed handle (P carries the SceneTable: set_scene): agent 0's circles, mates, tracks and grid together
-template <typename R>
-void launch_eval_scene_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
-// launch_eval_grid_at / launch_eval_scene_at with the grid priced under the vehicle's outline (the pose's yaw column).
-// what == EVAL_GRID_FOOTPRINT: x is pose[n][3] = x, y, yaw, out[i] = g_foot of agent `agent`'s grid there and pts (nullable)
-// [n][9][2] its nine world points
-constexpr int EVAL_GRID_FOOTPRINT = 17;
-template <typename R>
-void launch_eval_grid_foot_at(const KParams<R> &P, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out,
-                              R *pts, hipStream_t s);
-template <typename R>
-void launch_eval_scene_foot_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s);
 template <typename R> void launch_eval_filter(const R *xx, R *out, int T, int W, int mode, hipStream_t s);
 void launch_eval_weights(const double *S, int n, double beta, double *w, hipStream_t s);
 template <typename R> void launch_set_state_dev(const KParams<R> &P, const double *x_dev, int nx, hipStream_t s);

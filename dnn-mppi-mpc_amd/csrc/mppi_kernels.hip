@@ -2428,27 +2428,73 @@ __global__ __launch_bounds__(256) void k_eval(const KParams<R> P, int what, cons
     }
 }
 
-// `_is_collided` and the costs of a handle with moving obstacles: pose i against the circles steps[i] rollout steps ahead of the
-// current clock (steps null: 0 -- "now"); the clock is read from the device state as the rollout kernels read it
+// `_is_collided` and the costs of a handle with moving obstacles: pose i against P's circles (agent 0's) steps[i] rollout steps
+// ahead of the current clock (steps null: 0 -- "now"; the clock is read from the device state as the rollout kernels read it),
+// agent `agent`'s mates at point steps[i] of their plans (kept inside [0, T]), its tracks at the point that step and their clock
+// select (any step >= 0: the index is kept inside the table), and its grid's value at the state's position -- under the
+// vehicle's outline with EVAL_FORM_FOOT -- in the hit (g >= lethal) and, weighted, in the cost, as Rollout::costs prices them
+// (the stage methods pass agent 0).  `form` says where the ingredients' descriptors stand (EVAL_FORM_*, wave-uniform); a missing
+// ingredient is a null pointer, n == 0 or nx == 0, and everything is read from memory.  One kernel for every form: not a hot
+// path, so the branches are free.
+// EVAL_GRID_POINTS: x is xy[n][2] and out[i] = the raw value of the grid there; EVAL_GRID_FOOTPRINT: x is pose[n][3] = x, y,
+// yaw, out[i] = g_foot of the grid there and -- pts not null -- pts[i] its nine world points [9][2] (nothing else is read).
 template <typename R, int MODEL>
-__global__ __launch_bounds__(256) void k_eval_at(const KParams<R> P, int what, const R *__restrict__ x, const int *__restrict__ idx,
-                                                 const int *__restrict__ steps, int n, R *__restrict__ out) {
+__global__ __launch_bounds__(256) void k_eval_pose(KParams<R> P, int form, int what, int agent, const R *__restrict__ x,
+                                                   const int *__restrict__ idx, const int *__restrict__ steps, int n,
+                                                   R *__restrict__ out, R *__restrict__ pts) {
     constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
     const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool act = i < n, foot = (form & EVAL_FORM_FOOT) != 0;
+    const PlanPoint<R> *plans = nullptr;
+    TrackSet ts{};
+    GridSet<R> G{};
+    switch (form & ~EVAL_FORM_FOOT) {
+    case EVAL_FORM_SCENE: {  // (P's two words become the plan forms': mates_collided reads the threshold where it always has)
+        const SceneTable<R> tb = *scene_table(P);
+        scene_plan_words(P, tb.plans, tb.thr2);
+        plans = tb.plans;
+        if (tb.tracks != nullptr) ts = tb.tracks[agent];
+        if (tb.grids != nullptr) G = tb.grids[agent];
+    } break;
+    case EVAL_FORM_PLANS: plans = fleet_plan_table(P); break;
+    case EVAL_FORM_TRACKS: ts = track_sets(P)[agent]; break;
+    case EVAL_FORM_GRID: G = grid_sets(P)[agent]; break;
+    }
+    if (what == EVAL_GRID_POINTS) {
+        if (act) out[i] = G.nx > 0 ? grid_value(G, x[2 * (size_t)i], x[2 * (size_t)i + 1]) : R(0);
+        return;
+    }
+    if (what == EVAL_GRID_FOOTPRINT) {
+        if (act && G.nx > 0)
+            out[i] = grid_value_outline(G, P, x[3 * (size_t)i], x[3 * (size_t)i + 1], x[3 * (size_t)i + 2], pts ? pts + 18 * (size_t)i : nullptr);
+        return;
+    }
     const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
-    const bool act = i < n;
     R s[4] = {R(0), R(0), R(0), R(0)};
     if (act)
         for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
     const int j = act && steps ? steps[i] : 0;
-    const R tau = obstacle_time(P, obstacle_clock(P.st->iter, P.iter0) + j);
-    const bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
+    const int j0 = j < 0 ? 0 : j;
+    const long long iter = P.st->iter;
+    const R tau = obstacle_time(P, obstacle_clock(iter, P.iter0) + j);
+    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
+    if (plans != nullptr) hit |= mates_collided(P, plans, s[0], s[1], s[2], agent, j0 < P.T ? j0 : P.T);
+    if (ts.n > 0) {
+        const int at = track_index(track_clock(iter, ts.iter0, ts.L), j0, ts.L);
+        hit |= tracks_collided(P, static_cast<const PlanPoint<R> *>(ts.pts) + at, static_cast<const R *>(ts.thr2), ts.n, ts.L, s[0], s[1], s[2]);
+    }
+    R wg = R(0);
+    if (G.nx > 0) {
+        const R g = foot ? grid_value_outline(G, P, s[0], s[1], s[2]) : grid_value(G, s[0], s[1]);
+        hit |= g >= G.lethal;
+        wg = G.weight * g;
+    }
     if (what == EVAL_COLLIDED) {
         if (act) out[i] = hit ? R(1) : R(0);
     } else {
         const bool term = what == EVAL_COST_TERMINAL;
         const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
-                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit);
+                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit) + wg;
         if (act) out[i] = c;
     }
 }
@@ -2600,230 +2646,6 @@ __global__ __launch_bounds__(64) void k_fleet_plan(const FleetParams F) {
         const double d = sqrt(d2);
         q->min_dist = fmin(q->min_dist, d);
         if (d < F.contact) q->contact_iters += 1;
-    }
-}
-
-// k_eval_at for a handle in plan mode: agent 0's own circles steps[i] rollout steps ahead of its clock, and its mates at point
-// steps[i] of their plans (kept inside [0, T]: the host refuses anything else)
-template <typename R, int MODEL>
-__global__ __launch_bounds__(256) void k_eval_plan_at(const KParams<R> P, int what, const R *__restrict__ x, const int *__restrict__ idx,
-                                                      const int *__restrict__ steps, int n, R *__restrict__ out) {
-    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
-    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
-    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
-    const bool act = i < n;
-    R s[4] = {R(0), R(0), R(0), R(0)};
-    if (act)
-        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
-    const int j = act && steps ? steps[i] : 0;
-    const R tau = obstacle_time(P, obstacle_clock(P.st->iter, P.iter0) + j);
-    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
-    hit |= mates_collided(P, fleet_plan_table(P), s[0], s[1], s[2], 0, j < 0 ? 0 : j < P.T ? j : P.T);
-    if (what == EVAL_COLLIDED) {
-        if (act) out[i] = hit ? R(1) : R(0);
-    } else {
-        const bool term = what == EVAL_COST_TERMINAL;
-        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
-                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit);
-        if (act) out[i] = c;
-    }
-}
-
-// k_eval_at for a handle whose agent 0 has obstacle tracks: its own circles steps[i] rollout steps ahead of their clock, and
-// its tracks at the point that step and the tracks' clock select -- any step >= 0: the index is kept inside the table
-template <typename R, int MODEL>
-__global__ __launch_bounds__(256) void k_eval_tracks_at(const KParams<R> P, int what, const R *__restrict__ x, const int *__restrict__ idx,
-                                                        const int *__restrict__ steps, int n, R *__restrict__ out) {
-    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
-    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
-    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
-    const bool act = i < n;
-    R s[4] = {R(0), R(0), R(0), R(0)};
-    if (act)
-        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
-    const int j = act && steps ? steps[i] : 0;
-    const R tau = obstacle_time(P, obstacle_clock(P.st->iter, P.iter0) + j);
-    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
-    const TrackSet ts = track_sets(P)[0];
-    const int at = track_index(track_clock(P.st->iter, ts.iter0, ts.L), j < 0 ? 0 : j, ts.L);
-    hit |= tracks_collided(P, static_cast<const PlanPoint<R> *>(ts.pts) + at, static_cast<const R *>(ts.thr2), ts.n, ts.L, s[0], s[1], s[2]);
-    if (what == EVAL_COLLIDED) {
-        if (act) out[i] = hit ? R(1) : R(0);
-    } else {
-        const bool term = what == EVAL_COST_TERMINAL;
-        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
-                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit);
-        if (act) out[i] = c;
-    }
-}
-
-// k_eval_at for a handle whose agent 0 has a cost grid: its own circles steps[i] rollout steps ahead of their clock, and the
-// grid's value at the state's position -- in the hit (g >= lethal) and, weighted, in the cost, as Rollout::costs prices it.
-// EVAL_GRID_POINTS: x is xy[n][2] and out[i] = the raw value of agent `agent`'s grid there (nothing else is read).
-template <typename R, int MODEL>
-__global__ __launch_bounds__(256) void k_eval_grid_at(const KParams<R> P, int what, int agent, const R *__restrict__ x,
-                                                      const int *__restrict__ idx, const int *__restrict__ steps, int n, R *__restrict__ out) {
-    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
-    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool act = i < n;
-    const GridSet<R> G = grid_sets(P)[agent];
-    if (what == EVAL_GRID_POINTS) {
-        if (act) out[i] = G.nx > 0 ? grid_value(G, x[2 * (size_t)i], x[2 * (size_t)i + 1]) : R(0);
-        return;
-    }
-    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
-    R s[4] = {R(0), R(0), R(0), R(0)};
-    if (act)
-        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
-    const int j = act && steps ? steps[i] : 0;
-    const R tau = obstacle_time(P, obstacle_clock(P.st->iter, P.iter0) + j);
-    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
-    R wg = R(0);
-    if (G.nx > 0) {
-        const R g = grid_value(G, s[0], s[1]);
-        hit |= g >= G.lethal;
-        wg = G.weight * g;
-    }
-    if (what == EVAL_COLLIDED) {
-        if (act) out[i] = hit ? R(1) : R(0);
-    } else {
-        const bool term = what == EVAL_COST_TERMINAL;
-        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
-                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit) + wg;
-        if (act) out[i] = c;
-    }
-}
-
-// k_eval_at for a composed handle (mppi_set_scene_mode; P carries the SceneTable: set_scene): agent 0's own circles steps[i]
-// rollout steps ahead of their clock, its mates at point steps[i] of their plans (kept inside [0, T]), its tracks at the point
-// that step and their clock select, and its grid's value at the state's position in the hit and, weighted, in the cost --
-// k_eval_plan_at, k_eval_tracks_at and k_eval_grid_at in one, each ingredient guarded by its descriptor.  Everything is read
-// from memory.
-template <typename R, int MODEL>
-__global__ __launch_bounds__(256) void k_eval_scene_at(KParams<R> P, int what, const R *__restrict__ x, const int *__restrict__ idx,
-                                                       const int *__restrict__ steps, int n, R *__restrict__ out) {
-    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
-    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
-    const SceneTable<R> tb = *scene_table(P);
-    scene_plan_words(P, tb.plans, tb.thr2);
-    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
-    const bool act = i < n;
-    R s[4] = {R(0), R(0), R(0), R(0)};
-    if (act)
-        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
-    const int j = act && steps ? steps[i] : 0;
-    const int j0 = j < 0 ? 0 : j;
-    const long long iter = P.st->iter;
-    const R tau = obstacle_time(P, obstacle_clock(iter, P.iter0) + j);
-    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
-    if (tb.plans != nullptr) hit |= mates_collided(P, tb.plans, s[0], s[1], s[2], 0, j0 < P.T ? j0 : P.T);
-    if (tb.tracks != nullptr) {
-        const TrackSet ts = tb.tracks[0];
-        if (ts.n > 0) {
-            const int at = track_index(track_clock(iter, ts.iter0, ts.L), j0, ts.L);
-            hit |= tracks_collided(P, static_cast<const PlanPoint<R> *>(ts.pts) + at, static_cast<const R *>(ts.thr2), ts.n, ts.L, s[0], s[1], s[2]);
-        }
-    }
-    R wg = R(0);
-    if (tb.grids != nullptr) {
-        const GridSet<R> G = tb.grids[0];
-        if (G.nx > 0) {
-            const R g = grid_value(G, s[0], s[1]);
-            hit |= g >= G.lethal;
-            wg = G.weight * g;
-        }
-    }
-    if (what == EVAL_COLLIDED) {
-        if (act) out[i] = hit ? R(1) : R(0);
-    } else {
-        const bool term = what == EVAL_COST_TERMINAL;
-        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
-                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit) + wg;
-        if (act) out[i] = c;
-    }
-}
-
-// k_eval_grid_at with the grid priced under the vehicle's outline (mppi_set_cost_grid_footprint: grid_value_outline of the
-// pose's yaw column, as Rollout::costs prices it with FOOT).  EVAL_GRID_FOOTPRINT: x is pose[n][3] = x, y, yaw, out[i] = g_foot
-// of agent `agent`'s grid there and -- pts not null -- pts[i] its nine world points [9][2] (nothing else is read).  Kernels of
-// their own, so that k_eval_grid_at and k_eval_scene_at keep their text.
-template <typename R, int MODEL>
-__global__ __launch_bounds__(256) void k_eval_grid_foot_at(const KParams<R> P, int what, int agent, const R *__restrict__ x,
-                                                           const int *__restrict__ idx, const int *__restrict__ steps, int n,
-                                                           R *__restrict__ out, R *__restrict__ pts) {
-    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
-    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool act = i < n;
-    const GridSet<R> G = grid_sets(P)[agent];
-    if (what == EVAL_GRID_FOOTPRINT) {
-        if (act && G.nx > 0)
-            out[i] = grid_value_outline(G, P, x[3 * (size_t)i], x[3 * (size_t)i + 1], x[3 * (size_t)i + 2], pts ? pts + 18 * (size_t)i : nullptr);
-        return;
-    }
-    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
-    R s[4] = {R(0), R(0), R(0), R(0)};
-    if (act)
-        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
-    const int j = act && steps ? steps[i] : 0;
-    const R tau = obstacle_time(P, obstacle_clock(P.st->iter, P.iter0) + j);
-    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
-    R wg = R(0);
-    if (G.nx > 0) {
-        const R g = grid_value_outline(G, P, s[0], s[1], s[2]);
-        hit |= g >= G.lethal;
-        wg = G.weight * g;
-    }
-    if (what == EVAL_COLLIDED) {
-        if (act) out[i] = hit ? R(1) : R(0);
-    } else {
-        const bool term = what == EVAL_COST_TERMINAL;
-        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
-                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit) + wg;
-        if (act) out[i] = c;
-    }
-}
-// k_eval_scene_at likewise
-template <typename R, int MODEL>
-__global__ __launch_bounds__(256) void k_eval_scene_foot_at(KParams<R> P, int what, const R *__restrict__ x, const int *__restrict__ idx,
-                                                            const int *__restrict__ steps, int n, R *__restrict__ out) {
-    constexpr int NX = MODEL == MODEL_RACE ? 4 : 3;
-    const int lane = threadIdx.x & 63, i = blockIdx.x * blockDim.x + threadIdx.x;
-    const SceneTable<R> tb = *scene_table(P);
-    scene_plan_words(P, tb.plans, tb.thr2);
-    const ObsLanesMoving<R> obs = load_obstacles_moving(P, lane);  // (all lanes of the wave take part)
-    const bool act = i < n;
-    R s[4] = {R(0), R(0), R(0), R(0)};
-    if (act)
-        for (int q = 0; q < NX; ++q) s[q] = x[(size_t)i * NX + q];
-    const int j = act && steps ? steps[i] : 0;
-    const int j0 = j < 0 ? 0 : j;
-    const long long iter = P.st->iter;
-    const R tau = obstacle_time(P, obstacle_clock(iter, P.iter0) + j);
-    bool hit = collided<MODEL == MODEL_RACE, true>(P, s[0], s[1], s[2], obs, false, R(0), R(1), tau);
-    if (tb.plans != nullptr) hit |= mates_collided(P, tb.plans, s[0], s[1], s[2], 0, j0 < P.T ? j0 : P.T);
-    if (tb.tracks != nullptr) {
-        const TrackSet ts = tb.tracks[0];
-        if (ts.n > 0) {
-            const int at = track_index(track_clock(iter, ts.iter0, ts.L), j0, ts.L);
-            hit |= tracks_collided(P, static_cast<const PlanPoint<R> *>(ts.pts) + at, static_cast<const R *>(ts.thr2), ts.n, ts.L, s[0], s[1], s[2]);
-        }
-    }
-    R wg = R(0);
-    if (tb.grids != nullptr) {
-        const GridSet<R> G = tb.grids[0];
-        if (G.nx > 0) {
-            const R g = grid_value_outline(G, P, s[0], s[1], s[2]);
-            hit |= g >= G.lethal;
-            wg = G.weight * g;
-        }
-    }
-    if (what == EVAL_COLLIDED) {
-        if (act) out[i] = hit ? R(1) : R(0);
-    } else {
-        const bool term = what == EVAL_COST_TERMINAL;
-        const R c = state_cost_row<R, MODEL>(P, term ? P.wt : P.ws, term ? P.wrap_term : P.wrap_stage,
-                                             P.ref + 4 * (act ? idx[i] : 0), s[0], s[1], s[2], s[3], hit) + wg;
-        if (act) out[i] = c;
     }
 }
 
@@ -3130,47 +2952,11 @@ void launch_eval(const KParams<R> &P, int what, const R *x, const R *v, const in
     else hipLaunchKernelGGL((k_eval<R, MODEL_RACE>), grid, block, 0, s, P, what, x, v, idx, n, out);
 }
 template <typename R>
-void launch_eval_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
+void launch_eval_pose(const KParams<R> &P, int form, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out,
+                      R *pts, hipStream_t s) {
     const dim3 grid((n + 255) / 256), block(256);
-    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
-    else hipLaunchKernelGGL((k_eval_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
-}
-template <typename R>
-void launch_eval_plan_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
-    const dim3 grid((n + 255) / 256), block(256);
-    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_plan_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
-    else hipLaunchKernelGGL((k_eval_plan_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
-}
-template <typename R>
-void launch_eval_tracks_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
-    const dim3 grid((n + 255) / 256), block(256);
-    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_tracks_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
-    else hipLaunchKernelGGL((k_eval_tracks_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
-}
-template <typename R>
-void launch_eval_grid_at(const KParams<R> &P, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
-    const dim3 grid((n + 255) / 256), block(256);
-    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_grid_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, agent, x, idx, steps, n, out);
-    else hipLaunchKernelGGL((k_eval_grid_at<R, MODEL_RACE>), grid, block, 0, s, P, what, agent, x, idx, steps, n, out);
-}
-template <typename R>
-void launch_eval_scene_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
-    const dim3 grid((n + 255) / 256), block(256);
-    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_scene_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
-    else hipLaunchKernelGGL((k_eval_scene_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
-}
-template <typename R>
-void launch_eval_grid_foot_at(const KParams<R> &P, int what, int agent, const R *x, const int *idx, const int *steps, int n, R *out,
-                              R *pts, hipStream_t s) {
-    const dim3 grid((n + 255) / 256), block(256);
-    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_grid_foot_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, agent, x, idx, steps, n, out, pts);
-    else hipLaunchKernelGGL((k_eval_grid_foot_at<R, MODEL_RACE>), grid, block, 0, s, P, what, agent, x, idx, steps, n, out, pts);
-}
-template <typename R>
-void launch_eval_scene_foot_at(const KParams<R> &P, int what, const R *x, const int *idx, const int *steps, int n, R *out, hipStream_t s) {
-    const dim3 grid((n + 255) / 256), block(256);
-    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_scene_foot_at<R, MODEL_DIFF>), grid, block, 0, s, P, what, x, idx, steps, n, out);
-    else hipLaunchKernelGGL((k_eval_scene_foot_at<R, MODEL_RACE>), grid, block, 0, s, P, what, x, idx, steps, n, out);
+    if (P.model == MODEL_DIFF) hipLaunchKernelGGL((k_eval_pose<R, MODEL_DIFF>), grid, block, 0, s, P, form, what, agent, x, idx, steps, n, out, pts);
+    else hipLaunchKernelGGL((k_eval_pose<R, MODEL_RACE>), grid, block, 0, s, P, form, what, agent, x, idx, steps, n, out, pts);
 }
 template <typename R> void launch_fleet_rows(const FleetParams &F, hipStream_t s) {
     if (!F.plans) hipLaunchKernelGGL(k_fleet_rows<R>, dim3(F.n_agents), dim3(64), 0, s, F);
@@ -3227,14 +3013,8 @@ extern "C" int mppi_debug_stamps(unsigned long long *out, int n) {
     template void launch_weights<R>(const KParams<R> &, double, double, double *, hipStream_t);           \
     template void launch_eval_index<R>(const KParams<R> &, const R *, int, int, int, int, int *, int *, hipStream_t); \
     template void launch_eval<R>(const KParams<R> &, int, const R *, const R *, const int *, int, R *, hipStream_t);   \
-    template void launch_eval_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
+    template void launch_eval_pose<R>(const KParams<R> &, int, int, int, const R *, const int *, const int *, int, R *, R *, hipStream_t); \
     template void launch_fleet_rows<R>(const FleetParams &, hipStream_t);                                            \
-    template void launch_eval_plan_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
-    template void launch_eval_tracks_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
-    template void launch_eval_grid_at<R>(const KParams<R> &, int, int, const R *, const int *, const int *, int, R *, hipStream_t); \
-    template void launch_eval_scene_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
-    template void launch_eval_grid_foot_at<R>(const KParams<R> &, int, int, const R *, const int *, const int *, int, R *, R *, hipStream_t); \
-    template void launch_eval_scene_foot_at<R>(const KParams<R> &, int, const R *, const int *, const int *, int, R *, hipStream_t); \
     template void launch_eval_filter<R>(const R *, R *, int, int, int, hipStream_t);                                 \
     template void launch_set_state_dev<R>(const KParams<R> &, const double *, int, hipStream_t);                     \
     template void launch_viz<R>(const KParams<R> &, const R *, const R *, long long, float *, float *, hipStream_t);

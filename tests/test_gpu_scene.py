@@ -1,5 +1,5 @@
 """Composed scenes on the device (mppi_set_scene_mode): a cost grid, obstacle tracks and the mates' plans on one
-handle -- the SPEC 7 rollout forms and k_eval_scene_at -- against the f64 reference of tests/scene_checks.py (the oracles of the
+handle -- the SPEC 7 rollout forms and k_eval_pose -- against the f64 reference of tests/scene_checks.py (the oracles of the
 three features composed: nothing new is computed there), the LDS layout on either side of its budget, what must stay bit for
 bit, a closed loop with a rolling costmap and ticking tracks, and the switch.  K = 256 throughout; the tolerances, the margin
 rule and the loop's bars are those of test_gpu_cost_grid.py / test_gpu_fleet.py."""
@@ -319,7 +319,7 @@ def contour_point(grid, inside, outside):
 @pytest.mark.parametrize("model", ["diff", "race"])
 def test_hit_and_cost_either_side_of_every_boundary(model, precision):
     """Agent 0 of a composed fleet handle at clock 2: poses 1e-3 m either side of a track's threshold circle, of a mate's, and
-    of the grid's lethal contour, at several steps ahead -- through k_eval_scene_at"""
+    of the grid's lethal contour, at several steps ahead -- through k_eval_pose"""
     import dnn_mppi_mpc_amd as pkg
     CLOCK = 2
     if model == "diff":
