@@ -52,8 +52,13 @@ class _ControllerBase:
                      obstacle_tracks=None, cost_grid=None, compose_scene=False):
         if obstacle_velocities is not None and obstacle_circles is None:
             raise ValueError("obstacle_velocities needs obstacle_circles")
-        # a create-time switch (mppi_config.obstacle_motion): any of the three keywords sets it
-        cfg.update(obstacle_motion=int(obstacle_velocities is not None or obstacle_tracks is not None or cost_grid is not None))
+        # a create-time switch (mppi_config.obstacle_motion): any of the three keywords sets it; with the learned model the
+        # scene handle is value 2 (value 1 stays refused there), which ``compose_scene=True`` alone asks for as well
+        scene = obstacle_velocities is not None or obstacle_tracks is not None or cost_grid is not None
+        if cfg.get("model") == capi.MODEL_DIFFDRIVE_MLP:
+            cfg.update(obstacle_motion=capi.OBSTACLE_MOTION_LEARNED if scene or compose_scene else 0)
+        else:
+            cfg.update(obstacle_motion=int(scene))
         cfg.update(precision=capi.PREC_F64 if precision in ("f64", "float64") else capi.PREC_F32,
                    device=int(device), seed=int(seed), collision_penalty=1.0e10, filter_window=10)
         self._pg = process_group
@@ -501,7 +506,9 @@ class MPPIAlgorithms(_ControllerBase):
     ``learned_dynamics``: the residual model x + dt (f(x, v) + MLP([x, v])) as a ``state_dict`` (or the torch module) with
     the keys ``input_layer.*``, ``hidden_layer.{i}.*``, ``out_layer.*``: Linear(5, H) -> n x [Linear(H, H), tanh] ->
     Linear(H, 3) with H in {64, 128, 256, 512} and n in {1, 2, 3, 4} (`Engine.SUPPORTED_MLP`); ``learned_scalers``: its
-    ``StandardScaler`` statistics (`Engine.set_mlp`).
+    ``StandardScaler`` statistics (`Engine.set_mlp`).  With any of ``obstacle_velocities``, ``obstacle_tracks``, ``cost_grid``
+    or ``compose_scene=True`` the learned controller is built as a scene handle (``obstacle_motion=2``): moving circles,
+    obstacle tracks and a cost grid are priced along every learned rollout as they are along the analytic one.
     """
 
     def __init__(self, delta_t, ref_path, max_speed, max_omega, num_samples_K, num_horizons_T, param_exploration,
@@ -556,6 +563,7 @@ class MPPIAlgorithms(_ControllerBase):
             clamp_u_after_update=int(self.visualze_sampled_trajs),  # :145-149
             filter_mode=capi.FILTER_TORCH if variant == "torch" else capi.FILTER_DIFFDRIVE,  # _torch.py:252-263
             obstacle_model=(capi.OBSTACLE_CIRCLE if obstacle_circles is not None or obstacle_tracks is not None or cost_grid is not None
+                            or (compose_scene and learned_dynamics is not None)  # (the learned scene handle needs a model)
                             else capi.OBSTACLE_NONE),
             raise_at_path_end=0,
             safety_margin=0.0 if safety_margin_rate is None else self.safefy_margin_rate,

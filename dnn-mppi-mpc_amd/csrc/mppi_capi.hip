@@ -282,6 +282,10 @@ static const mppi_handle::GridOwn &grid_of(const mppi_handle *h, int a) {
 static bool scene_composed(const mppi_handle *h) { return h->scene_mode == MPPI_SCENE_COMPOSED; }
 static int scene_ingredients(const mppi_handle *h) { return (h->fleet_plan ? 1 : 0) + (max_tracks(h) > 0 ? 1 : 0) + (h->any_grid ? 1 : 0); }
 static bool scene_form(const mppi_handle *h) { return scene_composed(h) && scene_ingredients(h) >= 2; }
+// the learned model's scene handle (mppi_config.obstacle_motion = 2): every launch carries the SceneTable (set_scene_learned)
+static bool learned_scene(const mppi_handle *h) { return h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP && h->cfg.obstacle_motion == 2; }
+// the create-time value a handle of this model needs for a scene, as the setters' refusals name it
+static int motion_value(const mppi_handle *h) { return h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP ? 2 : 1; }
 // some agent has obstacles: the obstacle instantiations serve and the records carry collision counts
 static bool any_obstacles(const mppi_handle *h) {
     if (max_tracks(h) > 0) return true;  // (tracks stand in no circle table: a handle may have tracks and no circles)
@@ -311,6 +315,7 @@ template <typename R> static RolloutPlan front_plan(const mppi_handle *h, const 
 static int upload_scenes(mppi_handle *h);
 static int upload_tracks(mppi_handle *h);
 static int upload_grids(mppi_handle *h);
+static int upload_scene_table(mppi_handle *h);
 static void drop_graph(mppi_handle *h);
 static int build_fleet_tables(mppi_handle *h, int only);
 
@@ -357,13 +362,23 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         CREATE_FAIL(MPPI_ERR_UNSUPPORTED,
              "MPPI_WAYPOINT_PER_ROLLOUT restates the diff-drive files' index bookkeeping (mppi_differential_drive.py:228,:244); "
              "the race-car files search from the x0 call's index (MPPI_WAYPOINT_FROZEN)");
-    if (c.obstacle_motion != 0 && c.obstacle_motion != 1)
-        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: obstacle_motion %d is neither 0 (static) nor 1 (constant velocity)", c.obstacle_motion);
+    // (2, MPPI_OBSTACLE_MOTION_LEARNED: the learned model's scene handle -- inside the library it is value 1 everywhere)
+    const bool scene_handle = c.obstacle_motion == 2 && c.model == MPPI_MODEL_DIFFDRIVE_MLP;
+    if (c.obstacle_motion != 0 && c.obstacle_motion != 1 && !scene_handle)
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: obstacle_motion %d is neither 0 (static) nor 1 (constant velocity)%s", c.obstacle_motion,
+                    c.obstacle_motion == 2 ? "; 2 (the learned model's scene handle) goes with MPPI_MODEL_DIFFDRIVE_MLP only" : "");
     if (c.obstacle_motion && c.obstacle_model == MPPI_OBSTACLE_NONE)
-        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: obstacle_motion = 1 needs an obstacle model (MPPI_OBSTACLE_CIRCLE or _OUTLINE), got MPPI_OBSTACLE_NONE");
-    if (c.obstacle_motion && c.model == MPPI_MODEL_DIFFDRIVE_MLP)
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: obstacle_motion = %d needs an obstacle model (MPPI_OBSTACLE_CIRCLE or _OUTLINE), got MPPI_OBSTACLE_NONE", c.obstacle_motion);
+    if (c.obstacle_motion == 1 && c.model == MPPI_MODEL_DIFFDRIVE_MLP)
         CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "moving obstacles (obstacle_motion = 1) are served by the analytic models only: the "
-                                          "learned-dynamics rollout (MPPI_MODEL_DIFFDRIVE_MLP) tests static circles");
+                                          "learned-dynamics rollout (MPPI_MODEL_DIFFDRIVE_MLP) tests static circles; its scene "
+                                          "handle is obstacle_motion = 2 (moving circles, obstacle tracks and cost grids)");
+    if (scene_handle && c.fleet_radius > 0)
+        CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "fleet avoidance (fleet_radius = %g) is served by the analytic models only: the mates' plans are "
+                                          "rolled out with analytic dynamics (limit: fleet_radius = 0 with MPPI_MODEL_DIFFDRIVE_MLP)", c.fleet_radius);
+    if (scene_handle && c.K_global != c.K)
+        CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "a learned-dynamics scene handle (obstacle_motion = 2) is not sharded (limit: K_global = K, "
+                                          "got K = %d, K_global = %d)", c.K, c.K_global);
     if (!(c.fleet_radius >= 0) || !std::isfinite(c.fleet_radius))
         CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: fleet_radius %g is not a finite radius >= 0 (0: fleet avoidance off)", c.fleet_radius);
     if (c.fleet_radius > 0 && c.n_agents < 2)
@@ -496,6 +511,14 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
         const std::vector<FleetClear> none(B, FleetClear{INFINITY, 0});
         if ((e = hipMemcpy(h->d_clear, none.data(), B * sizeof(FleetClear), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
         if (build_fleet_tables(h, -1) != MPPI_OK || upload_scenes(h) != MPPI_OK) {  // (no own circles yet: the mates' rows alone)
+            g_create_error = h->err;
+            mppi_destroy(h);
+            return MPPI_ERR_HIP;
+        }
+    }
+    if (scene_handle) {  // every launch of such a handle reads the table (make_params): all null until a setter fills it
+        if (int rc = zeroed(h->d_scene, sizeof(SceneTable<double>), "hipMalloc(scene table)")) return rc;
+        if (upload_scene_table(h) != MPPI_OK) {
             g_create_error = h->err;
             mppi_destroy(h);
             return MPPI_ERR_HIP;
@@ -657,7 +680,7 @@ static int set_agent_circles(mppi_handle *h, const char *who, int32_t agent, con
 #define NEEDS_MOTION(h, who)                                                                                            \
     if (!(h)->cfg.obstacle_motion)                                                                                      \
         FAIL(h, MPPI_ERR_STATE, "%s: the handle was created with obstacle_motion = 0 (static circles: mppi_set_obstacles); " \
-                                "moving circles need mppi_config.obstacle_motion = 1 at mppi_create", who)
+                                "moving circles need mppi_config.obstacle_motion = %d at mppi_create", who, motion_value(h))
 
 extern "C" int mppi_set_obstacles(mppi_handle *h, const double *xyr, int32_t m) {
     if (!h) return MPPI_ERR_BAD_ARG;
@@ -718,7 +741,7 @@ static int upload_tracks(mppi_handle *h) {
 static int set_tracks_impl(mppi_handle *h, const char *who, int agent, const double *xy, const double *radius, int32_t n, int32_t L) {
     if (!h->cfg.obstacle_motion)
         FAIL(h, MPPI_ERR_STATE, "%s: the handle was created with obstacle_motion = 0; obstacle tracks need "
-                                "mppi_config.obstacle_motion = 1 at mppi_create", who);
+                                "mppi_config.obstacle_motion = %d at mppi_create", who, motion_value(h));
     if (h->fleet && !scene_composed(h))
         FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: a fleet handle (fleet_radius > 0) takes no obstacle tracks: its plan mode uses the same "
                                       "parameter words (limit: fleet_radius = 0)", who);
@@ -857,7 +880,7 @@ static int set_grid_impl(mppi_handle *h, const char *who, int agent, const doubl
                          double resolution, double weight, double lethal) {
     if (!h->cfg.obstacle_motion)
         FAIL(h, MPPI_ERR_STATE, "%s: the handle was created with obstacle_motion = 0; a cost grid needs "
-                                "mppi_config.obstacle_motion = 1 at mppi_create", who);
+                                "mppi_config.obstacle_motion = %d at mppi_create", who, motion_value(h));
     if (h->fleet && !scene_composed(h))
         FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: a fleet handle (fleet_radius > 0) takes no cost grid: its plan mode uses the same "
                                       "parameter words (limit: fleet_radius = 0)", who);
@@ -960,7 +983,7 @@ extern "C" int mppi_set_cost_grid_footprint(mppi_handle *h, int32_t mode) {
         FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_cost_grid_footprint: mode %d is neither MPPI_GRID_FOOTPRINT_CENTRE nor MPPI_GRID_FOOTPRINT_OUTLINE", mode);
     if (!h->cfg.obstacle_motion)
         FAIL(h, MPPI_ERR_STATE, "mppi_set_cost_grid_footprint: the handle was created with obstacle_motion = 0; a cost grid needs "
-                                "mppi_config.obstacle_motion = 1 at mppi_create");
+                                "mppi_config.obstacle_motion = %d at mppi_create", motion_value(h));
     if (mode == MPPI_GRID_FOOTPRINT_OUTLINE && h->cfg.obstacle_model != MPPI_OBSTACLE_OUTLINE)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_cost_grid_footprint: the outline footprint needs obstacle_model = MPPI_OBSTACLE_OUTLINE "
                                       "(limit: a disc is served by inflating the map by its radius)");
@@ -1076,6 +1099,12 @@ static int pack_mlp(mppi_handle *h, const char *who, int32_t hidden, int32_t n_h
     if (h->B > 1 && sw.mlp.f32)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: MPPI_MLP_F32 is set, and the f32-input kernel runs one agent per handle "
                                       "(n_agents = %d)", who, h->B);
+    // a scene handle (obstacle_motion = 2) has scene forms of the split kernels only
+    if (learned_scene(h) && !f16_range)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: max |weight| = %.4g exceeds the f16 range, and the f32-input kernel that serves such a "
+                                      "model has no scene form (limit: obstacle_motion = 0)", who, wmax);
+    if (learned_scene(h) && sw.mlp.f32)
+        FAIL(h, MPPI_ERR_UNSUPPORTED, "%s: MPPI_MLP_F32 is set, and the f32-input kernel has no scene form (limit: obstacle_motion = 0)", who);
     const int CT = H / 32;  // column tiles of 32 outputs
     const size_t n_in = (size_t)CT * 1 * 64 * 4, n_h = (size_t)CT * (H / 8) * 64 * 4;
     const size_t total = n_in + H + MLP_MAX_HIDDEN * (n_h + H) + 3 * (size_t)H;
@@ -1401,7 +1430,7 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.chol[2] = (float)l11;
     P.ref = (const R *)sc0.ref;
     P.obs = (const R *)sc0.obs;
-    P.obs_motion = c.obstacle_motion;
+    P.obs_motion = c.obstacle_motion ? 1 : 0;  // (2, the learned scene handle, is 1 in here; the carriers below overwrite it)
     P.iter0 = sc0.iter0;
     P.scenes = h->d_scenes;
     P.u = (const R *)h->d_u.get();
@@ -1421,6 +1450,10 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.hyp_slots = h->d_hyp_slots;
     // (a composed handle with two or more of the three below: the one table that points at all of them, and the launch's
     // staged bytes of plans and tracks; with fewer it takes the single-ingredient carrier like any other handle)
+    if (learned_scene(h)) {  // (one carrier whatever the handle holds: the table built from the owners that exist, and the footprint word)
+        set_scene_learned<R>(P, h->d_scene.get(), h->grid_footprint);
+        return P;
+    }
     if (scene_form(h)) {
         set_scene<R>(P, h->d_scene.get(), h->fleet_plan ? h->B : 0, max_tracks(h));
         return P;
@@ -2744,7 +2777,7 @@ extern "C" int mppi_set_scene_mode(mppi_handle *h, int32_t mode) {
         FAIL(h, MPPI_ERR_BAD_ARG, "mppi_set_scene_mode: mode %d is neither MPPI_SCENE_EXCLUSIVE nor MPPI_SCENE_COMPOSED", mode);
     if (!h->cfg.obstacle_motion)
         FAIL(h, MPPI_ERR_STATE, "mppi_set_scene_mode: the handle was created with obstacle_motion = 0; fleet plans, obstacle tracks and "
-                                "cost grids need mppi_config.obstacle_motion = 1 at mppi_create");
+                                "cost grids need mppi_config.obstacle_motion = %d at mppi_create", motion_value(h));
     if (!h->fused)
         FAIL(h, MPPI_ERR_UNSUPPORTED, "mppi_set_scene_mode: composed scenes are served for horizons T <= 128 (T = %d runs the unfused rollout)",
              h->cfg.T);

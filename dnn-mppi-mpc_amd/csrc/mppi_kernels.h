@@ -302,6 +302,18 @@ template <typename R> inline void set_scene(KParams<R> &P, const void *table, in
     P.pad_scenes[1] = (long long)(((unsigned long long)(unsigned)s.tracks << 32) | (unsigned long long)(unsigned)s.plans);
     P.obs_motion = OBS_MOTION_SCENE;
 }
+// Learned-dynamics scene handles (mppi_config.obstacle_motion = 2; mppi_mlp.hip) use this carrier for EVERY launch,
+// whatever the handle holds: moving circles alone, tracks, a grid or both.  `plans` stays null (no fleets on learned handles)
+// and nothing is staged in LDS -- at a step of the learned rollout every lane reads the same track point --, so pad_scenes[1],
+// the staged byte counts of the analytic composed launch, is free there: it carries the footprint word (MPPI_GRID_FOOTPRINT_*),
+// which the learned scene forms read at run time where the analytic forms take a template argument.  No pinned layout moves:
+// KParams, SceneTable and GridSet are what they were, and k_eval_pose overwrites both words itself (scene_plan_words).
+template <typename R> inline void set_scene_learned(KParams<R> &P, const void *table, int footprint) {
+    P.pad_scenes[0] = (long long)reinterpret_cast<uintptr_t>(table);
+    P.pad_scenes[1] = (long long)footprint;
+    P.obs_motion = OBS_MOTION_SCENE;
+}
+template <typename R> __host__ __device__ inline int learned_scene_footprint(const KParams<R> &P) { return (int)P.pad_scenes[1]; }
 // the lower node and the fraction of coordinate x along an axis of n >= 2 nodes (mppi_grid_index.h: inside [0, n - 2] and
 // [0, 1] whatever x is, a NaN included)
 __host__ __device__ inline int grid_index(float x, float o, float inv, int n, float &f) { return mppi_grid_index_f32(x, o, inv, n, &f); }

@@ -203,6 +203,102 @@ __device__ __forceinline__ void mlp_advance(const KParams<float> &P, const ObsLa
     }
 }
 
+// ---- scene handles (mppi_config.obstacle_motion = 2) ----------------------------------------------------------
+// What wave 0 of a scene form carries across the step loop beside the moving table: the iteration counter the clocks count from
+// and its agent -- two scalar registers.  The descriptors themselves are NOT kept: held across the layers' GEMMs they cost the
+// kernels 100 - 170 bytes of scratch per lane beyond their static twins, so mlp_scene_at reads them afresh at
+// every priced step, three dependent scalar loads that hit the scalar cache, under ~0.5 % of a step.
+struct MlpScene {
+    long long iter;
+    int agent;
+};
+__device__ __forceinline__ MlpScene mlp_scene_load(const KParams<float> &, const DevState &sv, int agent) { return MlpScene{sv.iter, agent}; }
+// The agent's track and grid descriptors out of the handle's SceneTable (KParams::pad_scenes[0], OBS_MOTION_SCENE; `plans` is null
+// on a learned handle and not read), the two clocks and the footprint word (KParams::pad_scenes[1], learned_scene_footprint).
+// The step is uniform over the wave, so everything here but the grid's cells is: the uniform words go through readfirstlane
+// and sit in SGPRs.  A missing ingredient is a null table, trk_n == 0 or nx == 0.
+struct MlpSceneAt {
+    const PlanPoint<float> *trk_pts = nullptr;
+    const float *trk_thr2 = nullptr;
+    int trk_n = 0, trk_L = 1, trk_clock = 0;
+    GridSet<float> grid = {nullptr, 0, 0, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int foot = 0;   // MPPI_GRID_FOOTPRINT_OUTLINE: the grid under the nine outline points
+    int clock = 0;  // the circles' (obstacle_clock)
+};
+__device__ __forceinline__ MlpSceneAt mlp_scene_at(const KParams<float> &P, const MlpScene &S) {
+    MlpSceneAt sc;
+    const SceneTable<float> tb = *scene_table(P);
+    if (tb.tracks != nullptr) {
+        const TrackSet ts = tb.tracks[S.agent];
+        sc.trk_pts = static_cast<const PlanPoint<float> *>(ts.pts);
+        sc.trk_thr2 = static_cast<const float *>(ts.thr2);
+        sc.trk_n = __builtin_amdgcn_readfirstlane(ts.n);
+        sc.trk_L = __builtin_amdgcn_readfirstlane(ts.L);
+        sc.trk_clock = __builtin_amdgcn_readfirstlane(track_clock(S.iter, ts.iter0, ts.L));
+    }
+    if (tb.grids != nullptr) {
+        sc.grid = tb.grids[S.agent];
+        sc.grid.nx = __builtin_amdgcn_readfirstlane(sc.grid.nx);
+        sc.grid.ny = __builtin_amdgcn_readfirstlane(sc.grid.ny);
+    }
+    sc.foot = __builtin_amdgcn_readfirstlane(learned_scene_footprint(P));
+    sc.clock = __builtin_amdgcn_readfirstlane(obstacle_clock(S.iter, P.iter0));
+    return sc;
+}
+
+// mlp_advance for a scene form: the state after step t of the loop is stage call j = t + 1 -- the circles stand at
+// c + v obstacle_time(clock + j), the tracks at point track_index(trk_clock, j, L) (read from memory: at a step every lane
+// reads the same point), the grid is read at the state's position or under its outline -- and the terminal call prices the
+// same state with j = T.  A state is hit when any ingredient says so; weight g joins the stage cost behind the control term
+// and the terminal cost, as Rollout::costs has it (mppi_kernels.hip).
+__device__ __forceinline__ void mlp_advance_scene(const KParams<float> &P, const ObsLanesMoving<float> &obs, const MlpScene &SV, int c,
+                                                  int t, float r0, float r1, float r2, float u0, float u1, float v0, float v1,
+                                                  MlpLane &L) {
+    const float *__restrict__ ref = P.ref;
+    mlp_euler(P, r0, r1, r2, v0, v1, L);
+    auto nearest = [&](int from) {
+        float best = dist2(ref, from, L.x, L.y);
+        int bj = 0;
+#pragma unroll 4
+        for (int j = 1; j < P.window; ++j) {
+            const bool ok = from + j < P.n_ref;
+            const float d = ok ? dist2(ref, min(from + j, P.n_ref - 1), L.x, L.y) : INFINITY;
+            if (d < best) { best = d; bj = j; }
+        }
+        return from + bj;
+    };
+    const bool threads = P.sequential || P.per_rollout;
+    const int idx = nearest(threads ? L.p : c);
+    if (threads) L.p = idx;
+    if (P.accumulate || t == P.T - 1) {
+        const int j = t + 1;
+        const MlpSceneAt SC = mlp_scene_at(P, SV);
+        bool hit = collided<false, true>(P, L.x, L.y, L.yaw, obs, false, 0.f, 1.f, obstacle_time(P, SC.clock + j));
+        if (SC.trk_n > 0)
+            hit |= tracks_collided(P, SC.trk_pts + track_index(SC.trk_clock, j, SC.trk_L), SC.trk_thr2, SC.trk_n, SC.trk_L, L.x, L.y, L.yaw);
+        float wg = 0.f;
+        const bool has_grid = SC.grid.nx > 0;
+        if (has_grid) {
+            const float g = SC.foot ? grid_value_outline(SC.grid, P, L.x, L.y, L.yaw) : grid_value(SC.grid, L.x, L.y);
+            hit |= g >= SC.grid.lethal;
+            wg = SC.grid.weight * g;
+        }
+        float stage = stage_cost<float, MODEL_DIFF>(P, (bool)P.wrap_stage, idx, L.x, L.y, L.yaw, 0.f, hit, u0, u1, v0, v1);
+        if (has_grid) stage += wg;
+        L.S = P.accumulate ? L.S + stage : stage;
+        if (t == P.T - 1) {
+            int idx_term = idx;
+            if (threads) {  // the terminal call moves the index once more (:244)
+                L.p = nearest(L.p);
+                idx_term = L.p;
+            }
+            float term = terminal_cost<float, MODEL_DIFF>(P, (bool)P.wrap_term, idx_term, L.x, L.y, L.yaw, 0.f, hit);
+            if (has_grid) term += wg;
+            L.S += term;
+        }
+    }
+}
+
 // this tile's softmin record {rho, eta, eta2, pad, W[T][2]} (wave 0)
 __device__ __forceinline__ void mlp_record(const KParams<float> &P, float *__restrict__ partials, unsigned iter, int k, int c,
                                            bool valid, bool live, MlpLane &L, int lane) {
@@ -701,6 +797,12 @@ __device__ __forceinline__ float *mlp_agent_records(const KParams<float> &P, flo
     return partials + (size_t)a * P.slots * record_len(P.T, 4);
 }
 
+// The hook points of the two textually included bodies (mppi_mlp_h3_body.h, mppi_mlp_w_body.h): the statement that loads the
+// obstacle table `obs` (behind `sv`, in front of the early return) and wave 0's advance call.  For the static kernels below they
+// are the tokens that stood in the bodies, so those kernels compile to the code they had; the scene forms at the end of the
+// section define their own.
+#define MLP_BODY_OBS_LOAD const ObsLanes<float> obs = load_obstacles(P, lane);
+#define MLP_BODY_ADVANCE mlp_advance(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
 template <bool VIZ, int NW, int RT, int TERMS = 3>
 __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3(const KParams<float> P, const MlpParams Q,
                                                                float *__restrict__ partials, const MlpViz V) {
@@ -746,6 +848,64 @@ __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_agents(co
     const MlpViz V{};
 #include "mppi_mlp_w_body.h"
 }
+
+// ------------------------------------------------------------------------------------------
+// The scene forms (mppi_config.obstacle_motion = 2): the same bodies with the moving table, the agent's scene
+// (MlpScene) and mlp_advance_scene behind the two hooks -- moving circles, obstacle tracks and a cost grid priced along every
+// learned rollout.  One form per width of k_rollout_mlp_w and one of the default 8-wave three-term k_rollout_mlp_h3, each
+// single-agent and batched: ten symbols.  No visualisation form (the transition is the static kernels').  `scene_agent`: whose
+// descriptors the body's MLP_BODY_OBS_LOAD reads.
+// ------------------------------------------------------------------------------------------
+#undef MLP_BODY_OBS_LOAD
+#undef MLP_BODY_ADVANCE
+#define MLP_BODY_OBS_LOAD                                                      \
+    const ObsLanesMoving<float> obs = load_obstacles_moving(P, lane);          \
+    const MlpScene SC = mlp_scene_load(P, sv, scene_agent);
+#define MLP_BODY_ADVANCE mlp_advance_scene(PL, obs, SC, c, t, r0, r1, r2, u0, u1, v0, v1, L);
+// agent a's view for a scene form: mlp_agent's, and the clock its own circles were uploaded at (AgentScene::iter0)
+__device__ __forceinline__ KParams<float> mlp_agent_scene(const KParams<float> &P, int a) {
+    KParams<float> A = mlp_agent(P, a);
+    A.iter0 = P.scenes[a].iter0;
+    return A;
+}
+__global__ __launch_bounds__(64 * 8, 1) void k_rollout_mlp_h3_scene(const KParams<float> P, const MlpParams Q, float *__restrict__ partials) {
+    constexpr bool VIZ = false;
+    constexpr int NW = 8, RT = 2, TERMS = 3, scene_agent = 0;
+    const MlpViz V{};
+#include "mppi_mlp_h3_body.h"
+}
+__global__ __launch_bounds__(64 * 8, 1) void k_rollout_mlp_h3_scene_agents(const KParams<float> P_all, const MlpParams *__restrict__ models,
+                                                                          float *__restrict__ partials_all) {
+    constexpr bool VIZ = false;
+    constexpr int NW = 8, RT = 2, TERMS = 3;
+    const int scene_agent = (int)blockIdx.y;
+    const KParams<float> P = mlp_agent_scene(P_all, scene_agent);
+    MlpParamsConst &Q = mlp_agent_model(models, scene_agent);
+    float *__restrict__ partials = mlp_agent_records(P_all, partials_all, scene_agent);
+    const MlpViz V{};
+#include "mppi_mlp_h3_body.h"
+}
+template <int H>
+__global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_scene(const KParams<float> P, const MlpParams Q, float *__restrict__ partials) {
+    constexpr bool VIZ = false;
+    constexpr int scene_agent = 0;
+    const MlpViz V{};
+#include "mppi_mlp_w_body.h"
+}
+template <int H>
+__global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_scene_agents(const KParams<float> P_all,
+                                                                                  const MlpParams *__restrict__ models,
+                                                                                  float *__restrict__ partials_all) {
+    constexpr bool VIZ = false;
+    const int scene_agent = (int)blockIdx.y;
+    const KParams<float> P = mlp_agent_scene(P_all, scene_agent);
+    MlpParamsConst &Q = mlp_agent_model(models, scene_agent);
+    float *__restrict__ partials = mlp_agent_records(P_all, partials_all, scene_agent);
+    const MlpViz V{};
+#include "mppi_mlp_w_body.h"
+}
+#undef MLP_BODY_OBS_LOAD
+#undef MLP_BODY_ADVANCE
 #undef PH
 #ifdef MPPI_STAMPS
 extern "C" int mppi_debug_mlp_phases(unsigned long long *out) {
@@ -799,6 +959,24 @@ template <int H> static KernelLaunch w_agents_entry() {
     static KernelEntry e("k_rollout_mlp_w_agents<%d>", H);
     return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w_agents<H>), e, H, w_shmem(H));
 }
+// the scene forms (obstacle_motion = 2): the static forms' workgroups and LDS
+static KernelLaunch h3_scene_entry() {
+    static KernelEntry e("k_rollout_mlp_h3_scene");
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_h3_scene), e, 64 * 8, h3_shmem(8, 2));
+}
+static KernelLaunch h3_scene_agents_entry() {
+    static KernelEntry e("k_rollout_mlp_h3_scene_agents");
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_h3_scene_agents), e, 64 * 8, h3_shmem(8, 2));
+}
+template <int H> static KernelLaunch w_scene_entry() {
+    static KernelEntry e("k_rollout_mlp_w_scene<%d>", H);
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w_scene<H>), e, H, w_shmem(H));
+}
+template <int H> static KernelLaunch w_scene_agents_entry() {
+    static KernelEntry e("k_rollout_mlp_w_scene_agents<%d>", H);
+    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w_scene_agents<H>), e, H, w_shmem(H));
+}
+template <int H> static KernelLaunch w_scene_plan(bool agents) { return agents ? w_scene_agents_entry<H>() : w_scene_entry<H>(); }
 template <int H> static KernelLaunch w_plan(bool viz, bool agents) {
     return viz ? w_entry<H, true>() : agents ? w_agents_entry<H>() : w_entry<H, false>();
 }
@@ -807,7 +985,19 @@ RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches
     const int form = sw.mlp.form < 0 ? H3_FORM_DEFAULT : sw.mlp.form;
     const int agents = !viz && P.n_agents > 1 ? P.n_agents : 1;
     RolloutPlan p;
-    if (mlp_is_w(Q)) {  // (MPPI_MLP_FORM / MPPI_MLP_TERMS / MPPI_MLP_F32 concern the 512 x 3 and 512 x 2 shapes only)
+    // a scene handle (obstacle_motion = 2: make_params marks its launches OBS_MOTION_SCENE) takes the scene form of its shape;
+    // the visualisation rollouts and the batched transition price nothing and keep the static kernels
+    const bool scene = !viz && P.obs_motion == OBS_MOTION_SCENE;
+    if (scene && mlp_is_w(Q)) {
+        switch (Q.hidden) {
+        case 64: p.k = w_scene_plan<64>(agents > 1); break;
+        case 128: p.k = w_scene_plan<128>(agents > 1); break;
+        case 256: p.k = w_scene_plan<256>(agents > 1); break;
+        case 512: p.k = w_scene_plan<512>(agents > 1); break;
+        }
+    } else if (scene) {  // (512 x 3 / 512 x 2: the default form always -- mppi_set_mlp refuses the f32-input cases on a scene handle)
+        p.k = agents > 1 ? h3_scene_agents_entry() : h3_scene_entry();
+    } else if (mlp_is_w(Q)) {  // (MPPI_MLP_FORM / MPPI_MLP_TERMS / MPPI_MLP_F32 concern the 512 x 3 and 512 x 2 shapes only)
         switch (Q.hidden) {  // (mppi_set_mlp admits only these)
         case 64: p.k = w_plan<64>(viz, agents > 1); break;
         case 128: p.k = w_plan<128>(viz, agents > 1); break;

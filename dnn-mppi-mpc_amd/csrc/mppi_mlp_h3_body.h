@@ -3,6 +3,8 @@
 // exactly the code it did as a self-contained kernel (an inlined __device__ body is optimised before it is inlined and
 // changed the register allocation and scratch of every instantiation).  In scope: P, Q, partials, V and the template
 // parameters of the including kernel.  Not a header: no include guard, nothing else may include it.
+// Two hook points are the includer's (macros, mppi_mlp.hip): MLP_BODY_OBS_LOAD -- the statement that loads `obs` behind `sv` --
+// and MLP_BODY_ADVANCE -- the advance call of wave 0.  For the static kernels they expand to the tokens that stood here.
 #ifdef MPPI_STAMPS
     unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_t = clock64();
 #endif
@@ -19,7 +21,7 @@
     const int k0 = ((int)blockIdx.x + (VIZ ? V.block0 : 0)) * M, k = k0 + lane;
     const KParams<float> PL = mlp_stage_path(P, ref_lds, RT == 1 ? H3_REF_LDS_32 : MLP_REF_LDS_MAX);
     const DevState sv = load_state(P, P.st);
-    const ObsLanes<float> obs = load_obstacles(P, lane);
+    MLP_BODY_OBS_LOAD  // (hook: the obstacle table, and whatever the includer's advance call reads beside it)
     if (!VIZ && k0 + M <= sv.k_start) return;
     const bool in_tile = lane < M;  // (a 32-sample tile: the upper half of wave 0 carries no sample)
     const bool valid = in_tile && k < P.K, live = valid && k >= sv.k_start;
@@ -106,7 +108,7 @@
                              : opt_row ? V.opt + (size_t)t * 3 : smp_row ? V.smp + ((size_t)k * P.T + t) * 3 : nullptr;
                 if (dst) { dst[0] = L.x; dst[1] = L.y; dst[2] = L.yaw; }
             } else {
-                mlp_advance(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
+                MLP_BODY_ADVANCE  // (hook: the includer's mlp_advance call)
             }
         }
         PH(9);

@@ -88,7 +88,7 @@ class Engine:
 
     def set_obstacles(self, circles, agent=None, velocities=None):
         """``agent``: as in `set_ref_path`; an agent given no circles collides with nothing.  ``velocities``: [m, 2] = vx, vy
-        in metres per second, for a handle created with ``obstacle_motion=1`` (the circles then stand where given at this
+        in metres per second, for a handle created with ``obstacle_motion=1`` (the learned model: ``2``) (the circles then stand where given at this
         call and move with the handle's iteration counter, see mppi_config.obstacle_motion); None: they stand still."""
         c = np.ascontiguousarray(circles, dtype=np.float64).reshape(-1, 3)
         if velocities is not None:
@@ -119,7 +119,7 @@ class Engine:
 
     def set_obstacle_tracks(self, xy, radii, agent=None):
         """Obstacles given as predicted positions: ``xy`` [n, L, 2], point i of a track its centre i control steps after this
-        call (it holds the last one afterwards), ``radii`` [n]; for a handle created with ``obstacle_motion=1``.  ``agent``: as
+        call (it holds the last one afterwards), ``radii`` [n]; for a handle created with ``obstacle_motion=1`` (learned: ``2``).  ``agent``: as
         in `set_ref_path`.  n = 0 removes the set (mppi_set_obstacle_tracks / mppi_set_agent_obstacle_tracks)."""
         r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
         p = np.ascontiguousarray(xy, dtype=np.float64)
@@ -144,7 +144,7 @@ class Engine:
     def set_cost_grid(self, cells, origin=(0.0, 0.0), resolution=1.0, weight=1.0, lethal=float("inf"), agent=None):
         """A costmap priced along every rollout: ``cells`` [ny, nx], ``cells[iy, ix]`` the value at ``origin + (ix, iy) *
         resolution``, looked up bilinearly at every state's (x, y); the state's cost gains ``weight * g`` and it counts as
-        collided when ``g >= lethal``.  For a handle created with ``obstacle_motion=1``.  ``agent``: as in `set_ref_path`.
+        collided when ``g >= lethal``.  For a handle created with ``obstacle_motion=1`` (the learned model: ``2``).  ``agent``: as in `set_ref_path`.
         ``cells=None`` removes the grid (mppi_set_cost_grid / mppi_set_agent_cost_grid)."""
         if cells is None:
             c, ny, nx = None, 0, 0

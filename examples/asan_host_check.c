@@ -47,8 +47,36 @@ int main(void) {
     c.obstacle_model = MPPI_OBSTACLE_CIRCLE;
     c.model = MPPI_MODEL_DIFFDRIVE_MLP;
     EXPECT(mppi_create(&c, &h) == MPPI_ERR_UNSUPPORTED && strstr(mppi_last_error(NULL), "MPPI_MODEL_DIFFDRIVE_MLP") != NULL);
-    c.obstacle_motion = 2;
+    EXPECT(strstr(mppi_last_error(NULL), "obstacle_motion = 2") != NULL); /* (the refusal points to the learned scene handle) */
+    /* the learned model's scene handle, value 2: its create paths up to the device check */
+    c.obstacle_motion = MPPI_OBSTACLE_MOTION_LEARNED;
+    c.model = MPPI_MODEL_DIFFDRIVE;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG && strstr(mppi_last_error(NULL), "MPPI_MODEL_DIFFDRIVE_MLP") != NULL);
+    c.model = MPPI_MODEL_RACECAR;
     EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG);
+    c.model = MPPI_MODEL_DIFFDRIVE_MLP;
+    c.obstacle_model = MPPI_OBSTACLE_NONE;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_BAD_ARG && strstr(mppi_last_error(NULL), "MPPI_OBSTACLE_NONE") != NULL);
+    c.obstacle_model = MPPI_OBSTACLE_CIRCLE;
+    c.waypoint_mode = MPPI_WAYPOINT_FROZEN;
+    c.n_agents = 3;
+    c.fleet_radius = 0.4;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_UNSUPPORTED && strstr(mppi_last_error(NULL), "fleet") != NULL);
+    c.fleet_radius = 0.0;
+    c.n_agents = 0;
+    c.K_global = 512;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_UNSUPPORTED && strstr(mppi_last_error(NULL), "shard") != NULL);
+    c.K_global = 0;
+    c.precision = MPPI_PREC_F64;
+    EXPECT(mppi_create(&c, &h) == MPPI_ERR_UNSUPPORTED);
+    c.precision = MPPI_PREC_F32;
+    {   /* past every refusal: the handle, or -- without an MI355X -- the device check */
+        const int rc2 = mppi_create(&c, &h);
+        EXPECT(rc2 == MPPI_OK || rc2 == MPPI_ERR_NO_DEVICE);
+        if (rc2 == MPPI_OK) EXPECT(mppi_destroy(h) == MPPI_OK);
+        h = NULL;
+    }
+    c.waypoint_mode = MPPI_WAYPOINT_SEQUENTIAL;
     c.model = MPPI_MODEL_DIFFDRIVE;
     /* fleet avoidance: likewise refused before any device work (obstacle_model is MPPI_OBSTACLE_CIRCLE here) */
     c.obstacle_motion = 1;

@@ -25,6 +25,9 @@
 extern "C" {
 #endif
 
+/* 8: mppi_config.fleet_radius.  mppi_config.obstacle_motion = 2 (MPPI_OBSTACLE_MOTION_LEARNED, the learned model's scene handle)
+ * arrived WITHOUT a bump -- no symbol, field or layout changed -- so a caller that needs it probes by the answer of mppi_create:
+ * a library without it refuses value 2 with MPPI_ERR_BAD_ARG whatever the model. */
 #define MPPI_ABI_VERSION 8
 
 typedef enum {
@@ -80,6 +83,9 @@ typedef enum {
  *  CIRCLE   robot disc of radius 0.5*margin vs circles (mppi_differential_drive_obs.py:301-313)
  *  OUTLINE  9 outline points of the (l*m) x (w*m) box vs circles (mppi_race_car_obstacle.py:241-274) */
 typedef enum { MPPI_OBSTACLE_NONE = 0, MPPI_OBSTACLE_CIRCLE = 1, MPPI_OBSTACLE_OUTLINE = 2 } mppi_obstacle_model;
+
+/* mppi_config.obstacle_motion = 2: the learned model's scene handle (documented at the field) */
+#define MPPI_OBSTACLE_MOTION_LEARNED 2
 
 /*
  * Mirrors the constructor keywords of MPPIAlgorithms (mppi_differential_drive.py:44-60,
@@ -155,7 +161,20 @@ typedef struct {
      * One iteration is one tick: all speculation rounds of an iteration see the same clock, mppi_run_closed_loop advances
      * the obstacles with the plant without the host, and a replayed graph (MPPI_GRAPH=1) reads the clock afresh from the
      * device.  mppi_set_iteration replays noise and must not move obstacles: it shifts iter0 by the same amount.
-     * Needs an obstacle model (MPPI_OBSTACLE_NONE: MPPI_ERR_BAD_ARG); MPPI_MODEL_DIFFDRIVE_MLP: MPPI_ERR_UNSUPPORTED. */
+     * Needs an obstacle model (MPPI_OBSTACLE_NONE: MPPI_ERR_BAD_ARG); MPPI_MODEL_DIFFDRIVE_MLP: MPPI_ERR_UNSUPPORTED (the
+     * message points to value 2).
+     * 2 (MPPI_OBSTACLE_MOTION_LEARNED): THE LEARNED MODEL'S SCENE HANDLE.  Accepted with MPPI_MODEL_DIFFDRIVE_MLP only (an
+     * analytic model: MPPI_ERR_BAD_ARG, as any unknown value) and, like 1, only with an obstacle model.  A value of its own
+     * because value 1 with the learned model has always been refused with MPPI_ERR_UNSUPPORTED and callers probe for that
+     * answer: the refusal stays, and a caller that wants the scene says so.  Everything documented for value 1 holds on such
+     * a handle with the learned transition in place of the analytic one: the clock and its re-basing, mppi_set_obstacles_moving,
+     * mppi_set_obstacle_tracks, mppi_set_cost_grid, mppi_set_cost_grid_footprint, mppi_set_scene_mode and their per-agent forms
+     * with their exclusivity rules and their T <= 128 limit, j = t + 1 for the state after step t + 1 of a rollout and j = T
+     * for the terminal call, the stage methods (agent 0's scene), mppi_stats.n_collided.  Batched agents keep their own scenes
+     * and their own models (mppi_set_agent_mlp).  Limits, each MPPI_ERR_UNSUPPORTED: fleet_radius > 0 (the mates' plans are
+     * rolled out with analytic dynamics), K_global > K (sharding), and on such a handle the f32-input model cases of
+     * mppi_set_mlp (MPPI_MLP_F32=1, weights beyond the f16 range): the scene is priced by the f16-split kernels only, and
+     * MPPI_MLP_FORM / MPPI_MLP_TERMS do not apply.  f64 is refused for the learned model as before. */
     int32_t obstacle_motion;
     int32_t reserved0;
     /* Fleet avoidance.  0: off (zero-initialised configs: as before).  > 0: every agent of the handle sees every other agent
