@@ -167,42 +167,6 @@ __device__ __forceinline__ void mlp_controls_viz(const KParams<float> &P, const 
     clamp_controls(P, v0, v1);  // every row, the nominal one included (:148,:158)
 }
 
-// this call's waypoint index and costs behind the Euler step
-__device__ __forceinline__ void mlp_advance(const KParams<float> &P, const ObsLanes<float> &obs, int c, int t, float r0, float r1,
-                                            float r2, float u0, float u1, float v0, float v1, MlpLane &L) {
-    const float *__restrict__ ref = P.ref;
-    mlp_euler(P, r0, r1, r2, v0, v1, L);
-    // waypoint index of this call: per-lane, so the sequential index threads through the sample's own
-    // calls in order by construction (mppi_differential_drive.py:228)
-    auto nearest = [&](int from) {
-        float best = dist2(ref, from, L.x, L.y);
-        int bj = 0;
-#pragma unroll 4
-        for (int j = 1; j < P.window; ++j) {
-            const bool ok = from + j < P.n_ref;
-            const float d = ok ? dist2(ref, min(from + j, P.n_ref - 1), L.x, L.y) : INFINITY;
-            if (d < best) { best = d; bj = j; }
-        }
-        return from + bj;
-    };
-    const bool threads = P.sequential || P.per_rollout;  // the index moves with this sample's calls (:228)
-    const int idx = nearest(threads ? L.p : c);
-    if (threads) L.p = idx;
-    if (P.accumulate || t == P.T - 1) {
-        const bool hit = collided<false>(P, L.x, L.y, L.yaw, obs);
-        const float stage = stage_cost<float, MODEL_DIFF>(P, (bool)P.wrap_stage, idx, L.x, L.y, L.yaw, 0.f, hit, u0, u1, v0, v1);
-        L.S = P.accumulate ? L.S + stage : stage;
-        if (t == P.T - 1) {
-            int idx_term = idx;
-            if (threads) {  // the terminal call moves the index once more (:244)
-                L.p = nearest(L.p);
-                idx_term = L.p;
-            }
-            L.S += terminal_cost<float, MODEL_DIFF>(P, (bool)P.wrap_term, idx_term, L.x, L.y, L.yaw, 0.f, hit);
-        }
-    }
-}
-
 // ---- scene handles (mppi_config.obstacle_motion = 2) ----------------------------------------------------------
 // What wave 0 of a scene form carries across the step loop beside the moving table: the iteration counter the clocks count from
 // and its agent -- two scalar registers.  The descriptors themselves are NOT kept: held across the layers' GEMMs they cost the
@@ -212,7 +176,6 @@ struct MlpScene {
     long long iter;
     int agent;
 };
-__device__ __forceinline__ MlpScene mlp_scene_load(const KParams<float> &, const DevState &sv, int agent) { return MlpScene{sv.iter, agent}; }
 // The agent's track and grid descriptors out of the handle's SceneTable (KParams::pad_scenes[0], OBS_MOTION_SCENE; `plans` is null
 // on a learned handle and not read), the two clocks and the footprint word (KParams::pad_scenes[1], learned_scene_footprint).
 // The step is uniform over the wave, so everything here but the grid's cells is: the uniform words go through readfirstlane
@@ -246,16 +209,34 @@ __device__ __forceinline__ MlpSceneAt mlp_scene_at(const KParams<float> &P, cons
     return sc;
 }
 
-// mlp_advance for a scene form: the state after step t of the loop is stage call j = t + 1 -- the circles stand at
-// c + v obstacle_time(clock + j), the tracks at point track_index(trk_clock, j, L) (read from memory: at a step every lane
-// reads the same point), the grid is read at the state's position or under its outline -- and the terminal call prices the
-// same state with j = T.  A state is hit when any ingredient says so; weight g joins the stage cost behind the control term
-// and the terminal cost, as Rollout::costs has it (mppi_kernels.hip).
-__device__ __forceinline__ void mlp_advance_scene(const KParams<float> &P, const ObsLanesMoving<float> &obs, const MlpScene &SV, int c,
-                                                  int t, float r0, float r1, float r2, float u0, float u1, float v0, float v1,
-                                                  MlpLane &L) {
+// What wave 0's advance call prices a state against: the static kernels carry the obstacle table, the scene forms the moving
+// table and their MlpScene.  One loader, called behind `sv` and in front of the early return.
+template <bool SCENE> struct MlpObs {
+    ObsLanes<float> obs;
+};
+template <> struct MlpObs<true> {
+    ObsLanesMoving<float> obs;
+    MlpScene scene;
+};
+template <bool SCENE>
+__device__ __forceinline__ MlpObs<SCENE> mlp_obs_load(const KParams<float> &P, const DevState &sv, int lane, int agent) {
+    if constexpr (SCENE) return MlpObs<true>{load_obstacles_moving(P, lane), MlpScene{sv.iter, agent}};
+    else return MlpObs<false>{load_obstacles(P, lane)};
+}
+
+// this call's waypoint index and costs behind the Euler step.
+// SCENE: the state after step t of the loop is stage call j = t + 1 -- the circles stand at c + v obstacle_time(clock + j), the
+// tracks at point track_index(trk_clock, j, L) (read from memory: at a step every lane reads the same point), the grid is read
+// at the state's position or under its outline -- and the terminal call prices the same state with j = T.  A state is hit when
+// any ingredient says so; weight g joins the stage cost behind the control term and the terminal cost, as Rollout::costs has
+// it (mppi_kernels.hip).
+template <bool SCENE>
+__device__ __forceinline__ void mlp_advance(const KParams<float> &P, const MlpObs<SCENE> &O, int c, int t, float r0, float r1, float r2,
+                                            float u0, float u1, float v0, float v1, MlpLane &L) {
     const float *__restrict__ ref = P.ref;
     mlp_euler(P, r0, r1, r2, v0, v1, L);
+    // waypoint index of this call: per-lane, so the sequential index threads through the sample's own
+    // calls in order by construction (mppi_differential_drive.py:228)
     auto nearest = [&](int from) {
         float best = dist2(ref, from, L.x, L.y);
         int bj = 0;
@@ -267,21 +248,26 @@ __device__ __forceinline__ void mlp_advance_scene(const KParams<float> &P, const
         }
         return from + bj;
     };
-    const bool threads = P.sequential || P.per_rollout;
+    const bool threads = P.sequential || P.per_rollout;  // the index moves with this sample's calls (:228)
     const int idx = nearest(threads ? L.p : c);
     if (threads) L.p = idx;
     if (P.accumulate || t == P.T - 1) {
-        const int j = t + 1;
-        const MlpSceneAt SC = mlp_scene_at(P, SV);
-        bool hit = collided<false, true>(P, L.x, L.y, L.yaw, obs, false, 0.f, 1.f, obstacle_time(P, SC.clock + j));
-        if (SC.trk_n > 0)
-            hit |= tracks_collided(P, SC.trk_pts + track_index(SC.trk_clock, j, SC.trk_L), SC.trk_thr2, SC.trk_n, SC.trk_L, L.x, L.y, L.yaw);
+        bool hit, has_grid = false;
         float wg = 0.f;
-        const bool has_grid = SC.grid.nx > 0;
-        if (has_grid) {
-            const float g = SC.foot ? grid_value_outline(SC.grid, P, L.x, L.y, L.yaw) : grid_value(SC.grid, L.x, L.y);
-            hit |= g >= SC.grid.lethal;
-            wg = SC.grid.weight * g;
+        if constexpr (SCENE) {
+            const int j = t + 1;
+            const MlpSceneAt SC = mlp_scene_at(P, O.scene);
+            hit = collided<false, true>(P, L.x, L.y, L.yaw, O.obs, false, 0.f, 1.f, obstacle_time(P, SC.clock + j));
+            if (SC.trk_n > 0)
+                hit |= tracks_collided(P, SC.trk_pts + track_index(SC.trk_clock, j, SC.trk_L), SC.trk_thr2, SC.trk_n, SC.trk_L, L.x, L.y, L.yaw);
+            has_grid = SC.grid.nx > 0;
+            if (has_grid) {
+                const float g = SC.foot ? grid_value_outline(SC.grid, P, L.x, L.y, L.yaw) : grid_value(SC.grid, L.x, L.y);
+                hit |= g >= SC.grid.lethal;
+                wg = SC.grid.weight * g;
+            }
+        } else {
+            hit = collided<false>(P, L.x, L.y, L.yaw, O.obs);
         }
         float stage = stage_cost<float, MODEL_DIFF>(P, (bool)P.wrap_stage, idx, L.x, L.y, L.yaw, 0.f, hit, u0, u1, v0, v1);
         if (has_grid) stage += wg;
@@ -340,7 +326,7 @@ __global__ __launch_bounds__(64 * MLP_WAVES, 1) void k_rollout_mlp(const KParams
     const int k0 = blockIdx.x * MLP_M, k = k0 + lane;
     const KParams<float> PL = mlp_stage_path(P, ref_lds);
     const DevState sv = load_state(P, P.st);
-    const ObsLanes<float> obs = load_obstacles(P, lane);
+    const MlpObs<false> obs = mlp_obs_load<false>(P, sv, lane, 0);
     if (k0 + MLP_M <= sv.k_start) return;  // every sample of the tile is final: its record stands
     const bool valid = k < P.K, live = valid && k >= sv.k_start;
     const int c = sv.c;
@@ -399,7 +385,7 @@ __global__ __launch_bounds__(64 * MLP_WAVES, 1) void k_rollout_mlp(const KParams
                 r1 += o.v[1];
                 r2 += o.v[2];
             }
-            mlp_advance(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
+            mlp_advance<false>(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
         }
         // zbuf / ypart are rewritten only after the next barrier sequence: wave 0 writes zbuf at the top of
         // the next step while the others wait at that step's first barrier
@@ -422,7 +408,7 @@ __global__ __launch_bounds__(64 * MLP_WAVES, 1) void k_rollout_mlp(const KParams
 // 16-byte load per lane.  Per k-step and wave: 4 LDS reads + 8 global loads feed 24 MFMAs (768 cycles).
 // ------------------------------------------------------------------------------------------
 using half8 = __attribute__((ext_vector_type(8))) _Float16;
-constexpr int H3_PITCH = 520, H3_ZPITCH = 24, H3_STEPS = MLP_H / 16;
+constexpr int H3_ZPITCH = 24;  // (the activations' row pitch is H + 8 halfs, a layer's k-steps H / 16)
 constexpr int H3_FORM_DEFAULT = 1;  // (H3_FORM_8x64, see the forms below)
 
 __device__ __forceinline__ void split_h3(float v, _Float16 &hi, _Float16 &lo) {
@@ -528,7 +514,7 @@ template <int RT> __device__ __forceinline__ void h3_zero(f32x16 (&ac)[RT][2]) {
 template <bool HAS_NEXT, int RT, int TERMS = 3, int H = MLP_H>
 __device__ __forceinline__ void gemm_pass_h3(f32x16 (&ac)[RT][2], const _Float16 *a_hi, const _Float16 *a_lo, const H3Pass &w,
                                              const H3Pass &next, H3Ring &ring, int lane) {
-    constexpr int n_steps = H / 16, pitch = H + 8;  // (H3_STEPS, H3_PITCH at 512)
+    constexpr int n_steps = H / 16, pitch = H + 8;
     const int aoff = (lane & 31) * pitch + 8 * (lane >> 5);
     auto load_a = [&](int s, H3FragA &f) {
 #pragma unroll
@@ -769,8 +755,9 @@ constexpr int h3_ref_cap(int rt, int h) { return rt == 1 ? H3_REF_LDS_32 : h == 
 // Several agents per launch (mppi_config.n_agents > 1): workgroup row a = blockIdx.y runs agent a, which sees
 // the handle's parameters with its own nominal controls u + 2 T a, costs and waypoint outputs S / pout + K a, controller
 // state st + a (x0, x0 index, iteration), noise (Philox stream noise_stream + a, or its tensor of the caller's ring) and
-// record heads + 4 slots a, its reference path and obstacle table (AgentScene) -- the layout of k_rollout_fused<..., MULTI>,
-// which k_finalize's batched path reads.  The
+// record heads + 4 slots a, its reference path, obstacle table and the clock its circles were uploaded at (AgentScene; only a
+// scene form reads iter0, in the static kernels the load is dead) -- the layout of k_rollout_fused<..., MULTI>, which
+// k_finalize's batched path reads.  The
 // records themselves: mlp_agent_records.  The single-agent kernels never call these, so their code stays what it was.
 __device__ __forceinline__ KParams<float> mlp_agent(const KParams<float> &P, int a) {
     KParams<float> A = P;
@@ -782,6 +769,7 @@ __device__ __forceinline__ KParams<float> mlp_agent(const KParams<float> &P, int
     if (P.eps) A.eps += (size_t)a * P.K * P.T * 2;  // eps_tensor(A, iter, 0) == eps_tensor(P, iter, a)
     A.heads += (size_t)a * P.slots * 4;
     agent_scene(A, P.scenes, a);  // its path and obstacles: mlp_stage_path's "fits in LDS" falls out per agent
+    A.iter0 = P.scenes[a].iter0;
     return A;
 }
 // Agent a's entry of the handle's model table (MlpParams[n_agents], mppi_set_agent_mlp), seen as CONSTANT memory: the host
@@ -797,16 +785,14 @@ __device__ __forceinline__ float *mlp_agent_records(const KParams<float> &P, flo
     return partials + (size_t)a * P.slots * record_len(P.T, 4);
 }
 
-// The hook points of the two textually included bodies (mppi_mlp_h3_body.h, mppi_mlp_w_body.h): the statement that loads the
-// obstacle table `obs` (behind `sv`, in front of the early return) and wave 0's advance call.  For the static kernels below they
-// are the tokens that stood in the bodies, so those kernels compile to the code they had; the scene forms at the end of the
-// section define their own.
-#define MLP_BODY_OBS_LOAD const ObsLanes<float> obs = load_obstacles(P, lane);
-#define MLP_BODY_ADVANCE mlp_advance(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
+// The f16-split kernels: eight wrappers around one textually included body (mppi_mlp_body.h, which lists what a wrapper has in
+// scope).  The default-width family first: 512 x 3 and 512 x 2, NW waves on RT row tiles.
 template <bool VIZ, int NW, int RT, int TERMS = 3>
 __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3(const KParams<float> P, const MlpParams Q,
                                                                float *__restrict__ partials, const MlpViz V) {
-#include "mppi_mlp_h3_body.h"
+    constexpr int H = MLP_H, scene_agent = 0;
+    constexpr bool SCENE = false, ONE_HIDDEN = false;
+#include "mppi_mlp_body.h"
 }
 // several agents per launch, agent = blockIdx.y (grid (mlp_blocks(K, 64), n_agents)); no visualisation form.  `models`: every
 // agent's MlpParams (its own weight buffers or the shared ones; one shape for all, mppi_set_agent_mlp): `Q` is this
@@ -815,18 +801,19 @@ template <int NW, int RT, int TERMS>
 __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3_agents(const KParams<float> P_all,
                                                                       const MlpParams *__restrict__ models,
                                                                       float *__restrict__ partials_all) {
-    constexpr bool VIZ = false;
+    constexpr int H = MLP_H, scene_agent = 0;
+    constexpr bool VIZ = false, SCENE = false, ONE_HIDDEN = false;
     const KParams<float> P = mlp_agent(P_all, (int)blockIdx.y);
     MlpParamsConst &Q = mlp_agent_model(models, (int)blockIdx.y);
     float *__restrict__ partials = mlp_agent_records(P_all, partials_all, (int)blockIdx.y);
     const MlpViz V{};
-#include "mppi_mlp_h3_body.h"
+#include "mppi_mlp_body.h"
 }
 
 // ------------------------------------------------------------------------------------------
-// Every other supported shape, H in {64, 128, 256, 512} x n_hidden in {1, 2, 3, 4}: the same f16-split
-// arithmetic and the same step loop as k_rollout_mlp_h3 (kept apart so that the 512 x 3 / 512 x 2 kernels compile to the code
-// they always did; a shared inlined body changed their register allocation), with H / 64 waves per workgroup, each owning 64 output columns of every layer (one pass of
+// Every other supported shape, H in {64, 128, 256, 512} x n_hidden in {1, 2, 3, 4}: the same body (kept as
+// kernels of their own so that the 512 x 3 / 512 x 2 kernels compile to the code they always did), with H / 64 waves per
+// workgroup, each owning 64 output columns of every layer (one pass of
 // two 32-column tiles, as the 8-wave form of the 512-wide kernel), on a 64-sample tile: blockDim = H.  The LDS of a tile
 // shrinks with H (38 KB at 64, 56 KB at 128, 79 KB at 256), so two (H = 256, 128) or four (H = 64) workgroups share a CU
 // and one's serial part -- wave 0's controls, waypoint search, cost and Euler step -- runs under another's matrix work.
@@ -834,78 +821,68 @@ __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3_age
 template <int H, bool VIZ>
 __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w(const KParams<float> P, const MlpParams Q, float *__restrict__ partials,
                                                                      const MlpViz V) {
-#include "mppi_mlp_w_body.h"
+    constexpr int NW = H / 64, RT = 2, TERMS = 3, scene_agent = 0;
+    constexpr bool SCENE = false, ONE_HIDDEN = true;
+#include "mppi_mlp_body.h"
 }
 // several agents per launch (see k_rollout_mlp_h3_agents)
 template <int H>
 __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_agents(const KParams<float> P_all,
                                                                             const MlpParams *__restrict__ models,
                                                                             float *__restrict__ partials_all) {
-    constexpr bool VIZ = false;
+    constexpr int NW = H / 64, RT = 2, TERMS = 3, scene_agent = 0;
+    constexpr bool VIZ = false, SCENE = false, ONE_HIDDEN = true;
     const KParams<float> P = mlp_agent(P_all, (int)blockIdx.y);
     MlpParamsConst &Q = mlp_agent_model(models, (int)blockIdx.y);
     float *__restrict__ partials = mlp_agent_records(P_all, partials_all, (int)blockIdx.y);
     const MlpViz V{};
-#include "mppi_mlp_w_body.h"
+#include "mppi_mlp_body.h"
 }
 
 // ------------------------------------------------------------------------------------------
-// The scene forms (mppi_config.obstacle_motion = 2): the same bodies with the moving table, the agent's scene
-// (MlpScene) and mlp_advance_scene behind the two hooks -- moving circles, obstacle tracks and a cost grid priced along every
+// The scene forms (mppi_config.obstacle_motion = 2): the same body with SCENE = true -- the moving table and the
+// agent's MlpScene in `obs`, mlp_advance<true> -- so moving circles, obstacle tracks and a cost grid are priced along every
 // learned rollout.  One form per width of k_rollout_mlp_w and one of the default 8-wave three-term k_rollout_mlp_h3, each
 // single-agent and batched: ten symbols.  No visualisation form (the transition is the static kernels').  `scene_agent`: whose
-// descriptors the body's MLP_BODY_OBS_LOAD reads.
+// descriptors mlp_scene_at reads.
 // ------------------------------------------------------------------------------------------
-#undef MLP_BODY_OBS_LOAD
-#undef MLP_BODY_ADVANCE
-#define MLP_BODY_OBS_LOAD                                                      \
-    const ObsLanesMoving<float> obs = load_obstacles_moving(P, lane);          \
-    const MlpScene SC = mlp_scene_load(P, sv, scene_agent);
-#define MLP_BODY_ADVANCE mlp_advance_scene(PL, obs, SC, c, t, r0, r1, r2, u0, u1, v0, v1, L);
-// agent a's view for a scene form: mlp_agent's, and the clock its own circles were uploaded at (AgentScene::iter0)
-__device__ __forceinline__ KParams<float> mlp_agent_scene(const KParams<float> &P, int a) {
-    KParams<float> A = mlp_agent(P, a);
-    A.iter0 = P.scenes[a].iter0;
-    return A;
-}
 __global__ __launch_bounds__(64 * 8, 1) void k_rollout_mlp_h3_scene(const KParams<float> P, const MlpParams Q, float *__restrict__ partials) {
-    constexpr bool VIZ = false;
-    constexpr int NW = 8, RT = 2, TERMS = 3, scene_agent = 0;
+    constexpr int H = MLP_H, NW = 8, RT = 2, TERMS = 3, scene_agent = 0;
+    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = false;
     const MlpViz V{};
-#include "mppi_mlp_h3_body.h"
+#include "mppi_mlp_body.h"
 }
 __global__ __launch_bounds__(64 * 8, 1) void k_rollout_mlp_h3_scene_agents(const KParams<float> P_all, const MlpParams *__restrict__ models,
                                                                           float *__restrict__ partials_all) {
-    constexpr bool VIZ = false;
-    constexpr int NW = 8, RT = 2, TERMS = 3;
+    constexpr int H = MLP_H, NW = 8, RT = 2, TERMS = 3;
+    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = false;
     const int scene_agent = (int)blockIdx.y;
-    const KParams<float> P = mlp_agent_scene(P_all, scene_agent);
+    const KParams<float> P = mlp_agent(P_all, scene_agent);
     MlpParamsConst &Q = mlp_agent_model(models, scene_agent);
     float *__restrict__ partials = mlp_agent_records(P_all, partials_all, scene_agent);
     const MlpViz V{};
-#include "mppi_mlp_h3_body.h"
+#include "mppi_mlp_body.h"
 }
 template <int H>
 __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_scene(const KParams<float> P, const MlpParams Q, float *__restrict__ partials) {
-    constexpr bool VIZ = false;
-    constexpr int scene_agent = 0;
+    constexpr int NW = H / 64, RT = 2, TERMS = 3, scene_agent = 0;
+    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = true;
     const MlpViz V{};
-#include "mppi_mlp_w_body.h"
+#include "mppi_mlp_body.h"
 }
 template <int H>
 __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_scene_agents(const KParams<float> P_all,
                                                                                   const MlpParams *__restrict__ models,
                                                                                   float *__restrict__ partials_all) {
-    constexpr bool VIZ = false;
+    constexpr int NW = H / 64, RT = 2, TERMS = 3;
+    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = true;
     const int scene_agent = (int)blockIdx.y;
-    const KParams<float> P = mlp_agent_scene(P_all, scene_agent);
+    const KParams<float> P = mlp_agent(P_all, scene_agent);
     MlpParamsConst &Q = mlp_agent_model(models, scene_agent);
     float *__restrict__ partials = mlp_agent_records(P_all, partials_all, scene_agent);
     const MlpViz V{};
-#include "mppi_mlp_w_body.h"
+#include "mppi_mlp_body.h"
 }
-#undef MLP_BODY_OBS_LOAD
-#undef MLP_BODY_ADVANCE
 #undef PH
 #ifdef MPPI_STAMPS
 extern "C" int mppi_debug_mlp_phases(unsigned long long *out) {
@@ -928,93 +905,76 @@ static size_t h3_shmem(int nw, int rt, int h = MLP_H) {
     return sizeof(_Float16) * 2 * (m * (h + 8) + m * H3_ZPITCH) + sizeof(float) * (nw + 1) * m * 4 +
            sizeof(float) * 4 * h3_ref_cap(rt, h);
 }
-// k_rollout_mlp_w<H, VIZ>: H / 64 waves, 64-sample tiles
-static size_t w_shmem(int h) { return h3_shmem(h / 64, 2, h); }
 static_assert(2 * (sizeof(_Float16) * 2 * (64 * (256 + 8) + 64 * H3_ZPITCH) + sizeof(float) * 5 * 64 * 4 + sizeof(float) * 4 * W256_REF_LDS)
                   <= 160 * 1024, "two H = 256 workgroups per CU");
-static bool mlp_is_w(const MlpParams &Q) { return !mlp_shape_is_h3(Q.hidden, Q.n_hidden); }
 
-// Plan entries: the one place per kernel where template arguments turn into the function to launch, its name as rocprofv3
-// prints it, its workgroup and its dynamic LDS (beyond 64 KB: launch_plan raises the attribute before the first launch on
-// a device).
-static KernelLaunch f32_entry() {
-    static KernelEntry e("k_rollout_mlp(");  // (up to the parenthesis: the other kernels' names begin with this one's)
-    const size_t ref_lds = sizeof(float) * 4 * MLP_REF_LDS_MAX;  // the path (mlp_stage_path)
-    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp), e, 64 * MLP_WAVES,
-                      sizeof(float) * (MLP_M * MLP_PITCH + MLP_M * 8 + MLP_WAVES * MLP_M * 4) + ref_lds);
+// Plan rows: the one place per kernel where template arguments meet the function to launch, its name as rocprofv3 prints it,
+// its workgroup and its dynamic LDS (beyond 64 KB: launch_plan raises the attribute before the first launch on a device; the
+// `lds_raised` flags live in the row's KernelEntry).  Three tables; their rows stand in the order the kernels have always been
+// instantiated in, which is the order of the functions in the code object.
+struct MlpKernel {
+    const void *fn;
+    KernelEntry e;
+    int threads;
+    size_t lds;
+    KernelLaunch plan() { return plan_entry(fn, e, threads, lds); }
+};
+template <typename F> static const void *kfn(F *f) { return reinterpret_cast<const void *>(f); }
+// k_rollout_mlp_w<H, VIZ> and its forms: H / 64 waves, 64-sample tiles
+static size_t w_shmem(int h) { return h3_shmem(h / 64, 2, h); }
+struct WSceneKernels { MlpKernel agents, one; };  // the scene handles' (obstacle_motion = 2)
+template <int H> static WSceneKernels w_scene_rows() {
+    return {{kfn(k_rollout_mlp_w_scene_agents<H>), KernelEntry("k_rollout_mlp_w_scene_agents<%d>", H), H, w_shmem(H)},
+            {kfn(k_rollout_mlp_w_scene<H>), KernelEntry("k_rollout_mlp_w_scene<%d>", H), H, w_shmem(H)}};
 }
-template <bool VIZ, int NW, int RT, int TERMS = 3> static KernelLaunch h3_entry() {
-    static KernelEntry e("k_rollout_mlp_h3<%s, %d, %d, %d>", KernelEntry::of(VIZ), NW, RT, TERMS);
-    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_h3<VIZ, NW, RT, TERMS>), e, 64 * NW, h3_shmem(NW, RT));
+struct WKernels { MlpKernel viz, agents, one; };
+template <int H> static WKernels w_rows() {
+    return {{kfn(k_rollout_mlp_w<H, true>), KernelEntry("k_rollout_mlp_w<%d, true>", H), H, w_shmem(H)},
+            {kfn(k_rollout_mlp_w_agents<H>), KernelEntry("k_rollout_mlp_w_agents<%d>", H), H, w_shmem(H)},
+            {kfn(k_rollout_mlp_w<H, false>), KernelEntry("k_rollout_mlp_w<%d, false>", H), H, w_shmem(H)}};
 }
-template <int NW, int RT, int TERMS> static KernelLaunch h3_agents_entry() {
-    static KernelEntry e("k_rollout_mlp_h3_agents<%d, %d, %d>", NW, RT, TERMS);
-    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_h3_agents<NW, RT, TERMS>), e, 64 * NW, h3_shmem(NW, RT));
-}
-template <int H, bool VIZ> static KernelLaunch w_entry() {
-    static KernelEntry e("k_rollout_mlp_w<%d, %s>", H, KernelEntry::of(VIZ));
-    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w<H, VIZ>), e, H, w_shmem(H));
-}
-template <int H> static KernelLaunch w_agents_entry() {
-    static KernelEntry e("k_rollout_mlp_w_agents<%d>", H);
-    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w_agents<H>), e, H, w_shmem(H));
-}
-// the scene forms (obstacle_motion = 2): the static forms' workgroups and LDS
-static KernelLaunch h3_scene_entry() {
-    static KernelEntry e("k_rollout_mlp_h3_scene");
-    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_h3_scene), e, 64 * 8, h3_shmem(8, 2));
-}
-static KernelLaunch h3_scene_agents_entry() {
-    static KernelEntry e("k_rollout_mlp_h3_scene_agents");
-    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_h3_scene_agents), e, 64 * 8, h3_shmem(8, 2));
-}
-template <int H> static KernelLaunch w_scene_entry() {
-    static KernelEntry e("k_rollout_mlp_w_scene<%d>", H);
-    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w_scene<H>), e, H, w_shmem(H));
-}
-template <int H> static KernelLaunch w_scene_agents_entry() {
-    static KernelEntry e("k_rollout_mlp_w_scene_agents<%d>", H);
-    return plan_entry(reinterpret_cast<const void *>(k_rollout_mlp_w_scene_agents<H>), e, H, w_shmem(H));
-}
-template <int H> static KernelLaunch w_scene_plan(bool agents) { return agents ? w_scene_agents_entry<H>() : w_scene_entry<H>(); }
-template <int H> static KernelLaunch w_plan(bool viz, bool agents) {
-    return viz ? w_entry<H, true>() : agents ? w_agents_entry<H>() : w_entry<H, false>();
-}
+// by width: 64, 128, 256, 512 (a further width is one more entry of each, and of plan_mlp's index)
+static WSceneKernels w_scene_kernels[] = {w_scene_rows<64>(), w_scene_rows<128>(), w_scene_rows<256>(), w_scene_rows<512>()};
+static WKernels w_kernels[] = {w_rows<64>(), w_rows<128>(), w_rows<256>(), w_rows<512>()};
+// 512 x 3 and 512 x 2: the forms of k_rollout_mlp_h3, and the f32-input kernel
+enum { H3_VIZ_8, H3_VIZ_4, H3_AGENTS, H3_F32, H3_8_TERMS_2, H3_8, H3_4, H3_SCENE, H3_SCENE_AGENTS };
+static MlpKernel h3_kernels[] = {
+    {kfn(k_rollout_mlp_h3<true, 8, 2, 3>), KernelEntry("k_rollout_mlp_h3<true, 8, 2, 3>"), 64 * 8, h3_shmem(8, 2)},
+    {kfn(k_rollout_mlp_h3<true, 4, 2, 3>), KernelEntry("k_rollout_mlp_h3<true, 4, 2, 3>"), 64 * 4, h3_shmem(4, 2)},
+    {kfn(k_rollout_mlp_h3_agents<8, 2, 3>), KernelEntry("k_rollout_mlp_h3_agents<8, 2, 3>"), 64 * 8, h3_shmem(8, 2)},
+    // (the name up to the parenthesis: the other kernels' names begin with this one's)
+    {kfn(k_rollout_mlp), KernelEntry("k_rollout_mlp("), 64 * MLP_WAVES,
+     sizeof(float) * (MLP_M * MLP_PITCH + MLP_M * 8 + MLP_WAVES * MLP_M * 4) + sizeof(float) * 4 * MLP_REF_LDS_MAX},
+    {kfn(k_rollout_mlp_h3<false, 8, 2, 2>), KernelEntry("k_rollout_mlp_h3<false, 8, 2, 2>"), 64 * 8, h3_shmem(8, 2)},
+    {kfn(k_rollout_mlp_h3<false, 8, 2, 3>), KernelEntry("k_rollout_mlp_h3<false, 8, 2, 3>"), 64 * 8, h3_shmem(8, 2)},
+    {kfn(k_rollout_mlp_h3<false, 4, 2, 3>), KernelEntry("k_rollout_mlp_h3<false, 4, 2, 3>"), 64 * 4, h3_shmem(4, 2)},
+    {kfn(k_rollout_mlp_h3_scene), KernelEntry("k_rollout_mlp_h3_scene"), 64 * 8, h3_shmem(8, 2)},
+    {kfn(k_rollout_mlp_h3_scene_agents), KernelEntry("k_rollout_mlp_h3_scene_agents"), 64 * 8, h3_shmem(8, 2)},
+};
 
 RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const MlpViz *viz) {
-    const int form = sw.mlp.form < 0 ? H3_FORM_DEFAULT : sw.mlp.form;
+    const bool f8 = (sw.mlp.form < 0 ? H3_FORM_DEFAULT : sw.mlp.form) == H3_FORM_8x64;
     const int agents = !viz && P.n_agents > 1 ? P.n_agents : 1;
-    RolloutPlan p;
     // a scene handle (obstacle_motion = 2: make_params marks its launches OBS_MOTION_SCENE) takes the scene form of its shape;
     // the visualisation rollouts and the batched transition price nothing and keep the static kernels
     const bool scene = !viz && P.obs_motion == OBS_MOTION_SCENE;
-    if (scene && mlp_is_w(Q)) {
-        switch (Q.hidden) {
-        case 64: p.k = w_scene_plan<64>(agents > 1); break;
-        case 128: p.k = w_scene_plan<128>(agents > 1); break;
-        case 256: p.k = w_scene_plan<256>(agents > 1); break;
-        case 512: p.k = w_scene_plan<512>(agents > 1); break;
-        }
-    } else if (scene) {  // (512 x 3 / 512 x 2: the default form always -- mppi_set_mlp refuses the f32-input cases on a scene handle)
-        p.k = agents > 1 ? h3_scene_agents_entry() : h3_scene_entry();
-    } else if (mlp_is_w(Q)) {  // (MPPI_MLP_FORM / MPPI_MLP_TERMS / MPPI_MLP_F32 concern the 512 x 3 and 512 x 2 shapes only)
-        switch (Q.hidden) {  // (mppi_set_mlp admits only these)
-        case 64: p.k = w_plan<64>(viz, agents > 1); break;
-        case 128: p.k = w_plan<128>(viz, agents > 1); break;
-        case 256: p.k = w_plan<256>(viz, agents > 1); break;
-        case 512: p.k = w_plan<512>(viz, agents > 1); break;
-        }
-    } else if (viz) {  // (the f16-split kernel, whichever rollout kernel MPPI_MLP_F32 selects: both weight sets are packed)
-        p.k = form == H3_FORM_8x64 ? h3_entry<true, 8, 2>() : h3_entry<true, 4, 2>();
-    } else if (agents > 1) {  // several agents: the default form always (mppi_set_mlp refuses the f32-input kernel)
-        p.k = h3_agents_entry<8, 2, 3>();
-    } else if (!Q.use_h3) {
-        p.k = f32_entry();
-    } else if (form == H3_FORM_8x64) {
-        p.k = sw.mlp.terms == 2 ? h3_entry<false, 8, 2, 2>() : h3_entry<false, 8, 2>();
-    } else {
-        p.k = h3_entry<false, 4, 2>();
-    }
+    // the one dispatch on width: 512 x 3 / 512 x 2 have their own family (mppi_set_mlp admits only these four widths)
+    const bool h3 = mlp_shape_is_h3(Q.hidden, Q.n_hidden);
+    const int wi = Q.hidden == 64 ? 0 : Q.hidden == 128 ? 1 : Q.hidden == 256 ? 2 : 3;
+    // MPPI_MLP_FORM / MPPI_MLP_TERMS / MPPI_MLP_F32 concern the single-agent rollouts of 512 x 3 / 512 x 2 only: scene handles
+    // and batches take the default form (mppi_set_mlp refuses the f32-input cases for both), the visualisation rollouts the
+    // f16-split kernel of the form whichever rollout kernel MPPI_MLP_F32 selects (both weight sets are packed)
+    const bool batch = agents > 1;
+    MlpKernel &k = scene && h3 ? h3_kernels[batch ? H3_SCENE_AGENTS : H3_SCENE]
+                   : scene     ? (batch ? w_scene_kernels[wi].agents : w_scene_kernels[wi].one)
+                   : !h3       ? (viz ? w_kernels[wi].viz : batch ? w_kernels[wi].agents : w_kernels[wi].one)
+                   : viz       ? h3_kernels[f8 ? H3_VIZ_8 : H3_VIZ_4]
+                   : batch     ? h3_kernels[H3_AGENTS]
+                   : !Q.use_h3 ? h3_kernels[H3_F32]
+                   : !f8       ? h3_kernels[H3_4]
+                               : h3_kernels[sw.mlp.terms == 2 ? H3_8_TERMS_2 : H3_8];
+    RolloutPlan p;
+    p.k = k.plan();
     p.records = mlp_blocks(P.K, MLP_M);  // every kernel: one 64-sample tile, one softmin record, per workgroup
     // viz: the samples' workgroups (when their trajectories are wanted) and one for the nominal sequence (likewise)
     if (viz) p.k.grid = dim3(viz->ex ? mlp_blocks(viz->en, MLP_M) : (viz->smp ? p.records : 0) + (viz->opt ? 1 : 0));

@@ -1,17 +1,19 @@
-// mppi_mlp_w_body.h: the body of k_rollout_mlp_w<H, VIZ> -- included textually by the
-// single-agent kernel and by its several-agents-per-launch form (mppi_mlp.hip), so that the single-agent kernel compiles to
-// exactly the code it did as a self-contained kernel (an inlined __device__ body is optimised before it is inlined and
-// changed the register allocation and scratch of every instantiation).  In scope: P, Q, partials, V and the template
-// parameters of the including kernel.  Not a header: no include guard, nothing else may include it.
-// Two hook points are the includer's (macros, mppi_mlp.hip): MLP_BODY_OBS_LOAD -- the statement that loads `obs` behind `sv` --
-// and MLP_BODY_ADVANCE -- the advance call of wave 0.  For the static kernels they expand to the tokens that stood here.
-    constexpr int NW = H / 64, RT = 2, TERMS = 3;
+// mppi_mlp_body.h: the one body of every f16-split rollout kernel -- k_rollout_mlp_h3, k_rollout_mlp_w, their several-agents-
+// per-launch forms and their scene forms (mppi_mlp.hip): eight wrappers include it textually, so that each kernel compiles to
+// exactly the code it did as a self-contained kernel (an inlined __device__ body is optimised before it is inlined and changed
+// the register allocation and scratch of 21 of the 29 kernels: DESIGN 3.6.3).  Not a header: no include guard, nothing else may
+// include it.  In scope at the point of inclusion:
+//   P, Q, partials, V   the kernel's (or this agent's) parameters, model, records and visualisation block
+//   H, NW, RT, TERMS    the layers' width, waves per workgroup, row tiles of 32 samples, terms of the split product
+//   VIZ, SCENE          the visualisation form; the scene form (moving table and MlpScene in `obs`, mlp_advance<true>)
+//   scene_agent         whose descriptors a scene form prices (0 where SCENE is false)
+//   ONE_HIDDEN          constexpr bool: n_hidden == 1 is admitted (the _w family; the _h3 kernels run 2 or 3 hidden layers)
 #ifdef MPPI_STAMPS
     unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_t = clock64();
 #endif
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int M = 32 * RT;  // samples of this workgroup's tile
-    constexpr int PITCH = H + 8;                           // (H3_PITCH at 512)
+    constexpr int PITCH = H + 8;                           // (520 at 512)
     _Float16 *a_hi = reinterpret_cast<_Float16 *>(smem);   // [M][H + 8]
     _Float16 *a_lo = a_hi + M * PITCH;
     _Float16 *z_hi = a_lo + M * PITCH;                     // [M][24] layer-0 input rows {x, y, yaw, v, w, 0 ...}: one k-step
@@ -23,7 +25,7 @@
     const int k0 = ((int)blockIdx.x + (VIZ ? V.block0 : 0)) * M, k = k0 + lane;
     const KParams<float> PL = mlp_stage_path(P, ref_lds, h3_ref_cap(RT, H));
     const DevState sv = load_state(P, P.st);
-    MLP_BODY_OBS_LOAD  // (hook: the obstacle table, and whatever the includer's advance call reads beside it)
+    const MlpObs<SCENE> obs = mlp_obs_load<SCENE>(P, sv, lane, scene_agent);  // what wave 0's advance call prices against
     if (!VIZ && k0 + M <= sv.k_start) return;
     const bool in_tile = lane < M;  // (a 32-sample tile: the upper half of wave 0 carries no sample)
     const bool valid = in_tile && k < P.K, live = valid && k >= sv.k_start;
@@ -83,7 +85,7 @@
             gemm_layer_h3<NW, RT, TERMS, H>(acc, a_hi, a_lo, Q.h3_w_h[l_last], wid, lane, ring);
             PH(4);
             float yo[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-            if (l_last == 0)  // one hidden layer: it is also the first, its accumulators those of h0 / s1
+            if (ONE_HIDDEN && l_last == 0)  // one hidden layer: it is also the first, its accumulators those of h0 / s1
                 store_layer_h3<NW, RT, true, true, 2, H>(a_hi, a_lo, acc, Q.b_h[0], wid, lane, Q.w_out, yo, zscale);
             else store_layer_h3<NW, RT, true, true, 0, H>(a_hi, a_lo, acc, Q.b_h[l_last], wid, lane, Q.w_out, yo);
 #pragma unroll
@@ -112,7 +114,7 @@
                              : opt_row ? V.opt + (size_t)t * 3 : smp_row ? V.smp + ((size_t)k * P.T + t) * 3 : nullptr;
                 if (dst) { dst[0] = L.x; dst[1] = L.y; dst[2] = L.yaw; }
             } else {
-                MLP_BODY_ADVANCE  // (hook: the includer's mlp_advance call)
+                mlp_advance<SCENE>(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
             }
         }
         PH(9);

@@ -366,6 +366,48 @@ def test_full_size_k32768_subset_new_shape():
     assert rmse(u, np.vstack([un[1:], un[-1:]])) <= 1e-4
 
 
+def plan_name(H, n, agents, scene):
+    """The kernel plan_mlp selects for a rollout: shape x one agent or a batch x a static or a scene handle."""
+    tail = ("_scene" if scene else "") + ("_agents" if agents > 1 else "")
+    if H == 512 and n in (2, 3):  # the default form of the 512 x 3 / 512 x 2 kernel
+        return f"k_rollout_mlp_h3{tail}" + ("" if scene else "<8, 2, 3>" if agents > 1 else "<false, 8, 2, 3>")
+    return f"k_rollout_mlp_w{tail}<{H}>" if tail else f"k_rollout_mlp_w<{H}, false>"
+
+
+PLAN_SHAPES = [(h, n) for h in (64, 128, 256, 512) for n in (1, 3)] + [(512, 2), (512, 4)]
+
+
+@pytest.mark.parametrize("H,n", PLAN_SHAPES)
+def test_plan_table(H, n):
+    """The host dispatch over shape x {one agent, two agents} x obstacle_motion {0, 2}: the exact kernel name, and that the
+    launch ran (finite controls and costs).  K = 65: one full 64-sample tile and a ragged one; T = 7; in-kernel Philox; an
+    empty scene.  Pinned elsewhere by an exact rollout_kernel() assertion: every static single-agent shape
+    (test_new_shapes_against_oracle, test_gpu_mlp_agents), the static batches of 512 x 3, 128 x 3, 64 x 1 and 256 x 2
+    (test_gpu_mlp_agents), the scene handles of 64 x 1, 128 x 2, 256 x 3 and 512 x 3 and the scene batches of 64 x 1 and 512 x 3
+    (test_gpu_mlp_scenes), MPPI_MLP_FORM / _TERMS / _F32 (test_gpu_engine).  New here, of this table's ten shapes: the static batches of
+    seven (all but 64 x 1, 128 x 3, 512 x 3), the scene handles and the scene batches of eight each (all but 64 x 1, 512 x 3)."""
+    import dnn_mppi_mpc_amd as pkg
+    from dnn_mppi_mpc_amd import _capi as capi
+    K, T = 65, 7
+    w = weights(H, n, 50 + H + n)
+    x0 = np.array([[0.4, -0.1, -0.35], [0.3, 0.1, -0.2]])
+    for motion in (0, 2):
+        for agents in (1, 2):
+            e = _mlp_engine(pkg, capi, K, w, T=T, filter_window=5, seed=3, obstacle_model=capi.OBSTACLE_CIRCLE,
+                            obstacle_motion=motion, n_agents=agents)
+            e.set_u_prev(u_nominal(T) if agents == 1 else np.stack([u_nominal(T)] * agents))
+            if agents == 1:
+                u = e.step(x0[0])[0]
+            else:
+                e.set_state(x0)
+                e.run_closed_loop(1)
+                u = e.get_u_prev()
+            assert e.rollout_kernel() == plan_name(H, n, agents, motion == 2), (motion, agents)
+            S = e.costs()
+            assert S.shape == ((K,) if agents == 1 else (agents, K)) and np.isfinite(S).all() and np.isfinite(u).all()
+            e.close()
+
+
 def test_dispatch_and_refusals():
     """rollout_kernel() names the kernel that serves the shape; shapes outside the set are refused naming the set, by the
     Python layer (ValueError) and by the C ABI (MPPI_ERR_SHAPE); a weight beyond the f16 range on a new shape is refused
