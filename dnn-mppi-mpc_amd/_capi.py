@@ -170,6 +170,8 @@ PROTOTYPES = {
     "mppi_cb_get_costs": (C.c_int, [_H, _D, _D]),
     "mppi_cb_eval": (C.c_int, [_H, C.c_int32, _D, _D, C.c_int32, C.c_int32, _D]),
     "mppi_cb_nominal_trajectory": (C.c_int, [_H, _D, _D]),
+    "mppi_cb_get_perturbed_actions": (C.c_int, [_H, C.c_void_p, _D]),
+    "mppi_cb_top_trajectories": (C.c_int, [_H, _D, C.c_void_p, C.c_int32, _D, C.POINTER(C.c_int32)]),
 }
 
 _lib = None

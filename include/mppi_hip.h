@@ -677,15 +677,28 @@ int mppi_get_rollout_kernel(const mppi_handle *h, char *buf, int32_t n);
 
 /*
  * `pytorch_mppi`-style MPPI with built-in dynamics / running-cost models: the callbacks the
- * reference's test/test_mppi.py, test/test_mppi_diff.py, test/test_mppi_diff_dyna.py and
- * train/bullet_mppi_differential_drive.py hand to `pytorch_mppi.MPPI`, as selectable device functions.  `mppi_cb_command`
+ * reference's test/test_mppi.py, test/test_mppi_diff.py, test/test_mppi_diff_dyna.py,
+ * train/bullet_mppi_differential_drive.py, test/test_mppi_racecar.py, test/test_torch_mppi_race_car.py and
+ * test/test_torch_mppi.py hand to `pytorch_mppi.MPPI`, as selectable device functions.  `mppi_cb_command`
  * is `MPPI.command(state)`: shift the nominal sequence, sample, roll out, weigh, update, return the first action.
  * The library itself is absent from the build container and un-pinned by the reference: the loop follows the
  * published algorithm and is PARITY UNPINNED (csrc/mppi_cb.hip, oracle/mppi_cb_oracle.py).  fp32 like the callers.
  */
 typedef enum {
     MPPI_CB_DYN_UNICYCLE = 0,   /* test/test_mppi.py:12-26: [x, y, theta], [v, omega] */
-    MPPI_CB_DYN_SKID_STEER = 1  /* test/test_mppi_diff_dyna.py:13-40: [x, y, theta, v, omega], 4 wheel forces */
+    MPPI_CB_DYN_SKID_STEER = 1, /* test/test_mppi_diff_dyna.py:13-40: [x, y, theta, v, omega], 4 wheel forces */
+    /* The three below step every component by Euler from the OLD state, in the order written, dt from the config.
+     * test/test_mppi_racecar.py:13-30, [x, y, theta, v], u = [steer delta, accel a], default dt 0.05:
+     *   x += v cos(theta) dt; y += v sin(theta) dt; theta += v / L * tan(delta) * dt; v += a dt;   model_params = {L = 0.3} */
+    MPPI_CB_DYN_RACECAR = 2,
+    /* test/test_torch_mppi_race_car.py:7-39, [x, y, theta, v], u = [acc, steer delta] -- the other order --, default dt 0.05:
+     *   alpha_f = atan2(v sin(delta) + l_f theta, v cos(delta)) - delta;  alpha_r = atan2(v sin(delta) - l_r theta, v cos(delta));
+     *   x, y as above; theta += (v / l_r) sin(delta) dt; v += (acc - (C_f alpha_f sin(delta) + C_r alpha_r) / m) dt;
+     * model_params = {l_r = 1.5, l_f = 1.0, m = 1000, C_f = 1000, C_r = 1000}.  The script puts the yaw theta where a yaw rate
+     * would be expected (:25-26); that is the caller's model and it is restated as it stands. */
+    MPPI_CB_DYN_RACECAR_DYNAMIC = 3,
+    /* test/test_torch_mppi.py:5-15, [p, v], u = [force], default dt 0.1: p += dt v; v += dt u (the script's A and B) */
+    MPPI_CB_DYN_DOUBLE_INTEGRATOR = 4
 } mppi_cb_dynamics;
 typedef enum {
     MPPI_CB_OBS_INVERSE = 0,     /* 1 / (d + 1e-6) inside the safety distance (test/test_mppi.py:40-50) */
@@ -693,7 +706,7 @@ typedef enum {
 } mppi_cb_obstacle_cost;
 typedef struct {
     int32_t struct_size, device;
-    int32_t dynamics;            /* mppi_cb_dynamics: fixes nx (3 / 5) and nu (2 / 4) */
+    int32_t dynamics;            /* mppi_cb_dynamics: fixes nx (3 / 5 / 4 / 4 / 2) and nu (2 / 4 / 2 / 2 / 1) */
     int32_t obstacle_kind;       /* mppi_cb_obstacle_cost */
     int32_t K, T;                /* num_samples, horizon (T * nu <= 256) */
     int32_t n_obs;               /* <= 16 */
@@ -706,6 +719,23 @@ typedef struct {
     double safety_distance, obstacle_weight;
     double skid_params[5];       /* m, I, r, L, damping (2.0, 0.05, 0.1, 0.4, 0.1 in the reference) */
     uint64_t seed;
+    /* --- grown at the end; struct_size tells a library that knows these fields from one that does not --- */
+    double model_params[8];      /* constants of the model chosen by `dynamics` (see the enum); a non-positive L, l_r or m:
+                                    MPPI_ERR_BAD_ARG */
+    /* `terminal_state_cost` (test/test_torch_mppi.py:23-25): terminal_cost != 0 adds (s_T - terminal_goal)^T diag(terminal_q)
+     * (s_T - terminal_goal), s_T the state after the last step, once per sample, to the sum of its running costs before the
+     * perturbation term; 0 leaves the rollout as it was. */
+    int32_t terminal_cost;
+    /* `noise_abs_cost`: the perturbation term is lambda sum_t sum_i U[t,i] sum_j |noise[t,j]| Sigma^-1[j,i], the absolute
+     * value taken of the noise after clamping; the update keeps the signed noise. */
+    int32_t noise_abs_cost;
+    double terminal_goal[5], terminal_q[5];
+    double noise_mu[4];          /* `noise_mu`: the in-kernel draw is mu + L z; an injected eps stands for the whole draw */
+    /* `u_scale`, finite and not 0 (else MPPI_ERR_BAD_ARG; 1 is the neutral value): dynamics and running cost see u_scale * the
+     * clamped perturbed action; bounds, perturbation term, update and returned action are in unscaled units;
+     * mppi_cb_nominal_trajectory and mppi_cb_top_trajectories apply it, as the callers' `self.u_scale * self.U[t]` does
+     * (test/test_mppi_racecar.py:73, :83). */
+    double u_scale;
 } mppi_cb_config;
 typedef struct mppi_cb_handle mppi_cb_handle;
 const char *mppi_cb_last_error(const mppi_cb_handle *h);
@@ -719,11 +749,25 @@ int mppi_cb_command(mppi_cb_handle *h, const double *state, const float *eps, in
                     double *action_out, void *stream);
 /* `cost_total` [K] and the weights `omega` [K] of the last command (either nullable) */
 int mppi_cb_get_costs(mppi_cb_handle *h, double *cost_total, double *omega);
-/* the callbacks themselves, batched: what = 0 `dynamics(states, actions, t)` -> [n, nx]; 1 `running_cost` -> [n] */
+/* the callbacks themselves, batched: what = 0 `dynamics(states, actions, t)` -> [n, nx]; 1 `running_cost` -> [n];
+ * 2 `terminal_state_cost(states)` -> [n] (actions ignored and may be NULL; a handle without one: MPPI_ERR_STATE) */
 int mppi_cb_eval(mppi_cb_handle *h, int32_t what, const double *states, const double *actions, int32_t t, int32_t n,
                  double *out);
 /* the trajectory U drives from `state`: [T, nx] (the optimal trajectory of the callers' get_trajectories) */
 int mppi_cb_nominal_trajectory(mppi_cb_handle *h, const double *state, double *traj);
+/* The handle keeps the nominal sequence the last command's samples were drawn around (after the shift, before the update) and
+ * that command's iteration number, so the two calls below make its draw again: from Philox (eps NULL), or from the injected
+ * tensor handed in again (eps, device float [K, T, nu]).  Before the first command, or with eps where the last command drew
+ * in the kernel and the other way round: MPPI_ERR_STATE.
+ * `perturbed_action` (test/test_mppi_racecar.py:83): the clamped, unscaled actions of the last command, host [K][T][nu]. */
+int mppi_cb_get_perturbed_actions(mppi_cb_handle *h, const float *eps, double *out);
+/* The callers' sampled fan (test/test_mppi_racecar.py:76-84, test/test_mppi.py:60-80): the trajectories from `state` of the n
+ * samples with the lowest `cost_total` of the last command, in ascending order -- host traj_out [n][T][nx] -- and their
+ * sample indices, host index_out [n].  The rank of sample k is the number of samples j with c_j < c_k, or c_j == c_k and
+ * j < k; a NaN cost counts as larger than every number and NaNs are ordered among themselves by index, so the ranks are a
+ * permutation of 0 .. K - 1 whatever the costs hold (a stable ascending argsort).  n outside [1, K]: MPPI_ERR_SHAPE. */
+int mppi_cb_top_trajectories(mppi_cb_handle *h, const double *state, const float *eps, int32_t n, double *traj_out,
+                             int32_t *index_out);
 
 #ifdef __cplusplus
 }
