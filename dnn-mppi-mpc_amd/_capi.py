@@ -28,6 +28,7 @@ FLEET_VELOCITY, FLEET_PLAN = 0, 1  # mppi_set_fleet_prediction
 SCENE_EXCLUSIVE, SCENE_COMPOSED = 0, 1  # mppi_set_scene_mode
 GRID_FOOTPRINT_CENTRE, GRID_FOOTPRINT_OUTLINE = 0, 1  # mppi_set_cost_grid_footprint
 OBSTACLE_MOTION_LEARNED = 2  # mppi_config.obstacle_motion: the learned model's scene handle (MODEL_DIFFDRIVE_MLP only)
+OBSTACLE_MOTION_LEARNED_FLEET = 3  # the learned model's fleet handle: a scene handle with fleet_radius > 0 (likewise)
 LAYOUT_FUSED, LAYOUT_DUAL, LAYOUT_PAIR, LAYOUT_TRI, LAYOUT_KIND, LAYOUT_TWICE = 0, 1, 2, 3, 3, 4  # mppi_get_rollout_layout (KIND: mask)
 
 

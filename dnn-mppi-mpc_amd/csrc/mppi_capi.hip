@@ -283,7 +283,10 @@ static bool scene_composed(const mppi_handle *h) { return h->scene_mode == MPPI_
 static int scene_ingredients(const mppi_handle *h) { return (h->fleet_plan ? 1 : 0) + (max_tracks(h) > 0 ? 1 : 0) + (h->any_grid ? 1 : 0); }
 static bool scene_form(const mppi_handle *h) { return scene_composed(h) && scene_ingredients(h) >= 2; }
 // the learned model's scene handle (mppi_config.obstacle_motion = 2): every launch carries the SceneTable (set_scene_learned)
-static bool learned_scene(const mppi_handle *h) { return h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP && h->cfg.obstacle_motion == 2; }
+static bool learned_scene(const mppi_handle *h) { return h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP && h->cfg.obstacle_motion >= 2; }
+// its fleet handle (obstacle_motion = 3, MPPI_OBSTACLE_MOTION_LEARNED_FLEET): a scene handle whose agents see each other -- the
+// fleet forms of the batched scene kernels, and in plan mode the plans rolled out through every agent's own model
+static bool learned_fleet(const mppi_handle *h) { return h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP && h->cfg.obstacle_motion == 3; }
 // the create-time value a handle of this model needs for a scene, as the setters' refusals name it
 static int motion_value(const mppi_handle *h) { return h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP ? 2 : 1; }
 // some agent has obstacles: the obstacle instantiations serve and the records carry collision counts
@@ -363,22 +366,34 @@ extern "C" int mppi_create(const mppi_config *cfg, mppi_handle **out) {
              "MPPI_WAYPOINT_PER_ROLLOUT restates the diff-drive files' index bookkeeping (mppi_differential_drive.py:228,:244); "
              "the race-car files search from the x0 call's index (MPPI_WAYPOINT_FROZEN)");
     // (2, MPPI_OBSTACLE_MOTION_LEARNED: the learned model's scene handle -- inside the library it is value 1 everywhere)
-    const bool scene_handle = c.obstacle_motion == 2 && c.model == MPPI_MODEL_DIFFDRIVE_MLP;
+    // (3, MPPI_OBSTACLE_MOTION_LEARNED_FLEET: a scene handle whose agents see each other -- likewise)
+    const bool fleet_handle = c.obstacle_motion == 3 && c.model == MPPI_MODEL_DIFFDRIVE_MLP;
+    const bool scene_handle = (c.obstacle_motion == 2 && c.model == MPPI_MODEL_DIFFDRIVE_MLP) || fleet_handle;
     if (c.obstacle_motion != 0 && c.obstacle_motion != 1 && !scene_handle)
         CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: obstacle_motion %d is neither 0 (static) nor 1 (constant velocity)%s", c.obstacle_motion,
-                    c.obstacle_motion == 2 ? "; 2 (the learned model's scene handle) goes with MPPI_MODEL_DIFFDRIVE_MLP only" : "");
+                    c.obstacle_motion == 2   ? "; 2 (the learned model's scene handle) goes with MPPI_MODEL_DIFFDRIVE_MLP only"
+                    : c.obstacle_motion == 3 ? "; 3 (the learned model's fleet handle) goes with MPPI_MODEL_DIFFDRIVE_MLP only (limit: an "
+                                               "analytic fleet is obstacle_motion = 1 with fleet_radius > 0)"
+                                             : "");
+    if (fleet_handle && !(c.fleet_radius > 0) && std::isfinite(c.fleet_radius))
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: obstacle_motion = 3 (the learned model's fleet handle) needs fleet_radius > 0, got %g "
+                                      "(limit: without a fleet the scene handle is obstacle_motion = 2)", c.fleet_radius);
+    if (fleet_handle && c.n_agents < 2)
+        CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: obstacle_motion = 3 (the learned model's fleet handle) needs n_agents >= 2 (an agent's "
+                                      "mates are the other agents of its handle), got %d", c.n_agents);
     if (c.obstacle_motion && c.obstacle_model == MPPI_OBSTACLE_NONE)
         CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: obstacle_motion = %d needs an obstacle model (MPPI_OBSTACLE_CIRCLE or _OUTLINE), got MPPI_OBSTACLE_NONE", c.obstacle_motion);
     if (c.obstacle_motion == 1 && c.model == MPPI_MODEL_DIFFDRIVE_MLP)
         CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "moving obstacles (obstacle_motion = 1) are served by the analytic models only: the "
                                           "learned-dynamics rollout (MPPI_MODEL_DIFFDRIVE_MLP) tests static circles; its scene "
                                           "handle is obstacle_motion = 2 (moving circles, obstacle tracks and cost grids)");
-    if (scene_handle && c.fleet_radius > 0)
-        CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "fleet avoidance (fleet_radius = %g) is served by the analytic models only: the mates' plans are "
-                                          "rolled out with analytic dynamics (limit: fleet_radius = 0 with MPPI_MODEL_DIFFDRIVE_MLP)", c.fleet_radius);
+    if (scene_handle && !fleet_handle && c.fleet_radius > 0)
+        CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "fleet avoidance (fleet_radius = %g) on an obstacle_motion = 2 handle is served by the analytic "
+                                          "models only: the mates' plans are rolled out with analytic dynamics (limit: fleet_radius = 0 "
+                                          "with obstacle_motion = 2; a learned-dynamics fleet is obstacle_motion = 3)", c.fleet_radius);
     if (scene_handle && c.K_global != c.K)
-        CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "a learned-dynamics scene handle (obstacle_motion = 2) is not sharded (limit: K_global = K, "
-                                          "got K = %d, K_global = %d)", c.K, c.K_global);
+        CREATE_FAIL(MPPI_ERR_UNSUPPORTED, "a learned-dynamics scene handle (obstacle_motion = %d) is not sharded (limit: K_global = K, "
+                                          "got K = %d, K_global = %d)", c.obstacle_motion, c.K, c.K_global);
     if (!(c.fleet_radius >= 0) || !std::isfinite(c.fleet_radius))
         CREATE_FAIL(MPPI_ERR_BAD_ARG, "mppi_create: fleet_radius %g is not a finite radius >= 0 (0: fleet avoidance off)", c.fleet_radius);
     if (c.fleet_radius > 0 && c.n_agents < 2)
@@ -1202,7 +1217,7 @@ static int set_model(mppi_handle *h, const char *who, int agent, const HostMlp &
         h->err = b;
     }
     // the rollout kernel that serves this model: its name before the first launch already
-    h->rollout_kernel = plan_mlp(make_params<float>(h, nullptr), has_model(h, 0) ? h->mlp : m.q, h->sw).k.name;
+    h->rollout_kernel = plan_mlp(make_params<float>(h, nullptr), has_model(h, 0) ? h->mlp : m.q, h->sw, nullptr, learned_fleet(h)).k.name;
     return MPPI_OK;
 }
 
@@ -1430,7 +1445,7 @@ template <typename R> static KParams<R> make_params(const mppi_handle *h, const 
     P.chol[2] = (float)l11;
     P.ref = (const R *)sc0.ref;
     P.obs = (const R *)sc0.obs;
-    P.obs_motion = c.obstacle_motion ? 1 : 0;  // (2, the learned scene handle, is 1 in here; the carriers below overwrite it)
+    P.obs_motion = c.obstacle_motion ? 1 : 0;  // (2 and 3, the learned scene and fleet handles, are 1 in here; the carriers below overwrite it)
     P.iter0 = sc0.iter0;
     P.scenes = h->d_scenes;
     P.u = (const R *)h->d_u.get();
@@ -1497,6 +1512,19 @@ static FleetParams make_fleet(const mppi_handle *h, int count) {
         F.wheel_base = c.wheel_base;
     }
     return F;
+}
+
+// The launch at the front of a fleet handle's slot, or the refresh in front of a getter or an mppi_eval_* call: the mates' rows
+// (k_fleet_rows) or their plans -- k_fleet_plan with the analytic dynamics, and on a learned fleet handle (obstacle_motion = 3)
+// the plan kernels of mppi_mlp.hip, every agent's nominal controls through its own model.  P: the parameters of the rollout
+// behind it (the learned plan kernels read the agents' states, controls and clamp from them).
+template <typename R> static void launch_fleet_front(const mppi_handle *h, const KParams<R> &P, int count, hipStream_t s) {
+    if constexpr (sizeof(R) == 4)
+        if (learned_fleet(h) && h->fleet_plan) {
+            launch_fleet_plan_mlp(P, h->mlp, h->d_models, make_fleet(h, count), s);
+            return;
+        }
+    launch_fleet_rows<R>(make_fleet(h, count), s);
 }
 
 // the softmin rate as the records carry it
@@ -1580,7 +1608,7 @@ static void wire_exchange(const mppi_handle *h, FinalizeParams &F) {
 // the rollout launch of this handle (the learned model: f32 handles only, mppi_create refuses the rest)
 template <typename R> static RolloutPlan front_plan(const mppi_handle *h, const KParams<R> &P) {
     if constexpr (sizeof(R) == 4)
-        if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) return plan_mlp(P, h->mlp, h->sw);
+        if (h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP) return plan_mlp(P, h->mlp, h->sw, nullptr, learned_fleet(h));
     return plan_rollout<R>(P, h->fused, h->sw, h->grid_footprint == MPPI_GRID_FOOTPRINT_OUTLINE);
 }
 
@@ -1629,7 +1657,7 @@ static SlotPlan plan_slot(const mppi_handle *h, const KParams<R> &P, FinalizePar
 // rollout's event pair (mppi_last_kernel_ms out[0]) and outside the launch counters (mppi_get_counters)
 template <typename R> static void launch_records(mppi_handle *h, const SlotPlan &sp, const KParams<R> &P, hipStream_t s, bool tm) {
     if (tm) hipEventRecord(next_event(h), s);
-    if (h->fleet) launch_fleet_rows<R>(make_fleet(h, 1), s);
+    if (h->fleet) launch_fleet_front<R>(h, P, 1, s);
     h->n_rollout_launches += h->rollout_repeats;
     for (int rep = 0; rep < h->rollout_repeats; ++rep) {
         if constexpr (sizeof(R) == 4)
@@ -2637,7 +2665,7 @@ static int eval_impl(mppi_handle *h, int what, const double *x, const double *v,
         if (what == EVAL_TRANSITION && h->cfg.model == MPPI_MODEL_DIFFDRIVE_MLP)  // x + dt (f + MLP([x, v])), fp32 handles only
             eval_transition_mlp(h, P, dx, dv, n, dout);
         else if (at) {
-            if (h->fleet) launch_fleet_rows<R>(make_fleet(h, 0), nullptr);  // agent 0's mates as of the current states
+            if (h->fleet) launch_fleet_front<R>(h, P, 0, nullptr);  // agent 0's mates as of the current states
             launch_eval_pose<R>(P, eval_form(h, P.obs_motion), what, 0, dx, di, ds, n, dout, nullptr, nullptr);
         }
         else
@@ -2807,9 +2835,11 @@ extern "C" int mppi_get_fleet_plans(mppi_handle *h, double *xy) {
     if (!xy) FAIL(h, MPPI_ERR_BAD_ARG, "mppi_get_fleet_plans: xy is null");
     if (!h->fleet_plan)
         FAIL(h, MPPI_ERR_STATE, "mppi_get_fleet_plans: the handle predicts its mates at constant velocity (mppi_set_fleet_prediction: MPPI_FLEET_PLAN)");
+    if (learned_fleet(h))  // (the plans run through the agents' models)
+        if (int rc = check_ready(h, "mppi_get_fleet_plans")) return rc;
     HIPCHECK(h, hipSetDevice(h->cfg.device));
     HIPCHECK(h, hipDeviceSynchronize());
-    with_real(h, [&](auto r) { launch_fleet_rows<decltype(r)>(make_fleet(h, 0), nullptr); return 0; });
+    with_real(h, [&](auto r) { launch_fleet_front<decltype(r)>(h, make_params<decltype(r)>(h, nullptr), 0, nullptr); return 0; });
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipDeviceSynchronize());
     return download_real(h, xy, h->d_plans, 2 * (size_t)(h->cfg.T + 1) * (size_t)h->B);

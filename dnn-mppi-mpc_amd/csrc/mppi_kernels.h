@@ -303,7 +303,8 @@ template <typename R> inline void set_scene(KParams<R> &P, const void *table, in
     P.obs_motion = OBS_MOTION_SCENE;
 }
 // Learned-dynamics scene handles (mppi_config.obstacle_motion = 2; mppi_mlp.hip) use this carrier for EVERY launch,
-// whatever the handle holds: moving circles alone, tracks, a grid or both.  `plans` stays null (no fleets on learned handles)
+// whatever the handle holds: moving circles alone, tracks, a grid or both.  `plans` stays null except on a fleet handle
+// (obstacle_motion = 3) in plan mode, whose fleet forms read the table and `thr2` from here (mlp_mates_collided),
 // and nothing is staged in LDS -- at a step of the learned rollout every lane reads the same track point --, so pad_scenes[1],
 // the staged byte counts of the analytic composed launch, is free there: it carries the footprint word (MPPI_GRID_FOOTPRINT_*),
 // which the learned scene forms read at run time where the analytic forms take a template argument.  No pinned layout moves:
@@ -572,7 +573,10 @@ int reduce_blocks(int K, int traj_per_block);
 // config 5: rollout through the residual MLP on MFMA, one record per 64-sample tile.  plan_mlp covers the three forms of
 // that launch: the rollout (viz null; `records` per agent), the visualisation rollouts and the batched transition
 struct MlpViz;
-RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const MlpViz *viz = nullptr);
+// fleet: the handle is a learned fleet handle (mppi_config.obstacle_motion = 3): its rollout takes the fleet forms
+RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const MlpViz *viz = nullptr, bool fleet = false);
+// a learned fleet handle in plan mode: every agent's plan through its own model (k_fleet_plan_mlp_*), in launch_fleet_rows' place
+void launch_fleet_plan_mlp(const KParams<float> &P, const MlpParams &Q, const MlpParams *models, const FleetParams &F, hipStream_t s);
 void launch_mlp(const RolloutPlan &plan, const KParams<float> &P, const MlpParams &Q, const MlpParams *models, void *partials,
                 const MlpViz *viz, hipStream_t s);
 // the visualisation rollouts (mppi_differential_drive.py:144-159) with the learned model: opt [T][3], smp [K][T][3] (either

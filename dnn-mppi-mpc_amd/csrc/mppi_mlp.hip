@@ -167,6 +167,47 @@ __device__ __forceinline__ void mlp_controls_viz(const KParams<float> &P, const 
     clamp_controls(P, v0, v1);  // every row, the nominal one included (:148,:158)
 }
 
+// ---- fleet plans with the learned model (mppi_config.obstacle_motion = 3) --------------------------------------
+// The plan form's controls: row t of the agent's nominal sequence -- control t at step t, not the visualisation's (t - 1) mod T
+// --, clamped where the rollout clamps (perturb_clamp of an exploiting sample at zero noise).
+__device__ __forceinline__ void mlp_controls_plan(const KParams<float> &P, int t, float &v0, float &v1) {
+    v0 = P.u[2 * t];
+    v1 = P.u[2 * t + 1];
+    if (P.clamp_rollout) clamp_controls(P, v0, v1);
+}
+// agent a's clearance record, as k_fleet_rows and k_fleet_plan keep it (mppi_kernels.hip): lanes over the mates, their squared
+// centre distances in f64, one minimum; updated where F.count says that an iteration starts here (wave 0 of the agent's one
+// workgroup, stream order: a plain read-modify-write)
+__device__ __forceinline__ void fleet_clearance(const FleetParams &F, int a, int lane) {
+    const double *x0 = F.st[a].x0;
+    double d2 = INFINITY;
+    for (int m = lane; m < F.n_agents; m += 64) {
+        if (m == a) continue;
+        const double dx = F.st[m].x0[0] - x0[0], dy = F.st[m].x0[1] - x0[1];
+        d2 = fmin(d2, dx * dx + dy * dy);
+    }
+    d2 = wv::reduce<wv::OpMin>(d2);
+    if (F.count && lane == 0) {
+        FleetClear *q = F.clear + a;
+        const double d = sqrt(d2);
+        q->min_dist = fmin(q->min_dist, d);
+        if (d < F.contact) q->contact_iters += 1;
+    }
+}
+// the mates of `agent` at point j of their plans: the table and the threshold out of the handle's SceneTable, handed to
+// mates_collided through the two words the analytic plan mode reads them from (fleet_plan_table / fleet_plan_thr2) in a copy
+// of the parameters -- on a learned handle those words carry the table's address and the footprint word.  At a step every lane
+// reads the same point of mate a (j is uniform over the wave): from memory.  A null table (MPPI_FLEET_VELOCITY): no test.
+__device__ __forceinline__ bool mlp_mates_collided(const KParams<float> &P, float x, float y, float yaw, int agent, int j) {
+    const SceneTable<float> tb = *scene_table(P);
+    if (tb.plans == nullptr) return false;
+    KParams<float> PM = P;
+    PM.pad_scenes[0] = (long long)reinterpret_cast<uintptr_t>(tb.plans);
+    PM.pad_scenes[1] = 0;
+    __builtin_memcpy(&PM.pad_scenes[1], &tb.thr2, sizeof(float));
+    return mates_collided(PM, tb.plans, x, y, yaw, agent, j);
+}
+
 // ---- scene handles (mppi_config.obstacle_motion = 2) ----------------------------------------------------------
 // What wave 0 of a scene form carries across the step loop beside the moving table: the iteration counter the clocks count from
 // and its agent -- two scalar registers.  The descriptors themselves are NOT kept: held across the layers' GEMMs they cost the
@@ -176,8 +217,8 @@ struct MlpScene {
     long long iter;
     int agent;
 };
-// The agent's track and grid descriptors out of the handle's SceneTable (KParams::pad_scenes[0], OBS_MOTION_SCENE; `plans` is null
-// on a learned handle and not read), the two clocks and the footprint word (KParams::pad_scenes[1], learned_scene_footprint).
+// The agent's track and grid descriptors out of the handle's SceneTable (KParams::pad_scenes[0], OBS_MOTION_SCENE; `plans` is
+// read by the fleet forms alone, mlp_mates_collided), the two clocks and the footprint word (KParams::pad_scenes[1], learned_scene_footprint).
 // The step is uniform over the wave, so everything here but the grid's cells is: the uniform words go through readfirstlane
 // and sit in SGPRs.  A missing ingredient is a null table, trk_n == 0 or nx == 0.
 struct MlpSceneAt {
@@ -230,7 +271,10 @@ __device__ __forceinline__ MlpObs<SCENE> mlp_obs_load(const KParams<float> &P, c
 // at the state's position or under its outline -- and the terminal call prices the same state with j = T.  A state is hit when
 // any ingredient says so; weight g joins the stage cost behind the control term and the terminal cost, as Rollout::costs has
 // it (mppi_kernels.hip).
-template <bool SCENE>
+// FLEET (with SCENE; obstacle_motion = 3): behind the moving table, the tracks and the grid the state is tested against its
+// mates at point j of their plans (mlp_mates_collided; skipped at run time in velocity mode, where the mates are rows of the
+// moving table); the terminal call prices the same state, j = T.
+template <bool SCENE, bool FLEET = false>
 __device__ __forceinline__ void mlp_advance(const KParams<float> &P, const MlpObs<SCENE> &O, int c, int t, float r0, float r1, float r2,
                                             float u0, float u1, float v0, float v1, MlpLane &L) {
     const float *__restrict__ ref = P.ref;
@@ -266,6 +310,7 @@ __device__ __forceinline__ void mlp_advance(const KParams<float> &P, const MlpOb
                 hit |= g >= SC.grid.lethal;
                 wg = SC.grid.weight * g;
             }
+            if constexpr (FLEET) hit |= mlp_mates_collided(P, L.x, L.y, L.yaw, O.scene.agent, j);
         } else {
             hit = collided<false>(P, L.x, L.y, L.yaw, O.obs);
         }
@@ -785,13 +830,14 @@ __device__ __forceinline__ float *mlp_agent_records(const KParams<float> &P, flo
     return partials + (size_t)a * P.slots * record_len(P.T, 4);
 }
 
-// The f16-split kernels: eight wrappers around one textually included body (mppi_mlp_body.h, which lists what a wrapper has in
+// The f16-split kernels: twelve wrappers (the last four: the fleet forms) around one textually included body (mppi_mlp_body.h, which lists what a wrapper has in
 // scope).  The default-width family first: 512 x 3 and 512 x 2, NW waves on RT row tiles.
 template <bool VIZ, int NW, int RT, int TERMS = 3>
 __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3(const KParams<float> P, const MlpParams Q,
                                                                float *__restrict__ partials, const MlpViz V) {
     constexpr int H = MLP_H, scene_agent = 0;
-    constexpr bool SCENE = false, ONE_HIDDEN = false;
+    constexpr bool SCENE = false, ONE_HIDDEN = false, FLEET = false, PLAN = false;
+    const FleetParams F{};
 #include "mppi_mlp_body.h"
 }
 // several agents per launch, agent = blockIdx.y (grid (mlp_blocks(K, 64), n_agents)); no visualisation form.  `models`: every
@@ -802,7 +848,8 @@ __global__ __launch_bounds__(64 * NW, RT == 1 ? 2 : 1) void k_rollout_mlp_h3_age
                                                                       const MlpParams *__restrict__ models,
                                                                       float *__restrict__ partials_all) {
     constexpr int H = MLP_H, scene_agent = 0;
-    constexpr bool VIZ = false, SCENE = false, ONE_HIDDEN = false;
+    constexpr bool VIZ = false, SCENE = false, ONE_HIDDEN = false, FLEET = false, PLAN = false;
+    const FleetParams F{};
     const KParams<float> P = mlp_agent(P_all, (int)blockIdx.y);
     MlpParamsConst &Q = mlp_agent_model(models, (int)blockIdx.y);
     float *__restrict__ partials = mlp_agent_records(P_all, partials_all, (int)blockIdx.y);
@@ -822,7 +869,8 @@ template <int H, bool VIZ>
 __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w(const KParams<float> P, const MlpParams Q, float *__restrict__ partials,
                                                                      const MlpViz V) {
     constexpr int NW = H / 64, RT = 2, TERMS = 3, scene_agent = 0;
-    constexpr bool SCENE = false, ONE_HIDDEN = true;
+    constexpr bool SCENE = false, ONE_HIDDEN = true, FLEET = false, PLAN = false;
+    const FleetParams F{};
 #include "mppi_mlp_body.h"
 }
 // several agents per launch (see k_rollout_mlp_h3_agents)
@@ -831,7 +879,8 @@ __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_agents(co
                                                                             const MlpParams *__restrict__ models,
                                                                             float *__restrict__ partials_all) {
     constexpr int NW = H / 64, RT = 2, TERMS = 3, scene_agent = 0;
-    constexpr bool VIZ = false, SCENE = false, ONE_HIDDEN = true;
+    constexpr bool VIZ = false, SCENE = false, ONE_HIDDEN = true, FLEET = false, PLAN = false;
+    const FleetParams F{};
     const KParams<float> P = mlp_agent(P_all, (int)blockIdx.y);
     MlpParamsConst &Q = mlp_agent_model(models, (int)blockIdx.y);
     float *__restrict__ partials = mlp_agent_records(P_all, partials_all, (int)blockIdx.y);
@@ -848,14 +897,16 @@ __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_agents(co
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * 8, 1) void k_rollout_mlp_h3_scene(const KParams<float> P, const MlpParams Q, float *__restrict__ partials) {
     constexpr int H = MLP_H, NW = 8, RT = 2, TERMS = 3, scene_agent = 0;
-    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = false;
+    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = false, FLEET = false, PLAN = false;
+    const FleetParams F{};
     const MlpViz V{};
 #include "mppi_mlp_body.h"
 }
 __global__ __launch_bounds__(64 * 8, 1) void k_rollout_mlp_h3_scene_agents(const KParams<float> P_all, const MlpParams *__restrict__ models,
                                                                           float *__restrict__ partials_all) {
     constexpr int H = MLP_H, NW = 8, RT = 2, TERMS = 3;
-    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = false;
+    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = false, FLEET = false, PLAN = false;
+    const FleetParams F{};
     const int scene_agent = (int)blockIdx.y;
     const KParams<float> P = mlp_agent(P_all, scene_agent);
     MlpParamsConst &Q = mlp_agent_model(models, scene_agent);
@@ -866,7 +917,8 @@ __global__ __launch_bounds__(64 * 8, 1) void k_rollout_mlp_h3_scene_agents(const
 template <int H>
 __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_scene(const KParams<float> P, const MlpParams Q, float *__restrict__ partials) {
     constexpr int NW = H / 64, RT = 2, TERMS = 3, scene_agent = 0;
-    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = true;
+    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = true, FLEET = false, PLAN = false;
+    const FleetParams F{};
     const MlpViz V{};
 #include "mppi_mlp_body.h"
 }
@@ -875,11 +927,70 @@ __global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_scene_age
                                                                                   const MlpParams *__restrict__ models,
                                                                                   float *__restrict__ partials_all) {
     constexpr int NW = H / 64, RT = 2, TERMS = 3;
-    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = true;
+    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = true, FLEET = false, PLAN = false;
+    const FleetParams F{};
     const int scene_agent = (int)blockIdx.y;
     const KParams<float> P = mlp_agent(P_all, scene_agent);
     MlpParamsConst &Q = mlp_agent_model(models, scene_agent);
     float *__restrict__ partials = mlp_agent_records(P_all, partials_all, scene_agent);
+    const MlpViz V{};
+#include "mppi_mlp_body.h"
+}
+
+// ------------------------------------------------------------------------------------------
+// The fleet forms (mppi_config.obstacle_motion = 3): a batch whose agents see each other.  The rollout kernels are
+// the batched scene forms with FLEET = true: in velocity mode the mates are rows of the moving table (k_fleet_rows<float>), in
+// plan mode points of the plan table behind SceneTable::plans.  The plan kernels write that table: the body with PLAN = true,
+// one workgroup per agent (grid (1, n_agents)) with the agent's own model, at the front of every slot in k_fleet_plan's place.
+// One of each per width of the _w family and one of the 8-wave three-term _h3 family: ten symbols.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * 8, 1) void k_rollout_mlp_h3_fleet_agents(const KParams<float> P_all, const MlpParams *__restrict__ models,
+                                                                          float *__restrict__ partials_all) {
+    constexpr int H = MLP_H, NW = 8, RT = 2, TERMS = 3;
+    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = false, FLEET = true, PLAN = false;
+    const int scene_agent = (int)blockIdx.y;
+    const KParams<float> P = mlp_agent(P_all, scene_agent);
+    MlpParamsConst &Q = mlp_agent_model(models, scene_agent);
+    float *__restrict__ partials = mlp_agent_records(P_all, partials_all, scene_agent);
+    const MlpViz V{};
+    const FleetParams F{};
+#include "mppi_mlp_body.h"
+}
+template <int H>
+__global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_rollout_mlp_w_fleet_agents(const KParams<float> P_all,
+                                                                                  const MlpParams *__restrict__ models,
+                                                                                  float *__restrict__ partials_all) {
+    constexpr int NW = H / 64, RT = 2, TERMS = 3;
+    constexpr bool VIZ = false, SCENE = true, ONE_HIDDEN = true, FLEET = true, PLAN = false;
+    const int scene_agent = (int)blockIdx.y;
+    const KParams<float> P = mlp_agent(P_all, scene_agent);
+    MlpParamsConst &Q = mlp_agent_model(models, scene_agent);
+    float *__restrict__ partials = mlp_agent_records(P_all, partials_all, scene_agent);
+    const MlpViz V{};
+    const FleetParams F{};
+#include "mppi_mlp_body.h"
+}
+// the plan kernels: agent = blockIdx.y, its parameters and model as the batched rollouts see them; no records
+__global__ __launch_bounds__(64 * 8, 1) void k_fleet_plan_mlp_h3(const KParams<float> P_all, const MlpParams *__restrict__ models,
+                                                                const FleetParams F) {
+    constexpr int H = MLP_H, NW = 8, RT = 2, TERMS = 3;
+    constexpr bool VIZ = false, SCENE = false, ONE_HIDDEN = false, FLEET = false, PLAN = true;
+    const int scene_agent = (int)blockIdx.y;
+    const KParams<float> P = mlp_agent(P_all, scene_agent);
+    MlpParamsConst &Q = mlp_agent_model(models, scene_agent);
+    float *__restrict__ partials = nullptr;
+    const MlpViz V{};
+#include "mppi_mlp_body.h"
+}
+template <int H>
+__global__ __launch_bounds__(H, H == 256 ? 2 : 1) void k_fleet_plan_mlp_w(const KParams<float> P_all, const MlpParams *__restrict__ models,
+                                                                        const FleetParams F) {
+    constexpr int NW = H / 64, RT = 2, TERMS = 3;
+    constexpr bool VIZ = false, SCENE = false, ONE_HIDDEN = true, FLEET = false, PLAN = true;
+    const int scene_agent = (int)blockIdx.y;
+    const KParams<float> P = mlp_agent(P_all, scene_agent);
+    MlpParamsConst &Q = mlp_agent_model(models, scene_agent);
+    float *__restrict__ partials = nullptr;
     const MlpViz V{};
 #include "mppi_mlp_body.h"
 }
@@ -927,6 +1038,11 @@ template <int H> static WSceneKernels w_scene_rows() {
     return {{kfn(k_rollout_mlp_w_scene_agents<H>), KernelEntry("k_rollout_mlp_w_scene_agents<%d>", H), H, w_shmem(H)},
             {kfn(k_rollout_mlp_w_scene<H>), KernelEntry("k_rollout_mlp_w_scene<%d>", H), H, w_shmem(H)}};
 }
+struct WFleetKernels { MlpKernel rollout, plan; };  // the fleet handles' (obstacle_motion = 3)
+template <int H> static WFleetKernels w_fleet_rows() {
+    return {{kfn(k_rollout_mlp_w_fleet_agents<H>), KernelEntry("k_rollout_mlp_w_fleet_agents<%d>", H), H, w_shmem(H)},
+            {kfn(k_fleet_plan_mlp_w<H>), KernelEntry("k_fleet_plan_mlp_w<%d>", H), H, w_shmem(H)}};
+}
 struct WKernels { MlpKernel viz, agents, one; };
 template <int H> static WKernels w_rows() {
     return {{kfn(k_rollout_mlp_w<H, true>), KernelEntry("k_rollout_mlp_w<%d, true>", H), H, w_shmem(H)},
@@ -936,6 +1052,7 @@ template <int H> static WKernels w_rows() {
 // by width: 64, 128, 256, 512 (a further width is one more entry of each, and of plan_mlp's index)
 static WSceneKernels w_scene_kernels[] = {w_scene_rows<64>(), w_scene_rows<128>(), w_scene_rows<256>(), w_scene_rows<512>()};
 static WKernels w_kernels[] = {w_rows<64>(), w_rows<128>(), w_rows<256>(), w_rows<512>()};
+static WFleetKernels w_fleet_kernels[] = {w_fleet_rows<64>(), w_fleet_rows<128>(), w_fleet_rows<256>(), w_fleet_rows<512>()};
 // 512 x 3 and 512 x 2: the forms of k_rollout_mlp_h3, and the f32-input kernel
 enum { H3_VIZ_8, H3_VIZ_4, H3_AGENTS, H3_F32, H3_8_TERMS_2, H3_8, H3_4, H3_SCENE, H3_SCENE_AGENTS };
 static MlpKernel h3_kernels[] = {
@@ -951,8 +1068,11 @@ static MlpKernel h3_kernels[] = {
     {kfn(k_rollout_mlp_h3_scene), KernelEntry("k_rollout_mlp_h3_scene"), 64 * 8, h3_shmem(8, 2)},
     {kfn(k_rollout_mlp_h3_scene_agents), KernelEntry("k_rollout_mlp_h3_scene_agents"), 64 * 8, h3_shmem(8, 2)},
 };
+static MlpKernel h3_fleet_rollout = {kfn(k_rollout_mlp_h3_fleet_agents), KernelEntry("k_rollout_mlp_h3_fleet_agents"), 64 * 8, h3_shmem(8, 2)};
+static MlpKernel h3_fleet_plan = {kfn(k_fleet_plan_mlp_h3), KernelEntry("k_fleet_plan_mlp_h3"), 64 * 8, h3_shmem(8, 2)};
 
-RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const MlpViz *viz) {
+// `fleet`: a fleet handle (obstacle_motion = 3; always a batch): the fleet forms of the batched scene kernels
+RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const MlpViz *viz, bool fleet) {
     const bool f8 = (sw.mlp.form < 0 ? H3_FORM_DEFAULT : sw.mlp.form) == H3_FORM_8x64;
     const int agents = !viz && P.n_agents > 1 ? P.n_agents : 1;
     // a scene handle (obstacle_motion = 2: make_params marks its launches OBS_MOTION_SCENE) takes the scene form of its shape;
@@ -965,7 +1085,8 @@ RolloutPlan plan_mlp(const KParams<float> &P, const MlpParams &Q, const Switches
     // and batches take the default form (mppi_set_mlp refuses the f32-input cases for both), the visualisation rollouts the
     // f16-split kernel of the form whichever rollout kernel MPPI_MLP_F32 selects (both weight sets are packed)
     const bool batch = agents > 1;
-    MlpKernel &k = scene && h3 ? h3_kernels[batch ? H3_SCENE_AGENTS : H3_SCENE]
+    MlpKernel &k = scene && batch && fleet ? (h3 ? h3_fleet_rollout : w_fleet_kernels[wi].rollout)
+                   : scene && h3 ? h3_kernels[batch ? H3_SCENE_AGENTS : H3_SCENE]
                    : scene     ? (batch ? w_scene_kernels[wi].agents : w_scene_kernels[wi].one)
                    : !h3       ? (viz ? w_kernels[wi].viz : batch ? w_kernels[wi].agents : w_kernels[wi].one)
                    : viz       ? h3_kernels[f8 ? H3_VIZ_8 : H3_VIZ_4]
@@ -990,6 +1111,17 @@ void launch_mlp(const RolloutPlan &plan, const KParams<float> &P, const MlpParam
     void *args[] = {const_cast<KParams<float> *>(&P), agents ? (void *)&models : (void *)const_cast<MlpParams *>(&Q), &partials,
                     const_cast<MlpViz *>(viz ? viz : &none)};
     launch_plan(plan.k, args, s);  // (k_rollout_mlp and the _agents kernels take no MlpViz)
+}
+
+// The launch at the front of a learned fleet handle's slot in plan mode (F.plans set), in launch_fleet_rows' place: every
+// agent's plan through its own model, one workgroup per agent.  Q: the batch's shape (hidden, n_hidden).
+void launch_fleet_plan_mlp(const KParams<float> &P, const MlpParams &Q, const MlpParams *models, const FleetParams &F, hipStream_t s) {
+    const int wi = Q.hidden == 64 ? 0 : Q.hidden == 128 ? 1 : Q.hidden == 256 ? 2 : 3;
+    MlpKernel &k = mlp_shape_is_h3(Q.hidden, Q.n_hidden) ? h3_fleet_plan : w_fleet_kernels[wi].plan;
+    KernelLaunch l = k.plan();
+    l.grid = dim3(1, F.n_agents);
+    void *args[] = {const_cast<KParams<float> *>(&P), (void *)&models, const_cast<FleetParams *>(&F)};
+    launch_plan(l, args, s);
 }
 
 void launch_viz_mlp(const KParams<float> &P, const MlpParams &Q, const Switches &sw, const float *u_before, const float *u_upd,

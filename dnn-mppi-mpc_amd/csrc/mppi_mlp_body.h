@@ -1,6 +1,6 @@
 // mppi_mlp_body.h: the one body of every f16-split rollout kernel -- k_rollout_mlp_h3, k_rollout_mlp_w, their several-agents-
-// per-launch forms and their scene forms (mppi_mlp.hip): eight wrappers include it textually, so that each kernel compiles to
-// exactly the code it did as a self-contained kernel (an inlined __device__ body is optimised before it is inlined and changed
+// per-launch forms, their scene and fleet forms and the fleet's plan kernels (mppi_mlp.hip): wrappers include it textually, so
+// that each kernel compiles to exactly the code it did as a self-contained kernel (an inlined __device__ body is optimised before it is inlined and changed
 // the register allocation and scratch of 21 of the 29 kernels: DESIGN 3.6.3).  Not a header: no include guard, nothing else may
 // include it.  In scope at the point of inclusion:
 //   P, Q, partials, V   the kernel's (or this agent's) parameters, model, records and visualisation block
@@ -8,6 +8,10 @@
 //   VIZ, SCENE          the visualisation form; the scene form (moving table and MlpScene in `obs`, mlp_advance<true>)
 //   scene_agent         whose descriptors a scene form prices (0 where SCENE is false)
 //   ONE_HIDDEN          constexpr bool: n_hidden == 1 is admitted (the _w family; the _h3 kernels run 2 or 3 hidden layers)
+//   FLEET               constexpr bool: a scene form that also tests the mates' plans (mlp_advance<true, true>)
+//   PLAN, F             constexpr bool: the fleet's plan form -- every row of the tile carries this agent's NOMINAL sequence (control t
+//                       at step t, clamped where the rollout clamps), nothing is priced, lane 0 stores point t + 1 of the agent's
+//                       plan into F.plans and the clearance record follows the step loop; F: the launch's FleetParams (else unused)
 #ifdef MPPI_STAMPS
     unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_t = clock64();
 #endif
@@ -23,10 +27,11 @@
     float *ref_lds = zscale + M * 4;                                // [n_ref][4] when the path fits
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int k0 = ((int)blockIdx.x + (VIZ ? V.block0 : 0)) * M, k = k0 + lane;
-    const KParams<float> PL = mlp_stage_path(P, ref_lds, h3_ref_cap(RT, H));
+    // (the plan form prices nothing: it neither stages the path nor loads an obstacle table)
+    const KParams<float> PL = PLAN ? P : mlp_stage_path(P, ref_lds, h3_ref_cap(RT, H));
     const DevState sv = load_state(P, P.st);
-    const MlpObs<SCENE> obs = mlp_obs_load<SCENE>(P, sv, lane, scene_agent);  // what wave 0's advance call prices against
-    if (!VIZ && k0 + M <= sv.k_start) return;
+    const MlpObs<SCENE> obs = PLAN ? MlpObs<SCENE>{} : mlp_obs_load<SCENE>(P, sv, lane, scene_agent);  // what wave 0's advance call prices against
+    if (!VIZ && !PLAN && k0 + M <= sv.k_start) return;
     const bool in_tile = lane < M;  // (a 32-sample tile: the upper half of wave 0 carries no sample)
     const bool valid = in_tile && k < P.K, live = valid && k >= sv.k_start;
     // VIZ: the workgroup behind the samples' carries the nominal sequence in its lane 0
@@ -40,13 +45,19 @@
     const int n_steps = eval ? 1 : P.T;
     const bool exploit = (k + P.k_offset) < P.n_exploit;
     f32x16 acc[H / 64 / NW][RT][2];
+    PlanPoint<float> *plan_out = nullptr;
+    if constexpr (PLAN) {
+        plan_out = static_cast<PlanPoint<float> *>(F.plans) + (size_t)scene_agent * (P.T + 1);
+        if (threadIdx.x == 0) plan_out[0] = PlanPoint<float>{L.x, L.y};
+    }
     if (wid == 0 && in_tile) {  // the padding of the layer-0 rows stays zero
         for (int q = 0; q < H3_ZPITCH; ++q) { z_hi[lane * H3_ZPITCH + q] = (_Float16)0.f; z_lo[lane * H3_ZPITCH + q] = (_Float16)0.f; }
     }
     for (int t = 0; t < n_steps; ++t) {
         float u0 = 0, u1 = 0, v0 = 0, v1 = 0;
         if (wid == 0) {
-            if (eval) {
+            if constexpr (PLAN) mlp_controls_plan(P, t, v0, v1);
+            else if (eval) {
                 if (eval_row) { v0 = V.ev[2 * k]; v1 = V.ev[2 * k + 1]; }
             } else if (VIZ) mlp_controls_viz(P, V, k, t, smp_row, opt_row, exploit, v0, v1);
             else mlp_controls(P, iter, k, t, valid, exploit, u0, u1, v0, v1);
@@ -108,18 +119,23 @@
                 r1 += o.v[1];
                 r2 += o.v[2];
             }
-            if (VIZ) {
+            if constexpr (PLAN) {
+                mlp_euler(P, r0, r1, r2, v0, v1, L);
+                if (lane == 0) plan_out[t + 1] = PlanPoint<float>{L.x, L.y};
+            } else if (VIZ) {
                 mlp_euler(P, r0, r1, r2, v0, v1, L);
                 float *dst = eval_row ? V.eout + (size_t)k * 3
                              : opt_row ? V.opt + (size_t)t * 3 : smp_row ? V.smp + ((size_t)k * P.T + t) * 3 : nullptr;
                 if (dst) { dst[0] = L.x; dst[1] = L.y; dst[2] = L.yaw; }
             } else {
-                mlp_advance<SCENE>(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
+                mlp_advance<SCENE, FLEET>(PL, obs, c, t, r0, r1, r2, u0, u1, v0, v1, L);
             }
         }
         PH(9);
     }
-    if (!VIZ && wid == 0) mlp_record(P, partials, iter, k, c, valid, live, L, lane);
+    if constexpr (PLAN) {
+        if (wid == 0) fleet_clearance(F, scene_agent, lane);
+    } else if (!VIZ && wid == 0) mlp_record(P, partials, iter, k, c, valid, live, L, lane);
 #ifdef MPPI_STAMPS
     if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && wid == (NW > 1 ? 1 : 0))
         for (int i = 0; i < 10; ++i) g_mlp_phase[i] = ph[i];

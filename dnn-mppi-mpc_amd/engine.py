@@ -206,7 +206,8 @@ class Engine:
 
     def set_fleet_prediction(self, mode):
         """How a fleet handle predicts an agent's mates along the horizon: ``"velocity"`` (the default: constant velocity from
-        the mate rows) or ``"plan"`` (along each mate's own nominal rollout, made afresh at the start of every iteration);
+        the mate rows) or ``"plan"`` (along each mate's own nominal rollout, made afresh at the start of every iteration; on a
+        learned-dynamics fleet, ``model=MODEL_DIFFDRIVE_MLP, obstacle_motion=3``, through the mate's own network);
         mppi_set_fleet_prediction."""
         modes = {"velocity": capi.FLEET_VELOCITY, "plan": capi.FLEET_PLAN}
         if mode not in modes:

@@ -86,6 +86,8 @@ typedef enum { MPPI_OBSTACLE_NONE = 0, MPPI_OBSTACLE_CIRCLE = 1, MPPI_OBSTACLE_O
 
 /* mppi_config.obstacle_motion = 2: the learned model's scene handle (documented at the field) */
 #define MPPI_OBSTACLE_MOTION_LEARNED 2
+/* mppi_config.obstacle_motion = 3: the learned model's fleet handle -- a scene handle with fleet_radius > 0 (likewise) */
+#define MPPI_OBSTACLE_MOTION_LEARNED_FLEET 3
 
 /*
  * Mirrors the constructor keywords of MPPIAlgorithms (mppi_differential_drive.py:44-60,
@@ -174,13 +176,29 @@ typedef struct {
      * and their own models (mppi_set_agent_mlp).  Limits, each MPPI_ERR_UNSUPPORTED: fleet_radius > 0 (the mates' plans are
      * rolled out with analytic dynamics), K_global > K (sharding), and on such a handle the f32-input model cases of
      * mppi_set_mlp (MPPI_MLP_F32=1, weights beyond the f16 range): the scene is priced by the f16-split kernels only, and
-     * MPPI_MLP_FORM / MPPI_MLP_TERMS do not apply.  f64 is refused for the learned model as before. */
+     * MPPI_MLP_FORM / MPPI_MLP_TERMS do not apply.  f64 is refused for the learned model as before.  The fleet_radius refusal
+     * keeps its answer (callers probe for it) and points to value 3.
+     * 3 (MPPI_OBSTACLE_MOTION_LEARNED_FLEET): THE LEARNED MODEL'S FLEET HANDLE, a value-2 handle whose agents see each other.
+     * Accepted with MPPI_MODEL_DIFFDRIVE_MLP, n_agents from 2 to 256, fleet_radius > 0, an obstacle model, f32 and K_global = K.
+     * Refused before the device is looked for: an analytic model, fleet_radius = 0 or n_agents < 2 (MPPI_ERR_BAD_ARG);
+     * n_agents > 256, sharding, f64 (MPPI_ERR_UNSUPPORTED); and whatever a learned batch refuses (the sequential index, the
+     * f32-input model cases, more than 512 records per agent).  Everything a value-2 batch takes keeps working: a model per agent
+     * or one for all, own circles with velocities, tracks and a grid under the exclusivity rules of the analytic fleet handles
+     * (with the mates' plans: mppi_set_scene_mode(MPPI_SCENE_COMPOSED)), mppi_set_fleet_prediction, mppi_get_fleet_plans,
+     * mppi_get_agent_circles, mppi_get_fleet_clearance, mppi_run_closed_loop, graph capture, mppi_set_iteration.
+     *   MPPI_FLEET_VELOCITY (the default): the mate rows documented at fleet_radius, word for word -- the speed is row 0 of the
+     *   mate's nominal sequence, clamped; THE RESIDUAL DOES NOT ENTER the constant-velocity prediction.
+     *   MPPI_FLEET_PLAN: point 0 of agent a's plan is its (x, y), point j its position after Euler steps of f + ITS OWN MLP with
+     *   rows 0 .. j - 1 of its nominal sequence (control t at step t), clamped where the rollout clamps, in the learned rollout's
+     *   own arithmetic -- one launch of one workgroup per agent in front of the rollout launch, inside a captured graph.
+     * A library without value 3 refuses it with MPPI_ERR_BAD_ARG whatever the model; MPPI_ABI_VERSION stays 8. */
     int32_t obstacle_motion;
     int32_t reserved0;
     /* Fleet avoidance.  0: off (zero-initialised configs: as before).  > 0: every agent of the handle sees every other agent
      * (its "mates") as a moving circle of this radius, written on the device at the start of every iteration -- no host round
      * trip, no re-upload.  Needs n_agents >= 2 and obstacle_motion = 1 (else MPPI_ERR_BAD_ARG), and with obstacle_motion an
-     * obstacle model, an analytic dynamics model, T <= 128 and K <= 8192; n_agents <= 256 (more: MPPI_ERR_UNSUPPORTED);
+     * obstacle model, an analytic dynamics model (the learned model: obstacle_motion = 3, documented there), T <= 128 and
+     * K <= 8192; n_agents <= 256 (more: MPPI_ERR_UNSUPPORTED);
      * negative or non-finite: MPPI_ERR_BAD_ARG.  All of it is refused before the device is looked for.
      * THE MATE ROWS.  At the start of every iteration mppi_run_closed_loop runs, before that iteration's rollout launch, agent
      * b's obstacle table is its own circles (mppi_set_obstacles[_moving] / mppi_set_agent_obstacles[_moving], unchanged, in
